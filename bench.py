@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the GDMCF diffusion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload yelp|amazon-book]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload yelp|amazon-book] [--dump-outputs DIR] [--full]
 
 One "step" = the body of the reference training loop (main.py:345-351): zero_grad ->
 GaussianDiffusion.training_losses -> mean -> backward -> AdamW.step on one batch of 400 dense user
@@ -9,11 +9,15 @@ rows resident in HBM.  Metric: training users/sec (BASELINE.json), fp32, synthet
 (the reference ships no dataset), random-init weights.  N > 1: one process per GPU (torchrun), each
 rank takes its own 400-row batch (weak scaling), gradients all-reduced with RCCL.
 
-Besides the contract fields the JSON line carries
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = wall time of one
+timed step).  --dump-outputs DIR also writes what the last timed step computed (dump_outputs below).
+--full adds everything beyond the headline figure, as the default line carried it before:
   roofline     -- the dominant kernel's achieved rate, timed live with HIP events on the launch
                   stream inside the timed region (gdmcf_prof_*), against the gfx950 peak;
   cpu_baseline -- the oracle (a PyTorch-CPU restatement of the reference path, parity-pinned to
-                  the reference by tests/golden) timed on this host's cores on the same workload.
+                  the reference by tests/golden) timed on this host's cores on the same workload;
+  the SpMM, sampling, other-optimiser-placement, hipGraph and configs[2] legs, and at N > 1 the replica
+  check and the strong-scaling leg.
 
 Other legs / variants (not part of the default line): --gemm-dtype bf16 (BASELINE configs[2]), --workload
 amazon-book|stress, --fuse-optimizer (AdamW inside the weight-gradient GEMM epilogues, N = 1), --allreduce-optimizer (N > 1: plain
@@ -81,7 +85,7 @@ def live_traffic(kernel_tag, argv):
         if skip_next:
             skip_next = False
             continue
-        if a in ("--steps", "--warmup", "--preheat-seconds", "--cpu-seconds", "--gpus"):
+        if a in ("--steps", "--warmup", "--preheat-seconds", "--cpu-seconds", "--gpus", "--dump-outputs"):
             skip_next = True
             continue
         keep.append(a)
@@ -114,7 +118,7 @@ def live_traffic(kernel_tag, argv):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
@@ -144,7 +148,7 @@ def parse():
                          "from starting behind the previous one: ~5 us per launch, ~80 us per bracketed step (rocprofv3 kernel "
                          "trace, profiles/README.md) -- every 4th step still inflates the line by 1.5 %%.  0 (default) = three "
                          "bracketed steps spread over the timed region (every max(4, ceil(steps / 3))th step)")
-    ap.add_argument("--spmm", action="store_true", help="(default on) time the LightGCN SpMM, reported under 'spmm'")
+    ap.add_argument("--spmm", action="store_true", help="(on with --full) time the LightGCN SpMM, reported under 'spmm'")
     ap.add_argument("--no-spmm", action="store_true", help="skip the LightGCN SpMM leg")
     ap.add_argument("--spmm-only", action="store_true",
                     help="time ONLY the LightGCN propagation of --workload (yelp / amazon-book / stress: BASELINE configs[4]'s 1.2 M-node "
@@ -191,12 +195,19 @@ def parse():
                          "happens by default when N > 1 and neither variant is requested)")
     ap.add_argument("--allreduce-optimizer", action="store_true",
                     help="N > 1: all-reduce of the gradients + full AdamW on every rank instead of the sharded optimiser")
-    ap.add_argument("--sampling", action="store_true", help="(default on) time p_sample + masked top-k, reported under 'sampling'")
+    ap.add_argument("--sampling", action="store_true", help="(on with --full) time p_sample + masked top-k, reported under 'sampling'")
     ap.add_argument("--no-sampling", action="store_true", help="skip the evaluation-path leg")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure: HIP-event kernel table and roofline (with its "
+                         "rocprofv3 child passes), CPU baseline, the SpMM / sampling / other-optimiser-placement / hipGraph / "
+                         "configs[2] legs, and at N > 1 the replica check and the strong-scaling leg.  Without it the run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args(argv)
     if args.strong and not args.global_batch:
         args.global_batch = 400
-    default_line = args.backbone == "dnn" and not args.rehearse_dp
+    default_line = args.full and args.backbone == "dnn" and not args.rehearse_dp
     # single GPU, plain denoiser: AdamW of the two large weights runs inside their weight-gradient products unless asked otherwise
     args.fuse_main = (args.gpus == 1 and args.backbone == "dnn" and not args.rehearse_dp and not args.separate_optimizer) \
         or args.fuse_optimizer
@@ -330,6 +341,30 @@ def prof_stride(steps, asked=0):
     brackets cost ~80 us per step (each event pair holds the next launch back ~5 us); the kernels' averages need a handful of
     samples, not a quarter of the steps."""
     return max(1, asked) if asked > 0 else max(4, -(-steps // 3))
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of a larger parameter
+DUMP_LIMIT = 64 << 20  # bytes of all dumped arrays together
+
+
+def dump_outputs(out_dir, loss, model):
+    """What the timed path hands its caller after its last step: the step's loss (float64, `loss.npy`) and every parameter as
+    the optimiser left it (float32, `param.<name>.npy`).  A parameter of more than DUMP_SAMPLE elements is written as a fixed,
+    seeded sample of its flat elements (sorted indices, the same for every run of the same shapes).  Returns {name: array}."""
+    arrays = {"loss": loss.detach().double().cpu().numpy().reshape(-1)}
+    for name, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays["param." + name] = flat.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return arrays
 
 
 def physical_cores():
@@ -468,7 +503,8 @@ def main():
     lo = rank * n_pool * B
     sub_ptr = indptr[lo:lo + n_pool * B + 1] - indptr[lo]
     sub_idx = indices[indptr[lo]:indptr[lo + n_pool * B]]
-    x_host = data.dense_batches(sub_ptr, sub_idx, I, B, n_pool)  # only for the CPU baseline / sampling legs
+    dense_legs = args.full or args.sampling  # only the CPU baseline / sampling legs read dense host rows
+    x_host = data.dense_batches(sub_ptr, sub_idx, I, B, n_pool) if dense_legs else None
     # the interaction matrix is resident in HBM as CSR before the timed region; every step densifies its own
     # 400 rows on the device (gdmcf_densify_rows_f32) -- the batch provider is part of the step
     import scipy.sparse as sp
@@ -476,7 +512,7 @@ def main():
     dcsr = DeviceCSR(sp.csr_matrix((np.ones(len(sub_idx), np.float32), sub_idx, sub_ptr), shape=(n_pool * B, I)), dev)
     row_ids = [torch.arange(i * B, (i + 1) * B, device=dev) for i in range(n_pool)]
     x_buf = torch.empty(B, I, dtype=torch.float32, device=dev)
-    x_dev = torch.from_numpy(x_host[:1]).to(dev)
+    x_dev = torch.from_numpy(x_host[:1]).to(dev) if dense_legs else None
     # what the step is handed: the rows left sparse (default for the plain denoiser: the CSR-fed input builder and the bitmap
     # loss target, gdmcf_amd.data_utils.CsrBatch -- bit-identical to the dense path), or densified on the device first
     # (--dense-rows; always for the one-hot backbones, which read the dense row)
@@ -567,7 +603,8 @@ def main():
                            chosen="sharded" if sharded else "allreduce")
         if failed:
             dp_autotune["sharded_error"] = failed
-    prof = not args.no_prof
+    # HIP-event brackets (the kernel table and the roofline) with --full, or when a bracket stride is asked for
+    prof = not args.no_prof and (args.full or args.prof_every > 0)
     every = prof_stride(args.steps, args.prof_every)
     n_profiled = len(range(0, args.steps, every)) if prof else 0
     t0 = time.perf_counter()
@@ -588,9 +625,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t)
 
+    if args.dump_outputs and rank == 0:
+        step.flush()
+        dump_outputs(args.dump_outputs, loss, model)
+
     # ---- data parallel: every replica must hold bit-identical parameters after the run (outside the timed region) ----
     in_sync = None
-    if dist.is_initialized():
+    if dist.is_initialized() and args.full:
         step.flush()
         cs = torch.stack([p.detach().double().sum() for p in model.parameters()] +
                          [p.detach().double().abs().max() for p in model.parameters()])
@@ -616,7 +657,7 @@ def main():
 
     # ---- N > 1: strong-scaling leg (BASELINE configs[3] as stated: global batch 400 split over the ranks) ----
     strong_leg = None
-    if world > 1 and not strong and not args.no_strong_leg and 400 % world == 0:
+    if args.full and world > 1 and not strong and not args.no_strong_leg and 400 % world == 0:
         Bs = 400 // world
         ids_s = [r[:Bs] for r in row_ids]
         xs_buf = torch.empty(Bs, I, dtype=torch.float32, device=dev)
@@ -642,7 +683,7 @@ def main():
     # same update rule, bit-identical weights by test; opt-in because `.grad` of the two big weights is then never
     # materialised).  Reported beside the main line, which keeps backward(); optimizer.step() as the reference's loop. ----
     fused_leg = separate_leg = None
-    if world == 1 and args.backbone == "dnn" and not args.rehearse_dp and not args.no_fused_leg:
+    if args.full and world == 1 and args.backbone == "dnn" and not args.rehearse_dp and not args.no_fused_leg:
         if fuse_main:
             opt.fuse_into_backward(model, min_numel=1 << 62)  # off: the separate pass
         else:
@@ -677,7 +718,7 @@ def main():
     # With --rehearse-dp (one-rank RCCL group) the captured body includes every collective of the data-parallel step; at N > 1
     # the leg is opt-in (--graph-dp): all ranks capture the same collectives.
     graph_dp = (args.rehearse_dp and world == 1) or (world > 1 and args.graph_dp)
-    if (world == 1 or graph_dp) and args.backbone == "dnn" and sparse_rows \
+    if (args.full or args.graph_dp) and (world == 1 or graph_dp) and args.backbone == "dnn" and sparse_rows \
             and (not args.rehearse_dp or graph_dp) and not args.no_graph_leg:
         from gdmcf_amd.graph import GraphedTrainStep
         try:
@@ -745,7 +786,7 @@ def main():
         k0 = klist[0]
         tag0 = k0["kernel"].split(" + ")[0]
         traffic, traffic_note = (None, "off (--no-live-traffic)")
-        if world == 1 and rank == 0 and not args.no_live_traffic and not args.rehearse_dp:
+        if args.full and world == 1 and rank == 0 and not args.no_live_traffic and not args.rehearse_dp:
             traffic, traffic_note = live_traffic(tag0, sys.argv[1:])
         if traffic is None:
             t2, n2 = measured_traffic(tag0, args.workload, args.gemm_dtype)
@@ -765,14 +806,14 @@ def main():
 
     # ---- N = 1, default line: BASELINE configs[2] (Amazon-Book shape, bf16 GEMM inputs) so that the driver's record carries it ----
     configs2_leg = None
-    if world == 1 and default_line_only(args) and not args.no_configs2_leg:
+    if args.full and world == 1 and default_line_only(args) and not args.no_configs2_leg:
         try:
             configs2_leg = bench_configs2(gdmcf_amd, lib, dev, args.steps, max(3, args.warmup // 4), preheat_seconds=args.preheat_seconds)
         except Exception as exc:  # reported, never fatal for the main line
             configs2_leg = dict(error=f"{type(exc).__name__}: {exc}"[:300])
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, I, x_host, args.cpu_seconds)
 
     if rank == 0:
@@ -801,7 +842,7 @@ def main():
             "rehearsal": ("ranks share the visible GPU(s), gloo group with host-staged collectives (GDMCF_BENCH_SHARE_GPU=1): "
                           "launcher / step rehearsal, not a measurement") if (share and world > 1) else None,
             "replicas_in_sync": in_sync, "dp_autotune": dp_autotune, "strong_scaling": strong_leg, "fused_optimizer_leg": fused_leg, "separate_optimizer_leg": separate_leg, "graph_leg": graph_leg, "f32x3_leg": x3_leg,
-            "configs2_leg": configs2_leg,
+            "configs2_leg": configs2_leg, "full": args.full,
             "ranks_in_group": dist.get_world_size() if dist.is_initialized() else 1,
             "optimizer": "FusedAdamW" + (" inside the weight-gradient products of the two large weights (optimiser stream interleaved "
                                          "into their k loops); separate pass for the small tensors" if fuse_main else

@@ -1449,15 +1449,15 @@ def test_fused_optimizer_row_epilogue_matches_separate_pass(shape, dtype):
 
 
 def test_bench_emits_the_contract_line():
-    """bench.py prints ONE JSON line with the driver's contract fields, the roofline object of the dominant kernel
-    (HIP-event timing inside the run) and, with the default flags, a cpu_baseline object."""
+    """bench.py --full prints ONE JSON line with the driver's contract fields, the roofline object of the dominant kernel
+    (HIP-event timing inside the run) and, with the other flags at their defaults, a cpu_baseline object."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "2", "--cpu-seconds", "1"],
-                       capture_output=True, text=True, cwd=root, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "2", "--cpu-seconds", "1",
+                        "--full"], capture_output=True, text=True, cwd=root, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -1481,11 +1481,11 @@ def test_bench_emits_the_contract_line():
     assert abs(d["value"] - 400 * 8 / (d["ms_per_step"] * 8e-3)) / d["value"] < 1e-3
     assert cb["physical_cores"] is None or cb["physical_cores"] >= 1
     assert cb["one_thread"]["value"] > 0  # the one-thread orientation figure of BASELINE.md section 3
-    # the SpMM and the evaluation path are part of the default line (north_star sets a target on the SpMM)
+    # the SpMM and the evaluation path are part of the --full line (north_star sets a target on the SpMM)
     sp = d["spmm"]
     assert sp["bound"] == "hbm" and sp["ms_per_layer"] > 0 and abs(sp["frac"] - sp["achieved"] / sp["peak"]) < 1e-3
     assert d["sampling"]["users_per_s"] > 0 and d["ranks_in_group"] == 1
-    # BASELINE configs[2] (Amazon-Book shape, bf16 GEMM inputs) rides in the default line so the driver's record carries it
+    # BASELINE configs[2] (Amazon-Book shape, bf16 GEMM inputs) rides in the --full line so the driver's record carries it
     c2 = d["configs2_leg"]
     assert "error" not in c2, c2
     assert c2["dtype"] == "bf16" and c2["n_items"] == 94949 and c2["ms_per_step"] > 0 and c2["users_per_s"] > 0
@@ -1497,6 +1497,42 @@ def test_bench_emits_the_contract_line():
         r2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
                             capture_output=True, text=True, cwd=root, timeout=600)
         assert r2.returncode != 0 and "{" not in r2.stdout
+
+
+def test_bench_plain_run_times_only_the_main_line_and_dumps_its_last_step(tmp_path):
+    """bench.py without --full: the contract fields, exactly --steps timed steps, none of the extra legs; --dump-outputs writes
+    the last timed step's loss and parameters (float32 / float64, at most 64 MB), the same in two runs of the same command."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, cwd=root, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["metric"] == "training users/sec" and d["unit"] == "users/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 5 and d["warmup"] == 2 and d["full"] is False
+    assert abs(d["value"] - 400 * 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-3
+    for k in ("roofline", "cpu_baseline", "separate_optimizer_leg", "graph_leg", "configs2_leg"):
+        assert d[k] is None, k
+    assert d["kernels"] == [] and "spmm" not in d and "sampling" not in d
+    got = {}
+    for tag in ("a", "b"):
+        files = sorted(os.listdir(tmp_path / tag))
+        assert "loss.npy" in files and any(f.startswith("param.") for f in files), files
+        got[tag] = {f: np.load(tmp_path / tag / f) for f in files}
+    assert sum(a.nbytes for a in got["a"].values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in got["a"].values())
+    assert float(got["a"]["loss.npy"][0]) == d["final_loss"]
+    assert got["a"].keys() == got["b"].keys()
+    for f, a in got["a"].items():
+        np.testing.assert_array_equal(got["b"][f], a, err_msg=f)
 
 
 @pytest.mark.gpu

@@ -126,7 +126,7 @@ def test_bench_gpus_2_end_to_end_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--workload", "tiny",
-           "--hidden", "96", "--graph-dp", "--preheat-seconds", "0.05"]
+           "--hidden", "96", "--graph-dp", "--preheat-seconds", "0.05", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

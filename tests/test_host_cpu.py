@@ -644,3 +644,27 @@ def test_fuse_into_backward_seats_weight_rows_on_128_byte_lines(tmp_path, monkey
     monkeypatch.setenv("GDMCF_ALIGN_ROWS", "0")
     opt.fuse_into_backward(m, min_numel=1 << 12)
     assert all(w.is_contiguous() for w in ws) and m.engine.fused_opt is opt
+
+
+def test_bench_plain_run_defaults_and_output_dump(tmp_path):
+    """bench.py's extra legs are off unless --full asks for them; dump_outputs writes the loss (float64) and every parameter
+    (float32), a fixed seeded sample of the large ones, the same arrays for the same model."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and a.full is False and a.dump_outputs is None
+    assert not a.spmm and not a.sampling
+    f = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert f.full and f.spmm and f.sampling and f.dump_outputs == str(tmp_path)
+    torch.manual_seed(0)
+    m = torch.nn.Linear(1100, 1000)  # weight: 1.1 M elements, more than DUMP_SAMPLE
+    out = bench.dump_outputs(str(tmp_path / "o"), torch.tensor(0.25, dtype=torch.float32), m)
+    assert sorted(os.listdir(tmp_path / "o")) == ["loss.npy", "param.bias.npy", "param.weight.npy"]
+    assert np.load(tmp_path / "o" / "loss.npy").dtype == np.float64 and float(out["loss"][0]) == 0.25
+    b = np.load(tmp_path / "o" / "param.bias.npy")
+    assert b.dtype == np.float32 and np.array_equal(b, m.bias.detach().numpy())
+    w = np.load(tmp_path / "o" / "param.weight.npy")
+    idx = np.unique(np.random.default_rng(0).integers(0, m.weight.numel(), bench.DUMP_SAMPLE))
+    assert w.dtype == np.float32 and len(w) <= bench.DUMP_SAMPLE
+    assert np.array_equal(w, m.weight.detach().numpy().reshape(-1)[idx])
+    again = bench.dump_outputs(str(tmp_path / "o2"), torch.tensor(0.25), m)
+    assert all(np.array_equal(again[k], v) for k, v in out.items())
