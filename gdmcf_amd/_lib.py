@@ -63,6 +63,10 @@ _SIGNATURES = {
     "gdmcf_tanh_bwd_f32": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, c_int, c_int, P, c_int64, P]),
     "gdmcf_gather_rows_f32": (c_int, [P, c_int64, P, c_int, c_int, P, c_int64, P]),
     "gdmcf_scatter_add_rows_f32": (c_int, [P, c_int64, P, c_int, c_int, P, c_int64, P]),
+    "gdmcf_normalize_rows_bwd_adamw_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, P, c_int64, P, P, c_float, c_float,
+                                                   c_float, c_float, c_float, c_int, c_float, P]),
+    "gdmcf_scatter_rows_adamw_f32": (c_int, [P, c_int64, P, c_int, c_int, c_int, P, c_int64, P, P, c_float, c_float, c_float,
+                                             c_float, c_float, c_int, c_float, P]),
     "gdmcf_dp_pack_f64": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, P, P]),
     "gdmcf_dp_unpack_f64": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
     "gdmcf_randn_f32": (c_int, [P, c_int64, c_int, c_int, c_int, c_uint64, c_uint64, P]),

@@ -530,14 +530,23 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict_
 
 // dX = (dY - Y * <dY, Y>) * inv_norm  for Y = X / |X| (row-wise); dX may alias dY.  Rows of up to 4096 columns stay in
 // registers between the dot product and the update (each operand is read once); longer rows are read twice.
+// ADAM_: dX is not stored; it is the gradient of the AdamW update of X itself (row stride ldx, moments on the same stride),
+// applied element by element in the same pass.  Both instances form dX with the same expressions in the same reduction
+// order (the path is picked from `cols` alone), so the fused update sees exactly the gradient the plain instance stores.
+template <bool ADAM_>
 __global__ __launch_bounds__(256) void normalize_rows_bwd_kernel(const float* __restrict__ dY, int64_t lddy,
                                                                 const float* __restrict__ Y, int64_t ldy,
                                                                 const float* __restrict__ inv_norm, int cols,
-                                                                float* __restrict__ dX, int64_t lddx) {
+                                                                float* __restrict__ dX, int64_t lddx,
+                                                                float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+                                                                GdAdamHyper h, const GdStepState* step_state) {
     __shared__ float red[4];
+    if (ADAM_ && step_state) h = step_state->hyper;  // graph mode: this step's scalars from the device
     const float* dy = dY + (int64_t)blockIdx.x * lddy;
     const float* y = Y + (int64_t)blockIdx.x * ldy;
     float* dx = dX + (int64_t)blockIdx.x * lddx;
+    float* mr = ADAM_ ? exp_avg + (int64_t)blockIdx.x * lddx : nullptr;
+    float* vr = ADAM_ ? exp_avg_sq + (int64_t)blockIdx.x * lddx : nullptr;
     const float rn = inv_norm[blockIdx.x];
     if (cols <= 4096 && (cols & 3) == 0) {
         typedef f32x4 f32x4_u4 __attribute__((aligned(4)));
@@ -557,14 +566,39 @@ __global__ __launch_bounds__(256) void normalize_rows_bwd_kernel(const float* __
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int c = (threadIdx.x + 256 * k) * 4;
-            if (c < cols) *reinterpret_cast<f32x4_u4*>(dx + c) = (a[k] - b[k] * dot) * rn;
+            if (c >= cols) continue;
+            const f32x4 g = (a[k] - b[k] * dot) * rn;
+            if (!ADAM_) {
+                *reinterpret_cast<f32x4_u4*>(dx + c) = g;
+                continue;
+            }
+            f32x4 pp = *reinterpret_cast<const f32x4_u4*>(dx + c);
+            f32x4 mm = *reinterpret_cast<const f32x4_u4*>(mr + c);
+            f32x4 vv = *reinterpret_cast<const f32x4_u4*>(vr + c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float pj = pp[j], mj = mm[j], vj = vv[j];
+                gd_adam_elem(pj, g[j], mj, vj, h);
+                pp[j] = pj;
+                mm[j] = mj;
+                vv[j] = vj;
+            }
+            *reinterpret_cast<f32x4_u4*>(dx + c) = pp;
+            *reinterpret_cast<f32x4_u4*>(mr + c) = mm;
+            *reinterpret_cast<f32x4_u4*>(vr + c) = vv;
         }
         return;
     }
     float dot = 0.f;
     for (int c = threadIdx.x; c < cols; c += 256) dot += dy[c] * y[c];
     dot = block_sum_256(dot, red);
-    for (int c = threadIdx.x; c < cols; c += 256) dx[c] = (dy[c] - y[c] * dot) * rn;
+    for (int c = threadIdx.x; c < cols; c += 256) {
+        const float g = (dy[c] - y[c] * dot) * rn;
+        if (ADAM_)
+            gd_adam_elem(dx[c], g, mr[c], vr[c], h);
+        else
+            dx[c] = g;
+    }
 }
 
 __global__ __launch_bounds__(256) void tanh_bwd_kernel(const float* __restrict__ dA, int64_t ldd, const float* __restrict__ A,
@@ -593,6 +627,66 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const float* __re
     const float* s = src + (int64_t)blockIdx.x * lds;
     float* d = dst + index[blockIdx.x] * ldd;
     for (int c = threadIdx.x; c < cols; c += 256) atomicAdd(d + c, s[c]);  // (rows of one batch are distinct users)
+}
+
+// One pass over ALL rows of an embedding table W [rows, cols] (row stride ldw; exp_avg / exp_avg_sq on the same stride):
+// AdamW with the dense gradient that scatter_add_rows would build in a zeroed table -- row index[j] takes 0 + src[j, :],
+// every other row takes 0 (torch.optim.AdamW moves those rows too).  A workgroup owns SCATTER_ADAM_ROWS consecutive rows
+// and finds the batch rows that land there by one scan of `index` (ids distinct within the batch, as above).
+constexpr int SCATTER_ADAM_ROWS = 16;
+
+__global__ __launch_bounds__(256) void scatter_rows_adamw_kernel(const float* __restrict__ src, int64_t lds,
+                                                                const int64_t* __restrict__ index, int n, int rows, int cols,
+                                                                float* __restrict__ W, int64_t ldw, float* __restrict__ exp_avg,
+                                                                float* __restrict__ exp_avg_sq, GdAdamHyper h,
+                                                                const GdStepState* step_state) {
+    __shared__ int slot[SCATTER_ADAM_ROWS];
+    if (step_state) h = step_state->hyper;  // graph mode: this step's scalars from the device
+    const int64_t r0 = (int64_t)blockIdx.x * SCATTER_ADAM_ROWS;
+    if (threadIdx.x < SCATTER_ADAM_ROWS) slot[threadIdx.x] = -1;
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const int64_t r = index[j] - r0;
+        if (r >= 0 && r < SCATTER_ADAM_ROWS) slot[r] = j;
+    }
+    __syncthreads();
+    const int nr = (int)min((int64_t)SCATTER_ADAM_ROWS, rows - r0);
+    const bool vec = ((cols | ldw | lds) & 3) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(exp_avg) |
+                       reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0;
+    if (vec) {
+        const int c4 = cols >> 2;
+        for (int it = threadIdx.x; it < nr * c4; it += 256) {
+            const int rr = it / c4, c = (it - rr * c4) * 4;
+            const int j = slot[rr];
+            const int64_t o = (r0 + rr) * ldw + c;
+            f32x4 gg = {0.f, 0.f, 0.f, 0.f};
+            if (j >= 0) gg = gg + *reinterpret_cast<const f32x4*>(src + (int64_t)j * lds + c);  // 0 + g: the zeroed table's sum
+            f32x4 pp = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(W + o));
+            f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(exp_avg + o));
+            f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(exp_avg_sq + o));
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float pq = pp[q], mq = mm[q], vq = vv[q];
+                gd_adam_elem(pq, gg[q], mq, vq, h);
+                pp[q] = pq;
+                mm[q] = mq;
+                vv[q] = vq;
+            }
+            __builtin_nontemporal_store(pp, reinterpret_cast<f32x4*>(W + o));
+            __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(exp_avg + o));
+            __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(exp_avg_sq + o));
+        }
+        return;
+    }
+    for (int it = threadIdx.x; it < nr * cols; it += 256) {
+        const int rr = it / cols, c = it - rr * cols;
+        const int j = slot[rr];
+        const int64_t o = (r0 + rr) * ldw + c;
+        float g = 0.f;
+        if (j >= 0) g = g + src[(int64_t)j * lds + c];
+        gd_adam_elem(W[o], g, exp_avg[o], exp_avg_sq[o], h);
+    }
 }
 
 __global__ void emb_cols_kernel(const int64_t* __restrict__ ts, const float* __restrict__ emb_w,
@@ -1238,9 +1332,25 @@ int gdmcf_normalize_rows_bwd_f32(const float* dY, int64_t lddy, const float* Y, 
                                  int cols, float* dX, int64_t lddx, void* stream) {
     GD_CHECK_SHAPE(rows > 0 && cols > 0 && lddy >= cols && ldy >= cols && lddx >= cols, "normalize_rows_bwd: bad shape");
     GD_CHECK_ARG(dY && Y && inv_norm && dX, "normalize_rows_bwd: null pointer");
-    hipLaunchKernelGGL(normalize_rows_bwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dY, lddy, Y, ldy, inv_norm,
-                       cols, dX, lddx);
+    hipLaunchKernelGGL(normalize_rows_bwd_kernel<false>, dim3(rows), dim3(256), 0, (hipStream_t)stream, dY, lddy, Y, ldy,
+                       inv_norm, cols, dX, lddx, nullptr, nullptr, GdAdamHyper{}, nullptr);
     return gd_launch_status("normalize_rows_bwd");
+}
+
+int gdmcf_normalize_rows_bwd_adamw_f32(const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* inv_norm,
+                                       int rows, int cols, float* X, int64_t ldx, float* exp_avg, float* exp_avg_sq, float lr,
+                                       float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                       void* stream) {
+    GD_CHECK_SHAPE(rows > 0 && cols > 0 && lddy >= cols && ldy >= cols && ldx >= cols, "normalize_rows_bwd_adamw: bad shape");
+    GD_CHECK_ARG(dY && Y && inv_norm && X && exp_avg && exp_avg_sq && step >= 1, "normalize_rows_bwd_adamw: null pointer");
+    const GdAdamHyper h = gd_adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale);
+    {
+        // algorithmic bytes: read dY, Y, X, m, v; write X, m, v
+        GdProfScope prof(6, 32.0 * (double)rows * cols, (hipStream_t)stream);
+        hipLaunchKernelGGL(normalize_rows_bwd_kernel<true>, dim3(rows), dim3(256), 0, (hipStream_t)stream, dY, lddy, Y, ldy,
+                           inv_norm, cols, X, ldx, exp_avg, exp_avg_sq, h, t_gd_step_state);
+    }
+    return gd_launch_status("normalize_rows_bwd_adamw");
 }
 
 int gdmcf_tanh_bwd_f32(const float* dA, int64_t ldd, const float* A, int64_t lda, const float* extra, int64_t lde,
@@ -1266,6 +1376,21 @@ int gdmcf_scatter_add_rows_f32(const float* src, int64_t lds, const int64_t* ind
     GD_CHECK_ARG(src && index && dst, "scatter_add_rows: null pointer");
     hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, src, lds, index, cols, dst, ldd);
     return gd_launch_status("scatter_add_rows");
+}
+
+int gdmcf_scatter_rows_adamw_f32(const float* src, int64_t lds, const int64_t* index, int n, int rows, int cols, float* W,
+                                 int64_t ldw, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int step, float grad_scale, void* stream) {
+    GD_CHECK_SHAPE(n >= 0 && rows > 0 && cols > 0 && ldw >= cols && (n == 0 || lds >= cols), "scatter_rows_adamw: bad shape");
+    GD_CHECK_ARG(W && exp_avg && exp_avg_sq && (n == 0 || (src && index)) && step >= 1, "scatter_rows_adamw: null pointer");
+    const GdAdamHyper h = gd_adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale);
+    {
+        // algorithmic bytes: read W, m, v; write W, m, v (the batch rows' gradient is noise beside them)
+        GdProfScope prof(6, 24.0 * (double)rows * cols, (hipStream_t)stream);
+        hipLaunchKernelGGL(scatter_rows_adamw_kernel, dim3(gd_cdiv(rows, SCATTER_ADAM_ROWS)), dim3(256), 0, (hipStream_t)stream,
+                           src, lds, index, n, rows, cols, W, ldw, exp_avg, exp_avg_sq, h, t_gd_step_state);
+    }
+    return gd_launch_status("scatter_rows_adamw");
 }
 
 int gdmcf_rowscale_f32(const float* A, int64_t lda, const float* rowscale, int M, int K, float* out, int64_t ldo,

@@ -48,6 +48,8 @@ class _OneHotTrainLoss(torch.autograd.Function):
 class OneHotEngine:
     _eps_target = DenoiserEngine._eps_target  # (target, alpha, rowdiv) of the eps parameterisation: one launch
     supports_grad_sink = True  # parallel.DataParallelStep may install `grad_sink` (overlapped gradient exchange)
+    # single-GPU optimiser-in-backward (FusedAdamW.fuse_into_backward): the weights it took over are updated by the kernel
+    # that forms their gradient (see _fused_state); ignored while a data-parallel grad_sink is installed
     fused_opt = None
 
     def __init__(self, model):
@@ -81,8 +83,9 @@ class OneHotEngine:
         out = [(l.weight, l.bias, 1 if i != n_out - 1 else 0) for i, l in enumerate(m.out_layers)]
         for w, b, _ in br1 + br2 + out:
             _lib.require_gpu(w, "DNNOneHot parameters")
-            if not (w.is_contiguous() and b.is_contiguous() and w.dtype == torch.float32):
-                raise RuntimeError("gdmcf_amd: DNNOneHot parameters must be contiguous float32")
+            # (rows of a weight may lie further apart than its columns: FusedAdamW.fuse_into_backward seats them on 128-byte lines)
+            if not (w.stride(1) == 1 and w.stride(0) >= w.shape[1] and b.is_contiguous() and w.dtype == torch.float32):
+                raise RuntimeError("gdmcf_amd: DNNOneHot parameters must be float32 with contiguous rows")
         return br1, br2, out
 
     def buffers(self, B, device):
@@ -276,17 +279,34 @@ class OneHotEngine:
             return bufs.gradcoef * gloss
         return (gloss.to(torch.float32) * bufs.gradcoef).contiguous()
 
-    def _weight_grad(self, bufs, B, w, bias, dz_ptr, lddz, rs, A_ptr, lda):
-        """(dW, db) of one layer -- or (None, None) once handed to the data-parallel gradient sink."""
+    def _fused_state(self, w):
+        """FusedAdamW.fused_state(w) when the fused optimiser took `w` over (then the caller updates w in the kernel that
+        forms its gradient, after every other reader of w in this backward), else None."""
+        fused = self.fused_opt if self.grad_sink is None else None
+        fs = fused.fused_state(w) if fused is not None else None
+        if fs is not None and (fs["exp_avg"].stride() != w.stride() or fs["exp_avg_sq"].stride() != w.stride()):
+            raise RuntimeError("gdmcf_amd: the moments of a fused weight must share its leading dimension")
+        return fs
+
+    def _weight_grad(self, bufs, B, w, bias, dz_ptr, lddz, rs, A_ptr, lda, fs=None):
+        """(dW, db) of one layer -- or (None, None) once handed to the data-parallel gradient sink, or (None, db) when
+        `fs` (_fused_state(w)) is given: w and its moments are then updated in the product's epilogue."""
         lib, st = self.lib, _lib.stream_ptr()
         N, K = w.shape
-        dW = torch.empty_like(w)
         db = torch.empty_like(bias) if bias is not None else None
         scol = 0
         if rs is not None:  # (rs . dZ)^T A == dZ^T (rs . A): scale the small activation instead of the big dZ
             _lib.check(lib.gdmcf_rowscale_f32(A_ptr, lda, rs.data_ptr(), B, K, bufs.hs.data_ptr(), bufs.hs.stride(0), st))
             A_ptr, lda = bufs.hs.data_ptr(), bufs.hs.stride(0)
             scol = int(lda > K)  # the copy's column K then holds the row scale: db comes out of the product
+        if fs is not None:
+            _lib.check(lib.gdmcf_linear_bwd_weight_adamw_f32(
+                dz_ptr, lddz, A_ptr, lda, _lib.ptr(rs), scol, B, N, K, w.data_ptr(), w.stride(0), fs["exp_avg"].data_ptr(),
+                fs["exp_avg_sq"].data_ptr(), _lib.ptr(db), fs["lr"], fs["beta1"], fs["beta2"], fs["eps"], fs["weight_decay"],
+                fs["step"], fs["grad_scale"], st))
+            torch.autograd.graph.increment_version(w)  # updated through a raw pointer
+            return None, db
+        dW = torch.empty_like(w)
         _lib.check(lib.gdmcf_linear_bwd_weight_f32(dz_ptr, lddz, A_ptr, lda, _lib.ptr(rs), scol, B, N, K, dW.data_ptr(),
                                                    dW.stride(0), _lib.ptr(db), 0, st))
         if self.grad_sink is not None and bias is not None:
@@ -301,25 +321,33 @@ class OneHotEngine:
 
     def _branch_backward(self, bufs, B, chain, acts, dzs, xin, ldx, I_cols, dz_ptr, lddz):
         """One input branch from d(pre-activation of its last layer): hidden layers, then the timestep-embedding columns
-        of its first layer.  Returns ([(dW, db)...], dWe, dbe)."""
+        of its first layer.  Returns ([(dW, db)...], dWe, dbe).  A fused weight's product (which overwrites W) runs after
+        the kernel that reads W: the input gradient, or the embedding backward's read of the first layer's E columns."""
         m = self.model
         grads = [None] * len(chain)
         dWe = dbe = None
         for li in range(len(chain) - 1, -1, -1):
             w, bias, _ = chain[li]
             N, K = w.shape
+            fs = self._fused_state(w)
             if li > 0:
                 A_prev = acts[li - 1]
-                grads[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, None, A_prev.data_ptr(), A_prev.stride(0))
+                if fs is None:
+                    grads[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, None, A_prev.data_ptr(), A_prev.stride(0))
                 self._input_grad(bufs, B, w.data_ptr(), w.stride(0), N, K, dz_ptr, lddz, None, A_prev.data_ptr(),
                                  A_prev.stride(0), chain[li - 1][2], dzs[li - 1].data_ptr(), dzs[li - 1].stride(0))
+                if fs is not None:
+                    grads[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, None, A_prev.data_ptr(), A_prev.stride(0), fs)
                 dz_ptr, lddz = dzs[li - 1].data_ptr(), dzs[li - 1].stride(0)
             else:
-                grads[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, None, xin.data_ptr(), ldx)
+                if fs is None:
+                    grads[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, None, xin.data_ptr(), ldx)
                 dWe, dbe = torch.empty_like(m.emb_layer.weight), torch.empty_like(m.emb_layer.bias)
                 _lib.check(self.lib.gdmcf_emb_bwd_f32(dz_ptr, lddz, w.data_ptr(), w.stride(0), I_cols, self.E,
                                                       bufs.temb.data_ptr(), B, N, bufs.demb.data_ptr(), dWe.data_ptr(),
                                                       dbe.data_ptr(), _lib.stream_ptr()))
+                if fs is not None:
+                    grads[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, None, xin.data_ptr(), ldx, fs)
         return grads, dWe, dbe
 
     def _branches_backward(self, bufs, B, br1, br2):
@@ -357,9 +385,13 @@ class OneHotEngine:
                 A_prev, act_prev, dprev = bufs.acts_out[li - 1], out[li - 1][2], bufs.dz_out[li - 1]
             else:
                 A_prev, act_prev, dprev = bufs.hcat, 1, bufs.dhcat  # both branches end in tanh
-            g_out[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, rs, A_prev.data_ptr(), A_prev.stride(0))
+            fs = self._fused_state(w)
+            if fs is None:
+                g_out[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, rs, A_prev.data_ptr(), A_prev.stride(0))
             self._input_grad(bufs, B, w.data_ptr(), w.stride(0), w.shape[0], w.shape[1], dz_ptr, lddz, rs, A_prev.data_ptr(),
                              A_prev.stride(0), act_prev, dprev.data_ptr(), dprev.stride(0))
+            if fs is not None:  # (after the input gradient, which reads w)
+                g_out[li] = self._weight_grad(bufs, B, w, bias, dz_ptr, lddz, rs, A_prev.data_ptr(), A_prev.stride(0), fs)
             dz_ptr, lddz, rs = dprev.data_ptr(), dprev.stride(0), None
         res = self._branches_backward(bufs, B, br1, br2)
         for g in g_out:
@@ -472,6 +504,10 @@ class DNNOneHot(nn.Module):
 
     def param_list(self):
         return list(self.parameters())
+
+    def fusable_weights(self):
+        """The 2-D weights FusedAdamW.fuse_into_backward may update inside the backward pass (DNN: layer_list())."""
+        return [l.weight for l in list(self.in_layers) + list(self.in_layers2) + list(self.out_layers)]
 
     def forward(self, x, timesteps, x_U, drop_mask=None, drop_mask_U=None, posterior=None):
         """model(x_t, t, x_tU) of the reference's evaluation path.  Training goes through

@@ -132,10 +132,21 @@ class OneHotEmbeddingEngine(OneHotEngine):
         else:
             gc = (0.1 * gloss.sum()).to(torch.float32).reshape(1)
         V, Wu = m.embedding_item.weight, m.embedding_user.weight
+        # fused optimiser: neither table is read again in this backward (the products below read Vhat), so each is updated
+        # by the pass that forms its gradient
+        fsV, fsU = self._fused_state(V), self._fused_state(Wu)
         # scores = uhat @ Vhat^T: gradient w.r.t. Vhat, then through V / |v|
         dV, _ = self._weight_grad(bufs, B, V, None, bufs.diff.data_ptr(), bufs.ldi, rs, bufs.uhat.data_ptr(), bufs.uhat.stride(0))
-        _lib.check(lib.gdmcf_normalize_rows_bwd_f32(dV.data_ptr(), dV.stride(0), bufs.Vhat.data_ptr(), bufs.Vhat.stride(0),
-                                                    bufs.rn_v.data_ptr(), self.I, bufs.D, dV.data_ptr(), dV.stride(0), st))
+        if fsV is None:
+            _lib.check(lib.gdmcf_normalize_rows_bwd_f32(dV.data_ptr(), dV.stride(0), bufs.Vhat.data_ptr(), bufs.Vhat.stride(0),
+                                                        bufs.rn_v.data_ptr(), self.I, bufs.D, dV.data_ptr(), dV.stride(0), st))
+        else:
+            _lib.check(lib.gdmcf_normalize_rows_bwd_adamw_f32(
+                dV.data_ptr(), dV.stride(0), bufs.Vhat.data_ptr(), bufs.Vhat.stride(0), bufs.rn_v.data_ptr(), self.I, bufs.D,
+                V.data_ptr(), V.stride(0), fsV["exp_avg"].data_ptr(), fsV["exp_avg_sq"].data_ptr(), fsV["lr"], fsV["beta1"],
+                fsV["beta2"], fsV["eps"], fsV["weight_decay"], fsV["step"], fsV["grad_scale"], st))
+            torch.autograd.graph.increment_version(V)  # (also what rebuilds the cached V / |v| at the next forward)
+            dV = None
         # ... w.r.t. uhat, then through u / |u|
         self._input_grad(bufs, B, bufs.Vhat.data_ptr(), bufs.Vhat.stride(0), self.I, bufs.D, bufs.diff.data_ptr(), bufs.ldi, rs,
                          bufs.ucat.data_ptr(), bufs.ucat.stride(0), 0, bufs.du.data_ptr(), bufs.du.stride(0))
@@ -143,10 +154,19 @@ class OneHotEmbeddingEngine(OneHotEngine):
                                                     bufs.uhat.stride(0), bufs.rn_u.data_ptr(), B, bufs.D, bufs.du.data_ptr(),
                                                     bufs.du.stride(0), st))
         self._extra_grads = self._user_vector_backward(bufs, B)
-        # user rows: scatter into the dense table gradient (torch.optim.AdamW on nn.Embedding sees a dense gradient too)
-        dWu = torch.zeros_like(Wu)
-        _lib.check(lib.gdmcf_scatter_add_rows_f32(bufs.du.data_ptr() + 4 * bufs.h12, bufs.du.stride(0), index.data_ptr(), B,
-                                                  bufs.eu, dWu.data_ptr(), dWu.stride(0), st))
+        # user rows: scatter into the dense table gradient (torch.optim.AdamW on nn.Embedding sees a dense gradient too) --
+        # or, fused, one AdamW pass over the whole table that takes the batch rows' gradient straight from du
+        if fsU is None:
+            dWu = torch.zeros_like(Wu)
+            _lib.check(lib.gdmcf_scatter_add_rows_f32(bufs.du.data_ptr() + 4 * bufs.h12, bufs.du.stride(0), index.data_ptr(), B,
+                                                      bufs.eu, dWu.data_ptr(), dWu.stride(0), st))
+        else:
+            _lib.check(lib.gdmcf_scatter_rows_adamw_f32(
+                bufs.du.data_ptr() + 4 * bufs.h12, bufs.du.stride(0), index.data_ptr(), B, Wu.shape[0], bufs.eu, Wu.data_ptr(),
+                Wu.stride(0), fsU["exp_avg"].data_ptr(), fsU["exp_avg_sq"].data_ptr(), fsU["lr"], fsU["beta1"], fsU["beta2"],
+                fsU["eps"], fsU["weight_decay"], fsU["step"], fsU["grad_scale"], st))
+            torch.autograd.graph.increment_version(Wu)
+            dWu = None
         # hidden activations: + NT-Xent gradient, times tanh'
         cg = sv["closs_grad"]
         _lib.check(lib.gdmcf_tanh_bwd_f32(bufs.du.data_ptr(), bufs.du.stride(0), bufs.ucat.data_ptr(), bufs.ucat.stride(0),
@@ -219,6 +239,11 @@ class DNNOneHotEmbedding(DNNOneHot):
         if self._engine is None:
             self._engine = OneHotEmbeddingEngine(self)
         return self._engine
+
+    def fusable_weights(self):
+        """As DNNOneHot's, without `out_layers` (never applied, no gradient), with the two embedding tables."""
+        return ([l.weight for l in list(self.in_layers) + list(self.in_layers2)]
+                + [self.embedding_item.weight, self.embedding_user.weight])
 
     @torch.no_grad()
     def load_lightgcn_embeddings(self, lightgcn, users=True, items=True):

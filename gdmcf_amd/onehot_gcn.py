@@ -88,12 +88,21 @@ class OneHotGCNEngine(OneHotEmbeddingEngine):
         def layer_backward(conv, dz, A, dA):
             w, bias = conv.lin.weight, conv.bias
             N, K = w.shape
-            dW, db = torch.empty_like(w), torch.empty_like(bias)
-            _lib.check(lib.gdmcf_linear_bwd_weight_f32(dz.data_ptr(), dz.stride(0), A.data_ptr(), A.stride(0), None, 0, B, N, K,
-                                                       dW.data_ptr(), dW.stride(0), db.data_ptr(), 0, st))
+            fs = self._fused_state(w)
+            dW, db = None, torch.empty_like(bias)
+            if fs is None:
+                dW = torch.empty_like(w)
+                _lib.check(lib.gdmcf_linear_bwd_weight_f32(dz.data_ptr(), dz.stride(0), A.data_ptr(), A.stride(0), None, 0, B, N,
+                                                           K, dW.data_ptr(), dW.stride(0), db.data_ptr(), 0, st))
             _lib.check(lib.gdmcf_linear_bwd_input_f32(dz.data_ptr(), dz.stride(0), w.data_ptr(), w.stride(0), None, A.data_ptr(),
                                                       A.stride(0), 0, B, N, K, dA.data_ptr(), dA.stride(0), bufs.ws.data_ptr(),
                                                       bufs.ws_bytes, st))
+            if fs is not None:  # fused optimiser: after the input gradient, which reads w
+                _lib.check(lib.gdmcf_linear_bwd_weight_adamw_f32(
+                    dz.data_ptr(), dz.stride(0), A.data_ptr(), A.stride(0), None, 0, B, N, K, w.data_ptr(), w.stride(0),
+                    fs["exp_avg"].data_ptr(), fs["exp_avg_sq"].data_ptr(), db.data_ptr(), fs["lr"], fs["beta1"], fs["beta2"],
+                    fs["eps"], fs["weight_decay"], fs["step"], fs["grad_scale"], st))
+                torch.autograd.graph.increment_version(w)
             grads[w], grads[bias] = dW, db
 
         if m.gcn_layers == 2:
@@ -167,3 +176,7 @@ class DNNOneHotEmbeddingGCN(DNNOneHotEmbedding):
         if self._engine is None:
             self._engine = OneHotGCNEngine(self)
         return self._engine
+
+    def fusable_weights(self):
+        convs = [] if self.gcn_layers == 0 else [self.gcn_model.conv1] + ([self.gcn_model.conv2] if self.gcn_layers == 2 else [])
+        return super().fusable_weights() + [conv.lin.weight for conv in convs]

@@ -26,6 +26,13 @@ def _seat_rows(t, ld):
     return out
 
 
+def _fusable(model):
+    """The weights fuse_into_backward may take over: fusable_weights() (one-hot backbones), else layer_list() (DNN)."""
+    if hasattr(model, "fusable_weights"):
+        return list(model.fusable_weights())
+    return [w for (w, _, _) in model.layer_list()]
+
+
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False):
         if amsgrad:
@@ -43,9 +50,11 @@ class FusedAdamW(torch.optim.Optimizer):
 
     # -- optimiser-in-backward (single GPU, opt-in) -------------------------------------------------------------
     def fuse_into_backward(self, model, min_numel=1 << 20, align_rows=None):
-        """Update the large 2-D weights of `model` (a gdmcf_amd.DNN) inside the epilogue of their weight-gradient
-        GEMM instead of in step(): the gradient tile never leaves the MFMA accumulators, the separate AdamW pass over
-        those tensors disappears (32 -> 24 B/param of HBM traffic).  The update rule and the resulting weights /
+        """Update the large 2-D weights of `model` (a gdmcf_amd.DNN: its layer_list(); a one-hot backbone: its
+        fusable_weights()) inside the epilogue of their weight-gradient GEMM instead of in step(): the gradient tile never
+        leaves the MFMA accumulators, the separate AdamW pass over those tensors disappears (32 -> 24 B/param of HBM
+        traffic).  The two embedding tables of DNNOneHotEmbedding(GCN) have no such product; their update is fused into the
+        pass that forms their gradient instead (gdmcf_normalize_rows_bwd_adamw_f32 / gdmcf_scatter_rows_adamw_f32).  The update rule and the resulting weights /
         moments are the same as step()'s.  Consequences: `.grad` of those weights stays None, exactly one
         backward per step() (no gradient accumulation), not for data parallel (gradients must be all-reduced
         first; DataParallelStep switches it off).  Returns self.
@@ -61,9 +70,10 @@ class FusedAdamW(torch.optim.Optimizer):
         if align_rows is None:
             align_rows = os.environ.get("GDMCF_ALIGN_ROWS", "1") != "0"
         mine = {id(p) for g in self.param_groups for p in g["params"]}
-        self._fused_ids = {id(w) for (w, _, _) in model.layer_list() if w.numel() >= min_numel and id(w) in mine}
+        cands = _fusable(model)
+        self._fused_ids = {id(w) for w in cands if w.numel() >= min_numel and id(w) in mine}
         with torch.no_grad():
-            for (w, _, _) in model.layer_list():
+            for w in cands:
                 if id(w) not in mine or w.dim() != 2:
                     continue
                 k = w.shape[1]

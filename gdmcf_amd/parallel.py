@@ -173,7 +173,7 @@ class DataParallelStep:
         if self.exchange:
             diffusion.update_history = False  # replayed below on the gathered global batch
             optimizer.grad_scale = 1.0 / self.world
-            if hasattr(optimizer, "unfuse") and hasattr(model, "layer_list"):
+            if hasattr(optimizer, "unfuse") and (hasattr(model, "layer_list") or hasattr(model, "fusable_weights")):
                 optimizer.unfuse(model)  # gradients must be all-reduced before the update (and collectives want contiguous weights)
             model.engine.fused_opt = None
             if hasattr(optimizer, "_fused_ids"):

@@ -51,7 +51,7 @@ int gdmcf_debug_last_gemm(void);
  * calls; gdmcf_prof_collect synchronises them and returns (tag, milliseconds, work) triples,
  * where work = algorithmic FLOPs (GEMM tags) or bytes (HBM-bound tags) of that launch.
  * Tags: 1 linear_fwd gemm, 2 loss_fwd gemm, 3 posterior gemm, 4 bwd_input gemm, 5 bwd_weight gemm,
- * 6 adamw, 7 prep_input, 8 spmm, 9 topk.
+ * 6 adamw (also normalize_rows_bwd_adamw / scatter_rows_adamw), 7 prep_input, 8 spmm, 9 topk.
  * on: 1 = record, 2 = pause (stop recording, keep the records), 0 = off and discard.           */
 int gdmcf_prof_enable(int on);
 int gdmcf_prof_collect(int cap, int* tags_host, float* ms_host, double* work_host);
@@ -297,6 +297,25 @@ int gdmcf_gather_rows_f32(const float* src, int64_t lds, const int64_t* index, i
                           int64_t ldd, void* stream);
 int gdmcf_scatter_add_rows_f32(const float* src, int64_t lds, const int64_t* index, int n, int cols,
                                float* dst, int64_t ldd, void* stream);
+/* Optimiser-in-backward for the two embedding tables of the indexIn backbones (FusedAdamW.fuse_into_backward).  Both
+ * apply torch.optim.AdamW's single-tensor math for step number `step` -- the element function, scalars and grad_scale
+ * of gdmcf_adamw_f32 / gdmcf_linear_bwd_weight_adamw_f32 -- to a table whose gradient is never materialised; the
+ * table and its moments share one row stride (ldx / ldw).  Results are bit-identical to the two-pass sequences named.
+ *   normalize_rows_bwd_adamw: the gradient of X is normalize_rows_bwd's dX (same reduction order) for Y = X/|X|:
+ *                       X, exp_avg, exp_avg_sq updated in one pass (== normalize_rows_bwd into a buffer, then
+ *                       gdmcf_adamw_f32).  dY, Y, inv_norm must not alias X or the moments.
+ *   scatter_rows_adamw: every one of the `rows` rows of W is updated; row index[j] (j < n) with gradient src[j, :],
+ *                       every other row with gradient 0 (== zero a dense gradient, gdmcf_scatter_add_rows_f32 into it,
+ *                       then gdmcf_adamw_f32).  The ids of one call must be distinct (as scatter_add_rows assumes);
+ *                       ids outside [0, rows) are ignored.  n == 0: every row takes gradient 0. */
+int gdmcf_normalize_rows_bwd_adamw_f32(const float* dY, int64_t lddy, const float* Y, int64_t ldy,
+                                       const float* inv_norm, int rows, int cols, float* X, int64_t ldx,
+                                       float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
+                                       float eps, float weight_decay, int step, float grad_scale, void* stream);
+int gdmcf_scatter_rows_adamw_f32(const float* src, int64_t lds, const int64_t* index, int n, int rows, int cols,
+                                 float* W, int64_t ldw, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                                 float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                 void* stream);
 /* Gradients of the timestep-embedding branch (models/DNN.py:73-74,78):
  *   demb[m,e] = sum_n dZ1[m,n]*W1[n, I+e] ;  dWe = demb^T @ temb ;  dbe = sum_m demb
  * demb_ws: float32 scratch of (M + N) * E elements.                                         */
