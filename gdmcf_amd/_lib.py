@@ -52,6 +52,7 @@ _SIGNATURES = {
     "gdmcf_linear_bwd_weight_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, P, c_int64, P, c_int, P]),
     "gdmcf_linear_bwd_weight_adamw_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, P, c_int64, P, P, P, c_float,
                                                   c_float, c_float, c_float, c_float, c_int, c_float, P]),
+    "gdmcf_linear_bwd_weight_adamw_multi_f32": (c_int, [P, c_int, P]),
     "gdmcf_rowscale_f32": (c_int, [P, c_int64, P, c_int, c_int, P, c_int64, P]),
     "gdmcf_emb_bwd_f32": (c_int, [P, c_int64, P, c_int64, c_int, c_int, P, c_int, c_int, P, P, P, P]),
     "gdmcf_row_loss_finish_f64": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),
@@ -98,6 +99,15 @@ _SIGNATURES = {
     "gdmcf_scale_f32": (c_int, [P, c_int64, c_float, P, P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+
+class GdDwAdamw(ctypes.Structure):
+    """One entry of gdmcf_linear_bwd_weight_adamw_multi_f32's list (include/gdmcf_hip.h): the arguments of one
+    gdmcf_linear_bwd_weight_adamw_f32 call."""
+    _fields_ = [("dZ", c_void_p), ("lddz", c_int64), ("A", c_void_p), ("lda", c_int64), ("rowscale", c_void_p),
+                ("a_scale_col", c_int), ("M", c_int), ("N", c_int), ("K", c_int), ("W", c_void_p), ("ldw", c_int64),
+                ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("db", c_void_p), ("lr", c_float), ("beta1", c_float),
+                ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float), ("step", c_int), ("grad_scale", c_float)]
 
 _lib = None
 

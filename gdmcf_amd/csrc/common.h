@@ -182,6 +182,9 @@ int gd_gemm_small_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s);
 // direct-to-register f32 products (gemm_dr.hip): GD_DR_NOT_TAKEN = not a product / shape it handles, fall back to the LDS-tiled kernels
 enum { GD_DR_NOT_TAKEN = 1 };
 int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s);
+// n (<= 4) fused-AdamW weight-gradient products (as gd_gemm_dr_launch takes them, GD_EPI_ADAMW) in ONE launch; GD_DR_NOT_TAKEN and
+// nothing launched unless the kernel takes every one of them with the same reduction length
+int gd_gemm_dr_adamw_multi(GdGemm* gs, int n, hipStream_t s);
 int gd_gemm_tile_m(int shape_class);
 int gd_gemm_tile_n(int shape_class);
 int gd_gemm_bk(int layA, int layB);

@@ -85,6 +85,33 @@ struct DrArgs {
     int stagger;  // waves 4-7 of a workgroup start this many x 3.4 us later
 };
 
+// One weight-gradient product with its AdamW update, as dr_tn_adamw_kernel takes it: C = W[M, N] = A[K, M]^T B[K, N] (N counts
+// the bias column when there is one), exp_avg / exp_avg_sq beside W with W's leading dimension.
+struct DrAdamProd {
+    const float* A;
+    const float* B;
+    float* W;
+    float* ea;    // exp_avg
+    float* ea2;   // exp_avg_sq
+    float* bias;  // bias gradient (column N - 1 of the product), or NULL
+    int lda, ldb, ldc;
+    int M, N, K;
+    int tiles_m, tiles_n, m_fastest;
+    const GdAdamHyper* adam_dev;  // this step's scalars in device memory (graph replay), NULL = adam
+    GdAdamHyper adam;
+};
+constexpr int DR_MULTI_MAX = 4;
+// Several such products in ONE launch: one tile queue over all of them (a queue serves its panels of product 0, then of product
+// 1, ...), so the launch has one ramp, one final stream drain and one ragged last round however many products it holds.  Every
+// product runs the same k-steps per tile (the same reduction length: the batch).
+struct DrMultiArgs {
+    DrAdamProd p[DR_MULTI_MAX];
+    int n;        // products
+    int ksp;      // k-steps run per tile (a multiple of the ring size)
+    int ctr;      // index into g_dr_ticket
+    int stagger;  // waves 4-7 of a workgroup start this many x 3.4 us later
+};
+
 // C[M,N] = A[K,M]^T * B[K,N], both operands row-contiguous.  TA / TB: 64-row load units per operand and k-step.
 template <int TA, int TB, int D, int EPI>
 __global__ __launch_bounds__(512, 2) void dr_tn_kernel(const DrArgs d) {
@@ -329,6 +356,13 @@ __global__ __launch_bounds__(512, 2) void dr_tn_kernel(const DrArgs d) {
 // system contention, not the counter.  profiles/r04_fused_stream_ablations.txt, section G.)
 // Tiles whose lanes do not all own a full 16-byte group (the last column panel when N % 64 != 0, or with the bias column) are
 // updated on the spot from the accumulators, as in round 3 (1/16 of the Yelp output-layer tiles, 1/538 of the first layer's).
+//
+// One launch takes up to DR_MULTI_MAX products (DrMultiArgs; a single product is the one-element case).  A launch pays at its
+// ends: each wave's first tile runs with no stream beside it, its last tile's stream runs after the k loops with the matrix pipe
+// idle, and the last round of tiles is ragged.  With all products behind one queue those ends are paid once: the last tile of
+// product p a wave draws is streamed inside the k loop of its first tile of product p + 1.  The tile a virtual id names
+// (dr_vtile) carries its product, so the three kinds of per-tile state each follow their own tile -- the load cursor's operand
+// descriptors, the k loop's tile (its end-of-tile path), and the pending tile's W / moment descriptors and AdamW scalars.
 // ---------------------------------------------------------------------------------------------------------------------
 #ifdef GD_NO_SNOP  // (probe builds only: the build's lint rejects the kernel without the guard)
 #define GD_SNOP ""
@@ -381,8 +415,13 @@ __device__ __forceinline__ void dr_load0_rw(f32x4& v, i32x4 srd, uint32_t voff) 
 #endif
 }
 
+// virtual tile id of a multi-product launch: the product in bits 24.., the product's own tile number below (numbered as in
+// dr_tn_kernel); DR_VT_PARK: no tile
+constexpr int DR_VT_SHIFT = 24;
+constexpr int DR_VT_PARK = 0x7fffffff;
+
 template <int D, bool NTL>
-__global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
+__global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrMultiArgs d) {
     constexpr int LPS = 2;  // ring loads per k-step
     constexpr int R = D + 1;
     // the optimiser stream's schedule inside a ring round: slot A is consumed AND reloaded in step UA, slot B in step UB -- a row
@@ -393,26 +432,41 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
     static_assert(UB < R && UB > UA, "two distinct steps of a round");
     static_assert(LPS * R + XS <= 63, "vmcnt is a 6-bit counter");
     constexpr uint32_t PARK = 0xFFFFFF00u;  // outside every descriptor
-    const GdGemm& g = d.g;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, q = lane >> 4;
     extern __shared__ __attribute__((aligned(16))) float dr_lds[];
     f32x4* const stash = reinterpret_cast<f32x4*>(dr_lds + wave * 4096) + lane;  // [16 accumulators][64 lanes] x 16 B
-    // this step's AdamW scalars: by value, or -- a step replayed from a hipGraph -- from the device's step state
-    GdAdamHyper hy = g.adam;
-    if (d.adam_dev) hy = *d.adam_dev;
-    // ---- tiles and tickets: as dr_tn_kernel ----
+    // ---- tiles and tickets: as dr_tn_kernel, with the panels of every product behind one another in each queue ----
     const int n_waves = gridDim.x * 8;
-    const int minor = d.m_fastest ? d.tiles_m : d.tiles_n;
-    const int panels = d.m_fastest ? d.tiles_n : d.tiles_m;
     int xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     int qx = xcc & 7, visited = 0;
     // (panels dealt round-robin over the queues.  Contiguous blocks of panels per queue -- neighbouring panels on one XCD, close in
     // time, for the 128-byte lines two neighbouring tiles share -- measured slower: 0.314 / 0.327 against 0.293 / 0.318 ms.)
-    auto q_tiles = [&](int x) { return ((panels - x + 7) >> 3) * minor; };
-    auto tile_of = [&](int x, int t) { return ((t / minor) * 8 + x) * minor + t % minor; };
+    auto minor_of = [&](int p) { return d.p[p].m_fastest ? d.p[p].tiles_m : d.p[p].tiles_n; };
+    auto q_tiles_of = [&](int p, int x) { return (((d.p[p].m_fastest ? d.p[p].tiles_n : d.p[p].tiles_m) - x + 7) >> 3) * minor_of(p); };
+    auto q_tiles = [&](int x) {
+        int n = 0;
+        for (int p = 0; p < d.n; ++p) n += q_tiles_of(p, x);
+        return n;
+    };
+    auto tile_of = [&](int x, int t) {  // ticket t < q_tiles(x) of queue x -> virtual tile id
+        int p = 0;
+        for (; p < d.n - 1; ++p) {
+            const int n = q_tiles_of(p, x);
+            if (t < n) break;
+            t -= n;
+        }
+        const int minor = minor_of(p);
+        return (p << DR_VT_SHIFT) | (((t / minor) * 8 + x) * minor + t % minor);
+    };
+    auto tile_mn = [&](int vt, int& tm, int& tn) {
+        const DrAdamProd& P = d.p[vt >> DR_VT_SHIFT];
+        const int t = vt & ((1 << DR_VT_SHIFT) - 1);
+        tm = P.m_fastest ? (t % P.tiles_m) : (t / P.tiles_n);
+        tn = P.m_fastest ? (t / P.tiles_m) : (t % P.tiles_n);
+    };
     auto draw_blocking = [&]() {
         for (;;) {
             if (visited == 8) return -1;
@@ -432,29 +486,53 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
         for (int i = 0; i < d.stagger; ++i) __builtin_amdgcn_s_sleep(127);
     int cur = draw_blocking();
     if (cur < 0) return;
-    const int ntiles = d.tiles_m * d.tiles_n;
     const int KSP = d.ksp;
-    const i32x4 srdA = dr_srd(g.A, (uint32_t)(((int64_t)(g.K - 1) * g.lda + g.M) * 4));
-    const i32x4 srdB = dr_srd(g.B, (uint32_t)(((int64_t)(g.K - 1) * g.ldb + g.N) * 4));
-    const uint32_t sa = 16u * (uint32_t)g.lda, sb = 16u * (uint32_t)g.ldb;
-    const int n_lim = g.out2 ? g.N - 1 : g.N;  // columns of C (a bias column, the last one of the product, goes to out2)
-    const uint32_t c_bytes = (uint32_t)(((int64_t)(g.M - 1) * g.ldc + n_lim) * 4);
-    const i32x4 srdW = dr_srd(g.C, c_bytes), srdM = dr_srd(g.aux, c_bytes), srdV = dr_srd(g.aux2, c_bytes);
-    const uint32_t ldc4 = (uint32_t)g.ldc * 4u;
 
-    uint32_t offA, offB, ka = 0, kb = 0;
+    // ---- load cursor: the tile whose operands are being fetched, with its product's operand descriptors ----
+    i32x4 srdA, srdB;
+    uint32_t sa, sb, offA, offB, ka = 0, kb = 0;
     int l_left = KSP;
-    auto set_cursor = [&](int tile) {
-        const bool ok = tile < ntiles;
-        const int tm = d.m_fastest ? (tile % d.tiles_m) : (tile / d.tiles_n);
-        const int tn = d.m_fastest ? (tile / d.tiles_m) : (tile % d.tiles_n);
-        offA = ok ? (uint32_t)(q * g.lda + tm * 64 + 4 * r) * 4u : 0xFFFFFFF0u;
-        offB = ok ? (uint32_t)(q * g.ldb + tn * 64 + 4 * r) * 4u : 0xFFFFFFF0u;
+    auto set_cursor = [&](int vt) {
+        vt = __builtin_amdgcn_readfirstlane(vt);
+        const bool ok = vt != DR_VT_PARK;  // parked: outside both matrices (of product 0), every load returns 0
+        const int vo = ok ? vt : 0;
+        const DrAdamProd& P = d.p[vo >> DR_VT_SHIFT];
+        int tm, tn;
+        tile_mn(vo, tm, tn);
+        srdA = dr_srd(P.A, (uint32_t)(((int64_t)(P.K - 1) * P.lda + P.M) * 4));
+        srdB = dr_srd(P.B, (uint32_t)(((int64_t)(P.K - 1) * P.ldb + P.N) * 4));
+        sa = 16u * (uint32_t)P.lda;
+        sb = 16u * (uint32_t)P.ldb;
+        offA = ok ? (uint32_t)(q * P.lda + tm * 64 + 4 * r) * 4u : 0xFFFFFFF0u;
+        offB = ok ? (uint32_t)(q * P.ldb + tn * 64 + 4 * r) * 4u : 0xFFFFFFF0u;
         ka = kb = 0;
         l_left = KSP;
     };
     set_cursor(cur);
-    // ---- optimiser stream state: the tile parked in LDS, its next row group, the two row groups in flight ----
+    // ---- optimiser stream state: the tile parked in LDS with its product's W / exp_avg / exp_avg_sq descriptors and AdamW
+    // scalars, its next row group, the two row groups in flight ----
+    auto c_bytes_of = [&](int p) {  // (a bias column, the product's last, goes to `bias`: it is not part of W)
+        const DrAdamProd& P = d.p[p];
+        return (uint32_t)(((int64_t)(P.M - 1) * P.ldc + (P.bias ? P.N - 1 : P.N)) * 4);
+    };
+    i32x4 srdW, srdM, srdV;
+    uint32_t ldc4;
+    GdAdamHyper hy;
+    int pp;  // the pending tile's product
+    auto set_pending_product = [&](int p) {
+        p = __builtin_amdgcn_readfirstlane(p);  // (wave-uniform: tells hipcc the descriptors below are scalars)
+        const DrAdamProd& P = d.p[p];
+        const uint32_t cb = c_bytes_of(p);
+        srdW = dr_srd(P.W, cb);
+        srdM = dr_srd(P.ea, cb);
+        srdV = dr_srd(P.ea2, cb);
+        ldc4 = (uint32_t)P.ldc * 4u;
+        // this step's AdamW scalars: by value, or -- a step replayed from a hipGraph -- from the device's step state
+        hy = P.adam;
+        if (P.adam_dev) hy = *P.adam_dev;
+        pp = p;
+    };
+    set_pending_product(cur >> DR_VT_SHIFT);
     uint32_t pend_base = PARK;  // per-lane byte offset of row group 0 of the pending tile inside W / exp_avg / exp_avg_sq
     bool pend_lane = false;     // this lane owns a full 16-byte group in the pending tile (else its stream accesses stay parked)
     int pend_g = 16;            // next row group of the pending tile to issue (16: none left)
@@ -545,8 +623,8 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
         unsigned int tick = visited < 8 ? dr_ticket_issue(tctr) : 0u;
         const bool drew = visited < 8;
         int nxt = 0;
-        const int tm = d.m_fastest ? (cur % d.tiles_m) : (cur / d.tiles_n);
-        const int tn = d.m_fastest ? (cur / d.tiles_m) : (cur % d.tiles_n);
+        int tm, tn;
+        tile_mn(cur, tm, tn);
         const int m0 = tm * 64, n0 = tn * 64;
         f32x4 acc[4][4];
 #pragma unroll
@@ -598,7 +676,7 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
                                     nxt = draw_blocking();
                                 }
                             }
-                            if (nxt < 0) nxt = ntiles;
+                            if (nxt < 0) nxt = DR_VT_PARK;
                             set_cursor(nxt);
                         }
                         __builtin_amdgcn_sched_barrier(0);
@@ -619,7 +697,12 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        // ---- end of tile ----
+        // ---- end of tile: the stream's state moves on to this tile's product (the previous pending tile has been consumed in full
+        // by a k loop of >= 9 rounds; a shorter loop never leaves one pending) ----
+        const int pc = cur >> DR_VT_SHIFT;
+        const DrAdamProd& g = d.p[pc];
+        set_pending_product(pc);
+        const int n_lim = g.bias ? g.N - 1 : g.N;  // columns of W (a bias column, the last one of the product, goes to g.bias)
         const uint32_t vo = (uint32_t)(16 * q * g.ldc + n0 + 4 * r) * 4u;
         const int n = n0 + 4 * r;
         const bool lane_full = n + 3 < n_lim;  // the lane owns a full 16-byte group of every row of the tile
@@ -639,9 +722,10 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
         } else if (lane_full) {
             // a reduction too short for the stream (< 9 ring rounds): updated on the spot from the accumulators, as in round 3
             // (one memory round trip per row group)
-            const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(g.C, 0, (int)c_bytes, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rM = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.aux), 0, (int)c_bytes, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.aux2), 0, (int)c_bytes, 0x00020000);
+            const int c_bytes = (int)c_bytes_of(pc);
+            const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(g.W, 0, c_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rM = __builtin_amdgcn_make_buffer_rsrc(g.ea, 0, c_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(g.ea2, 0, c_bytes, 0x00020000);
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -666,8 +750,8 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
         if (!lane_full && n < g.N) {
             // last column panel: the lane's group straddles the end of the row (N % 4 != 0) or holds the bias column -- element-wise
             // from the accumulators, now (at most one lane per row)
-            float* __restrict__ Mo = const_cast<float*>(g.aux);
-            float* __restrict__ Vo = const_cast<float*>(g.aux2);
+            float* __restrict__ Mo = g.ea;
+            float* __restrict__ Vo = g.ea2;
             for (int t = 0; t < 4; ++t)
                 for (int e = 0; e < 4; ++e) {
                     const int m = m0 + 16 * q + 4 * t + e;
@@ -676,19 +760,19 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
                         if (n + k >= g.N) continue;
                         const int64_t o = (int64_t)m * g.ldc + n + k;
                         const float gk = acc[e][k][t];
-                        if (g.out2 && n + k == g.N - 1) {  // the bias column (operand B's extra column): its own vector
-                            g.out2[m] = gk;
+                        if (g.bias && n + k == g.N - 1) {  // the bias column (operand B's extra column): its own vector
+                            g.bias[m] = gk;
                             continue;
                         }
-                        float pk = g.C[o], mk = Mo[o], vk = Vo[o];
+                        float pk = g.W[o], mk = Mo[o], vk = Vo[o];
                         gd_adam_elem(pk, gk, mk, vk, hy);
-                        g.C[o] = pk;
+                        g.W[o] = pk;
                         Mo[o] = mk;
                         Vo[o] = vk;
                     }
                 }
         }
-        if (nxt >= ntiles) break;
+        if (nxt == DR_VT_PARK) break;
         cur = nxt;
     }
     // the parked cursor's loads and the stream's last instructions are still in flight: their registers stay live until they landed
@@ -706,10 +790,13 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
         opt_update_store(sl[k]);
     }
     dr_wait<0>();
+#if !(GD_ADAMW_DBG & 32)  // (probe bit 5: the last tile's row groups are not updated -- prices this drain; results wrong)
     {
-        const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(g.C, 0, (int)c_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rM = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.aux), 0, (int)c_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.aux2), 0, (int)c_bytes, 0x00020000);
+        const DrAdamProd& g = d.p[pp];
+        const int c_bytes = (int)c_bytes_of(pp);
+        const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(g.W, 0, c_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rM = __builtin_amdgcn_make_buffer_rsrc(g.ea, 0, c_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(g.ea2, 0, c_bytes, 0x00020000);
         for (; pend_g < 16; pend_g += 4) {
             f32x4 pv[4], mv[4], vv[4];
             uint32_t oo[4];
@@ -738,6 +825,7 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrArgs d) {
             }
         }
     }
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1746,7 +1834,7 @@ void dr_nt_go(const DrArgs& d, int n_cu, hipStream_t s) {
 
 int dr_cu_count_fwd();
 template <int D, bool NTL>
-int dr_tn_adamw_go(const DrArgs& d, hipStream_t s) {
+int dr_tn_adamw_go(const DrMultiArgs& d, hipStream_t s) {
     static bool attr_set = false;  // 8 waves x 16 KB: the tile whose optimiser stream is running
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dr_tn_adamw_kernel<D, NTL>),
@@ -1761,17 +1849,21 @@ int dr_tn_adamw_go(const DrArgs& d, hipStream_t s) {
     return GDMCF_OK;
 }
 
-template <int D, int EPI>
-int dr_tn_go(const DrArgs& d, hipStream_t s) {
-    if constexpr (EPI == GD_EPI_ADAMW) {
-        // rows of W / exp_avg / exp_avg_sq on 128-byte lines: the stream's loads need not stay in L2 (dr_load0_rw)
-        const GdGemm& g = d.g;
-        const bool lines = (g.ldc & 31) == 0 && (((uintptr_t)g.C | (uintptr_t)g.aux | (uintptr_t)g.aux2) & 127) == 0;
-        static const int force = getenv("GDMCF_DR_NT_LOADS") ? atoi(getenv("GDMCF_DR_NT_LOADS")) : -1;  // tuning knob: 0 / 1
-        return (force >= 0 ? force != 0 : lines) ? dr_tn_adamw_go<D, true>(d, s) : dr_tn_adamw_go<D, false>(d, s);
-    } else {
-        hipLaunchKernelGGL((dr_tn_kernel<1, 1, D, EPI>), dim3(dr_cu_count_fwd()), dim3(512), 0, s, d);
+template <int D>
+int dr_tn_adamw_go(const DrMultiArgs& d, hipStream_t s) {
+    // rows of W / exp_avg / exp_avg_sq on 128-byte lines in every product: the stream's loads need not stay in L2 (dr_load0_rw)
+    bool lines = true;
+    for (int i = 0; i < d.n; ++i) {
+        const DrAdamProd& p = d.p[i];
+        lines = lines && (p.ldc & 31) == 0 && (((uintptr_t)p.W | (uintptr_t)p.ea | (uintptr_t)p.ea2) & 127) == 0;
     }
+    static const int force = getenv("GDMCF_DR_NT_LOADS") ? atoi(getenv("GDMCF_DR_NT_LOADS")) : -1;  // tuning knob: 0 / 1
+    return (force >= 0 ? force != 0 : lines) ? dr_tn_adamw_go<D, true>(d, s) : dr_tn_adamw_go<D, false>(d, s);
+}
+
+template <int D>
+int dr_tn_go(const DrArgs& d, hipStream_t s) {
+    hipLaunchKernelGGL((dr_tn_kernel<1, 1, D, GD_EPI_STORE>), dim3(dr_cu_count_fwd()), dim3(512), 0, s, d);
     return GDMCF_OK;
 }
 
@@ -1828,76 +1920,158 @@ static int dr_ticket_slot(hipStream_t s) {
     return (int)(g_dr_seq_eager.fetch_add(1, std::memory_order_relaxed) & 15u);
 }
 
-// Returns GD_DR_NOT_TAKEN when the product is not one this file handles (the caller falls back to the LDS-tiled kernels).
+// Tiles, ticket order and k-steps of a weight-gradient product on the register-streaming kernels (dr_tn_kernel /
+// dr_tn_adamw_kernel); false when they do not take it.  With a bias-column request (operand B one column wider than the product:
+// linear.hip) g.N counts that column on return and *bias_db is the vector it goes to, else NULL; *depth is the ring depth D.
+static bool dr_tn_prepare(int epi, GdGemm& g, DrArgs& d, float** bias_db, int* depth) {
+    const int64_t lim = (int64_t)1 << 32;  // 32-bit byte offsets inside every matrix
+    if ((int64_t)g.K * g.lda * 4 >= lim || (int64_t)g.K * g.ldb * 4 >= lim || (int64_t)g.M * g.ldc * 4 >= lim) return false;
+    if (g.lda < g.M || g.ldb < g.N || g.ldc < g.N) return false;
+    const long tiles = (long)gd_cdiv(g.M, 64) * gd_cdiv(g.N, 64);
+    if (tiles < 512 || g.K < 128) return false;  // (short reductions: a tile is all prologue; the LDS-tiled kernels take them)
+    // bias gradient requested as one more column of the product (linear.hip: operand B carries the row scale in column N): the
+    // kernel multiplies N + 1 columns -- the extra one needs its lane's 4-column group to straddle the end, i.e. N % 4 == 0 or
+    // any N (the straddle path stores element-wise) -- and writes it to out2 instead of C
+    *bias_db = (g.ldb > g.N) ? g.out2 : nullptr;
+    if (*bias_db) g.N += 1;
+    d.tiles_m = gd_cdiv(g.M, 64);
+    d.tiles_n = gd_cdiv(g.N, 64);
+    d.m_fastest = d.tiles_m <= d.tiles_n;  // tiles that share the LARGER operand's panel draw consecutive tickets
+    {   // tuning knob: GDMCF_DR_MF=0|1 forces the ticket order of the fused-AdamW product
+        static const int mf = getenv("GDMCF_DR_MF") ? atoi(getenv("GDMCF_DR_MF")) : -1;
+        if (mf >= 0 && epi == GD_EPI_ADAMW) d.m_fastest = mf;
+    }
+    const int ks = gd_cdiv(g.K, 4);
+    // ring depth: the one whose size wastes the fewest padded steps per tile
+    int best = 9, waste = 1 << 30;
+    for (int dd : {9, 8, 7}) {
+        const int w = gd_cdiv(ks, dd + 1) * (dd + 1) - ks;
+        if (w < waste) { waste = w; best = dd; }
+    }
+    {   // tuning knob: GDMCF_DR_D=7|8|9 forces the ring depth
+        static const int forced = getenv("GDMCF_DR_D") ? atoi(getenv("GDMCF_DR_D")) : 0;
+        if (forced >= 7 && forced <= 9) { best = forced; waste = gd_cdiv(ks, best + 1) * (best + 1) - ks; }
+    }
+    d.ksp = ks + waste;
+    *depth = best;
+    g.tiles_m = d.tiles_m;
+    g.tiles_n = d.tiles_n;
+    return true;
+}
+
+static DrAdamProd dr_adam_prod(const GdGemm& g, const DrArgs& d, float* bias_db) {
+    DrAdamProd p = {};
+    p.A = g.A; p.B = g.B; p.W = g.C; p.ea = const_cast<float*>(g.aux); p.ea2 = const_cast<float*>(g.aux2); p.bias = bias_db;
+    p.lda = (int)g.lda; p.ldb = (int)g.ldb; p.ldc = (int)g.ldc;
+    p.M = g.M; p.N = g.N; p.K = g.K;
+    p.tiles_m = d.tiles_m; p.tiles_n = d.tiles_n; p.m_fastest = d.m_fastest;
+    p.adam = g.adam;
+    p.adam_dev = g.adam_dev;  // a bound graph step state (linear.hip)
+    return p;
+}
+
+static int dr_adamw_launch(DrMultiArgs& m, int depth, hipStream_t s) {
+    m.ctr = dr_ticket_slot(s);
+    if (depth == 9) return dr_tn_adamw_go<9>(m, s);
+    if (depth == 8) return dr_tn_adamw_go<8>(m, s);
+    return dr_tn_adamw_go<7>(m, s);
+}
+
 int g_gd_dr_force = -1;  // tools/gemm_probe.hip: overrides GDMCF_GEMM_DR per call when >= 0
-int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
+static int dr_on_flags() {
     static const int on_env = getenv("GDMCF_GEMM_DR") ? atoi(getenv("GDMCF_GEMM_DR")) : 49;
-    const int on = g_gd_dr_force >= 0 ? g_gd_dr_force : on_env;  // bit 0: weight gradients (default), bit 1: forward
+    return g_gd_dr_force >= 0 ? g_gd_dr_force : on_env;  // bit 0: weight gradients (default), bit 1: forward
     // products (opt-in: measured SLOWER than the LDS-tiled kernels -- 0.279 vs 0.270 ms for the Yelp loss product: a K-contiguous
     // operand costs 16 half-line L1 accesses per load instead of 8 full lines, TCP accesses x3.6, 20 % of the wave cycles waiting)
+}
+static int dr_stagger() {
+    static const int stagger = getenv("GDMCF_DR_STAGGER") ? atoi(getenv("GDMCF_DR_STAGGER")) : 3;
+    return stagger;
+}
+// (the fused-AdamW epilogue: hipcc rotates accumulators through ring slots there, which the first, set-based lint
+// (build.py:lint_ring_registers) cannot tell from a copy of in-flight data; the per-register analysis that replaced it for
+// this variant (lint_vmcnt: no instruction touches a register whose load the counted waits do not cover) verifies it clean,
+// and tests/test_gpu_fullsize.py checks every element of W / exp_avg / exp_avg_sq at the full shapes.  GDMCF_GEMM_DR bit 2
+// clear (e.g. =1 with bit 2 masked by GDMCF_DR_NO_FUSED=1) sends the fused products back to the LDS-tiled kernel.)
+static bool dr_fused_on() {
+    static const int no_fused = getenv("GDMCF_DR_NO_FUSED") ? atoi(getenv("GDMCF_DR_NO_FUSED")) : 0;
+    return (dr_on_flags() & 1) && !no_fused;
+}
+
+// Several weight-gradient products with AdamW as ONE launch of dr_tn_adamw_kernel (gdmcf_linear_bwd_weight_adamw_multi_f32).
+// All or nothing: GD_DR_NOT_TAKEN (nothing launched) unless every product is one the kernel takes, in f32, with the same ring
+// depth and k-steps per tile.  A product whose bias column was taken has its out2 cleared, as gd_gemm_dr_launch does.
+int gd_gemm_dr_adamw_multi(GdGemm* gs, int n, hipStream_t s) {
+    if (n < 1 || n > DR_MULTI_MAX || !dr_fused_on()) return GD_DR_NOT_TAKEN;
+    DrMultiArgs m = {};
+    float* bias_db[DR_MULTI_MAX] = {};
+    int n_user[DR_MULTI_MAX] = {};
+    int depth = 0;
+    bool ok = true;
+    double flop = 0.0;
+    for (int i = 0; i < n && ok; ++i) {
+        GdGemm& g = gs[i];
+        ok = !g.bf16 && !g.accumulate && !g.C16 && g.splits <= 1;
+        DrArgs d = {};
+        int dep = 0;
+        n_user[i] = g.N;
+        if (ok) ok = dr_tn_prepare(GD_EPI_ADAMW, g, d, &bias_db[i], &dep);
+        if (ok) {
+            ok = (i == 0 || (dep == depth && d.ksp == m.ksp)) && (long)d.tiles_m * d.tiles_n < (1L << DR_VT_SHIFT);
+            depth = dep;
+            m.ksp = d.ksp;
+            m.p[i] = dr_adam_prod(g, d, bias_db[i]);
+            flop += 2.0 * g.M * n_user[i] * g.K;
+        }
+    }
+    if (!ok) {
+        for (int i = 0; i < n; ++i) gs[i].N = n_user[i] ? n_user[i] : gs[i].N;
+        return GD_DR_NOT_TAKEN;
+    }
+    m.n = n;
+    m.stagger = dr_stagger();
+    {
+        GdProfScope prof(gs[0].prof_tag, flop, s);
+        const int rc = dr_adamw_launch(m, depth, s);
+        if (rc != GDMCF_OK) return rc;
+    }
+    for (int i = 0; i < n; ++i) {
+        gs[i].N = n_user[i];
+        if (bias_db[i]) gs[i].out2 = nullptr;  // taken: the caller skips its column-sum pass
+    }
+    t_gd_last_gemm = 3;
+    return gd_launch_status("gemm_dr");
+}
+
+// Returns GD_DR_NOT_TAKEN when the product is not one this file handles (the caller falls back to the LDS-tiled kernels).
+int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
+    const int on = dr_on_flags();
     if (!on || g.bf16) return GD_DR_NOT_TAKEN;
     if (g.accumulate || g.C16 || (g.splits > 1 && epi != GD_EPI_SLAB)) return GD_DR_NOT_TAKEN;  // (slabs: dr_kn_kernel sets its own split count)
-    static const int stagger = getenv("GDMCF_DR_STAGGER") ? atoi(getenv("GDMCF_DR_STAGGER")) : 3;
     const int64_t lim = (int64_t)1 << 32;  // 32-bit byte offsets inside every matrix
     DrArgs d = {};
     d.ctr = -1;  // drawn per launch, once the product is known to be taken (dr_ticket_slot)
-    d.stagger = stagger;
-    // (the fused-AdamW epilogue: hipcc rotates accumulators through ring slots there, which the first, set-based lint
-    // (build.py:lint_ring_registers) cannot tell from a copy of in-flight data; the per-register analysis that replaced it for
-    // this variant (lint_vmcnt: no instruction touches a register whose load the counted waits do not cover) verifies it clean,
-    // and tests/test_gpu_fullsize.py checks every element of W / exp_avg / exp_avg_sq at the full shapes.  GDMCF_GEMM_DR bit 2
-    // clear (e.g. =1 with bit 2 masked by GDMCF_DR_NO_FUSED=1) sends the fused products back to the LDS-tiled kernel.)
-    static const int no_fused = getenv("GDMCF_DR_NO_FUSED") ? atoi(getenv("GDMCF_DR_NO_FUSED")) : 0;
-    if ((on & 1) && layA == GD_LAY_MC && layB == GD_LAY_MC && (epi == GD_EPI_STORE || (epi == GD_EPI_ADAMW && !no_fused))) {
-        if ((int64_t)g.K * g.lda * 4 >= lim || (int64_t)g.K * g.ldb * 4 >= lim || (int64_t)g.M * g.ldc * 4 >= lim) return GD_DR_NOT_TAKEN;
-        if (g.lda < g.M || g.ldb < g.N || g.ldc < g.N) return GD_DR_NOT_TAKEN;
-        const long tiles = (long)gd_cdiv(g.M, 64) * gd_cdiv(g.N, 64);
-        if (tiles < 512 || g.K < 128) return GD_DR_NOT_TAKEN;  // (short reductions: a tile is all prologue; the LDS-tiled kernels take them)
-        // bias gradient requested as one more column of the product (linear.hip: operand B carries the row scale in column N): the
-        // kernel multiplies N + 1 columns -- the extra one needs its lane's 4-column group to straddle the end, i.e. N % 4 == 0 or
-        // any N (the straddle path stores element-wise) -- and writes it to out2 instead of C
-        float* const bias_db = (g.ldb > g.N) ? g.out2 : nullptr;
+    d.stagger = dr_stagger();
+    // the fused-AdamW product: the one-element case of gd_gemm_dr_adamw_multi
+    if (epi == GD_EPI_ADAMW && layA == GD_LAY_MC && layB == GD_LAY_MC) return gd_gemm_dr_adamw_multi(&g, 1, s);
+    if ((on & 1) && layA == GD_LAY_MC && layB == GD_LAY_MC && epi == GD_EPI_STORE) {
         const int n_user = g.N;
-        if (bias_db) g.N = n_user + 1;
-        d.tiles_m = gd_cdiv(g.M, 64);
-        d.tiles_n = gd_cdiv(g.N, 64);
-        d.m_fastest = d.tiles_m <= d.tiles_n;  // tiles that share the LARGER operand's panel draw consecutive tickets
-        {   // tuning knob: GDMCF_DR_MF=0|1 forces the ticket order of the fused-AdamW product
-            static const int mf = getenv("GDMCF_DR_MF") ? atoi(getenv("GDMCF_DR_MF")) : -1;
-            if (mf >= 0 && epi == GD_EPI_ADAMW) d.m_fastest = mf;
+        float* bias_db = nullptr;
+        int best = 9;
+        if (!dr_tn_prepare(epi, g, d, &bias_db, &best)) {
+            g.N = n_user;
+            return GD_DR_NOT_TAKEN;
         }
-        const int ks = gd_cdiv(g.K, 4);
-        // ring depth: the one whose size wastes the fewest padded steps per tile
-        int best = 9, waste = 1 << 30;
-        for (int dd : {9, 8, 7}) {
-            const int w = gd_cdiv(ks, dd + 1) * (dd + 1) - ks;
-            if (w < waste) { waste = w; best = dd; }
-        }
-        {   // tuning knob: GDMCF_DR_D=7|8|9 forces the ring depth
-            static const int forced = getenv("GDMCF_DR_D") ? atoi(getenv("GDMCF_DR_D")) : 0;
-            if (forced >= 7 && forced <= 9) { best = forced; waste = gd_cdiv(ks, best + 1) * (best + 1) - ks; }
-        }
-        d.ksp = ks + waste;
-        g.tiles_m = d.tiles_m;
-        g.tiles_n = d.tiles_n;
         d.g = g;
         d.ctr = dr_ticket_slot(s);
-        d.adam_dev = epi == GD_EPI_ADAMW ? g.adam_dev : nullptr;  // a bound graph step state (linear.hip)
         d.g.out2 = bias_db;
         {
             GdProfScope prof(g.prof_tag, 2.0 * g.M * n_user * g.K, s);
-#define GD_DR_GO(DD)                                                      \
-    do {                                                                  \
-        int rc_ = (epi == GD_EPI_STORE) ? dr_tn_go<DD, GD_EPI_STORE>(d, s) : dr_tn_go<DD, GD_EPI_ADAMW>(d, s); \
-        if (rc_ != GDMCF_OK) return rc_;                                  \
-    } while (0)
-            if (best == 9) GD_DR_GO(9);
-            else if (best == 8) GD_DR_GO(8);
-            else GD_DR_GO(7);
-#undef GD_DR_GO
+            int rc_ = best == 9 ? dr_tn_go<9>(d, s) : best == 8 ? dr_tn_go<8>(d, s) : dr_tn_go<7>(d, s);
+            if (rc_ != GDMCF_OK) return rc_;
         }
         g.N = n_user;
-        t_gd_last_gemm = epi == GD_EPI_ADAMW ? 3 : 2;
+        t_gd_last_gemm = 2;
         if (bias_db) g.out2 = nullptr;  // taken: the caller skips its column-sum pass
         return gd_launch_status("gemm_dr");
     }

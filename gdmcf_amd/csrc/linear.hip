@@ -103,6 +103,33 @@ float* bias_col_request(int a_scale_col, int64_t lda, const float* rowscale, int
     return db;
 }
 
+// The product of one fused weight-gradient + AdamW call: dW[N x K_in] = dZ[M x N]^T A[M x K_in] -> gemm (N, K, reduction M),
+// both operands row-contiguous, W / exp_avg / exp_avg_sq updated in its epilogue
+int dw_adamw_setup(const GdDwAdamw& e, GdGemm& g, int& cls) {
+    GD_CHECK_SHAPE(e.M > 0 && e.N > 0 && e.K > 0 && e.lddz >= e.N && e.lda >= e.K && e.ldw >= e.K, "linear_bwd_weight_adamw: bad shape");
+    GD_CHECK_ARG(e.W && e.exp_avg && e.exp_avg_sq && e.step >= 1, "linear_bwd_weight_adamw: optimizer state missing");
+    const int M = e.M, N = e.N, K = e.K;
+    cls = pick_class_dw(N, K, t_gemm_prec, true);
+    g = GdGemm{};
+    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
+    g.A = e.dZ; g.lda = e.lddz; g.B = e.A; g.ldb = e.lda; g.M = N; g.N = K; g.K = M; g.splits = 1;
+    g.m_fastest = gd_cdiv(N, gd_gemm_tile_m(cls)) <= gd_cdiv(K, gd_gemm_tile_n(cls));
+    g.C = e.W; g.ldc = e.ldw; g.aux = e.exp_avg; g.aux2 = e.exp_avg_sq; g.prof_tag = 5;
+    g.adam = gd_adam_hyper(e.lr, e.beta1, e.beta2, e.eps, e.weight_decay, e.step, e.grad_scale);
+    g.adam_dev = t_gd_step_state ? &t_gd_step_state->hyper : nullptr;  // bound graph step state: the scalars of the step being replayed
+    attach_result_shadow(g);  // the bf16 kernels' row epilogue also refreshes W's bf16 shadow
+    attach_shadows(g, GD_LAY_MC, GD_LAY_MC);
+    g.out2 = bias_col_request(e.a_scale_col, e.lda, e.rowscale, K, e.db);
+    return GDMCF_OK;
+}
+
+// after the product: the bias gradient, unless it came out of the product as its extra column
+int dw_adamw_finish(const GdDwAdamw& e, bool asked, const GdGemm& g, hipStream_t s) {
+    if (asked && g.out2 == nullptr) return GDMCF_OK;  // db came out of the product
+    if (e.db) return gd_colsum(e.dZ, e.lddz, e.rowscale, e.M, e.N, e.db, s);
+    return GDMCF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -320,25 +347,49 @@ int gdmcf_linear_bwd_weight_adamw_f32(const float* dZ, int64_t lddz, const float
                                       int a_scale_col, int M, int N, int K, float* W, int64_t ldw, float* exp_avg, float* exp_avg_sq,
                                       float* db, float lr, float beta1, float beta2, float eps, float weight_decay,
                                       int step, float grad_scale, void* stream) {
-    GD_CHECK_SHAPE(M > 0 && N > 0 && K > 0 && lddz >= N && lda >= K && ldw >= K, "linear_bwd_weight_adamw: bad shape");
-    GD_CHECK_ARG(W && exp_avg && exp_avg_sq && step >= 1, "linear_bwd_weight_adamw: optimizer state missing");
-    hipStream_t s = (hipStream_t)stream;
-    const int cls = pick_class_dw(N, K, t_gemm_prec, true);
-    GdGemm g = {};
-    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
-    g.A = dZ; g.lda = lddz; g.B = A; g.ldb = lda; g.M = N; g.N = K; g.K = M; g.splits = 1;
-    g.m_fastest = gd_cdiv(N, gd_gemm_tile_m(cls)) <= gd_cdiv(K, gd_gemm_tile_n(cls));
-    g.C = W; g.ldc = ldw; g.aux = exp_avg; g.aux2 = exp_avg_sq; g.prof_tag = 5;
-    g.adam = gd_adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale);
-    g.adam_dev = t_gd_step_state ? &t_gd_step_state->hyper : nullptr;  // bound graph step state: the scalars of the step being replayed
-    attach_result_shadow(g);  // the bf16 kernels' row epilogue also refreshes W's bf16 shadow
-    attach_shadows(g, GD_LAY_MC, GD_LAY_MC);
-    g.out2 = bias_col_request(a_scale_col, lda, rowscale, K, db);
-    const bool asked = g.out2 != nullptr;
-    int rc = gd_gemm_launch(GD_LAY_MC, GD_LAY_MC, GD_EPI_ADAMW, cls, g, s);
+    const GdDwAdamw e = {dZ, lddz, A, lda, rowscale, a_scale_col, M, N, K, W, ldw, exp_avg, exp_avg_sq, db,
+                         lr, beta1, beta2, eps, weight_decay, step, grad_scale};
+    GdGemm g;
+    int cls;
+    int rc = dw_adamw_setup(e, g, cls);
     if (rc) return rc;
-    if (asked && g.out2 == nullptr) return GDMCF_OK;  // db came out of the product
-    if (db) return gd_colsum(dZ, lddz, rowscale, M, N, db, s);
+    const bool asked = g.out2 != nullptr;
+    rc = gd_gemm_launch(GD_LAY_MC, GD_LAY_MC, GD_EPI_ADAMW, cls, g, (hipStream_t)stream);
+    if (rc) return rc;
+    return dw_adamw_finish(e, asked, g, (hipStream_t)stream);
+}
+
+int gdmcf_linear_bwd_weight_adamw_multi_f32(const GdDwAdamw* list, int n, void* stream) {
+    GD_CHECK_ARG(n >= 0 && (n == 0 || list), "linear_bwd_weight_adamw_multi: bad list");
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int MAXN = 4;  // products per launch (gemm_dr.hip: DR_MULTI_MAX)
+    for (int i0 = 0; i0 < n; i0 += MAXN) {
+        const int k = n - i0 < MAXN ? n - i0 : MAXN;
+        GdGemm g[MAXN];
+        bool asked[MAXN];
+        int cls;
+        for (int j = 0; j < k; ++j) {
+            const int rc = dw_adamw_setup(list[i0 + j], g[j], cls);
+            if (rc) return rc;
+            asked[j] = g[j].out2 != nullptr;
+        }
+        int rc = gd_gemm_dr_adamw_multi(g, k, s);
+        if (rc == GD_DR_NOT_TAKEN) {  // one call per product
+            for (int j = 0; j < k; ++j) {
+                const GdDwAdamw& e = list[i0 + j];
+                rc = gdmcf_linear_bwd_weight_adamw_f32(e.dZ, e.lddz, e.A, e.lda, e.rowscale, e.a_scale_col, e.M, e.N, e.K, e.W,
+                                                       e.ldw, e.exp_avg, e.exp_avg_sq, e.db, e.lr, e.beta1, e.beta2, e.eps,
+                                                       e.weight_decay, e.step, e.grad_scale, stream);
+                if (rc) return rc;
+            }
+            continue;
+        }
+        if (rc) return rc;
+        for (int j = 0; j < k; ++j) {
+            rc = dw_adamw_finish(list[i0 + j], asked[j], g[j], s);
+            if (rc) return rc;
+        }
+    }
     return GDMCF_OK;
 }
 

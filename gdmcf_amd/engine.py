@@ -13,7 +13,9 @@ HBM layout (all float32 row-major, leading dims padded to 64 elements = 256 B):
   slabs           split-K partial sums (forward of layer 0, input-gradient of the last layer)
 """
 
+import ctypes
 import functools
+import os
 
 import torch
 
@@ -443,6 +445,11 @@ class DenoiserEngine:
         dWe = dbe = None
         fused = self.fused_opt if self.grad_sink is None else None
         dz, lddz, rs = dz_last, ld_last, rowscale
+        # f32 products of fused weights: queued and issued as ONE launch after every input gradient (one ramp, one optimiser-stream
+        # drain and one ragged last round of tiles per step instead of one per weight).  Their operands -- the per-layer dzs, the
+        # row-scaled copy bufs.hs (written for the last layer only) and the activations -- are not written again before that.
+        # GDMCF_DW_MULTI=0: one launch per weight, where its layer's backward issues it.
+        dw_queue = [] if (fused is not None and self.gemm_dtype == "f32" and os.environ.get("GDMCF_DW_MULTI", "1") != "0") else None
 
         def input_grad(li, w, A_prev, lda_prev, N, K):
             nonlocal dWe, dbe
@@ -477,12 +484,18 @@ class DenoiserEngine:
             if fs is not None:
                 if fs["exp_avg"].stride() != w.stride() or fs["exp_avg_sq"].stride() != w.stride():
                     raise RuntimeError("gdmcf_amd: the moments of a fused weight must share its leading dimension")
-                _lib.check(lib.gdmcf_linear_bwd_weight_adamw_f32(
-                    dz.data_ptr(), lddz, A_use.data_ptr(), lda_use, _lib.ptr(rs), scol, B, N, K, w.data_ptr(), w.stride(0),
-                    fs["exp_avg"].data_ptr(), fs["exp_avg_sq"].data_ptr(), db.data_ptr(), fs["lr"], fs["beta1"],
-                    fs["beta2"], fs["eps"], fs["weight_decay"], fs["step"], fs["grad_scale"], st))
-                if not (self.gemm_dtype == "bf16" and _lib.shadow_info(w.data_ptr()) is not None):
-                    torch.autograd.graph.increment_version(w)  # updated in the GEMM epilogue (bf16: shadow too)
+                if dw_queue is not None:
+                    dw_queue.append((_lib.GdDwAdamw(
+                        dz.data_ptr(), lddz, A_use.data_ptr(), lda_use, _lib.ptr(rs), scol, B, N, K, w.data_ptr(), w.stride(0),
+                        fs["exp_avg"].data_ptr(), fs["exp_avg_sq"].data_ptr(), db.data_ptr(), fs["lr"], fs["beta1"],
+                        fs["beta2"], fs["eps"], fs["weight_decay"], fs["step"], fs["grad_scale"]), w))
+                else:
+                    _lib.check(lib.gdmcf_linear_bwd_weight_adamw_f32(
+                        dz.data_ptr(), lddz, A_use.data_ptr(), lda_use, _lib.ptr(rs), scol, B, N, K, w.data_ptr(), w.stride(0),
+                        fs["exp_avg"].data_ptr(), fs["exp_avg_sq"].data_ptr(), db.data_ptr(), fs["lr"], fs["beta1"],
+                        fs["beta2"], fs["eps"], fs["weight_decay"], fs["step"], fs["grad_scale"], st))
+                    if not (self.gemm_dtype == "bf16" and _lib.shadow_info(w.data_ptr()) is not None):
+                        torch.autograd.graph.increment_version(w)  # updated in the GEMM epilogue (bf16: shadow too)
                 dW = None
             else:
                 dW = self._grad_like(w)
@@ -519,6 +532,11 @@ class DenoiserEngine:
                 weight_grad(li, w, bias, A_prev, lda_prev, N, K)
                 nxt = input_grad(li, w, A_prev, lda_prev, N, K)
             dz, lddz, rs = nxt
+        if dw_queue:
+            arr = (_lib.GdDwAdamw * len(dw_queue))(*[e for e, _ in dw_queue])
+            _lib.check(lib.gdmcf_linear_bwd_weight_adamw_multi_f32(ctypes.addressof(arr), len(dw_queue), st))
+            for _, w in dw_queue:
+                torch.autograd.graph.increment_version(w)  # updated in the GEMM epilogue
         if self._side2_used:  # everything that consumes the gradients is ordered behind the side stream
             torch.cuda.current_stream().wait_stream(self._side2)
             self._side2_used = False

@@ -270,6 +270,30 @@ int gdmcf_linear_bwd_weight_adamw_f32(const float* dZ, int64_t lddz, const float
                                       int64_t ldw, float* exp_avg, float* exp_avg_sq, float* db, float lr,
                                       float beta1, float beta2, float eps, float weight_decay, int step,
                                       float grad_scale, void* stream);
+/* The arguments of one gdmcf_linear_bwd_weight_adamw_f32 call, for the list form below. */
+typedef struct GdDwAdamw {
+    const float* dZ;
+    int64_t lddz;
+    const float* A;
+    int64_t lda;
+    const float* rowscale;
+    int a_scale_col, M, N, K;
+    float* W;
+    int64_t ldw;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* db;
+    float lr, beta1, beta2, eps, weight_decay;
+    int step;
+    float grad_scale;
+} GdDwAdamw;
+/* n such products, each with the contract of gdmcf_linear_bwd_weight_adamw_f32 and the same results bit for bit, issued as
+ * ONE kernel launch when the register-streaming kernel takes all of them (f32 mode, the same reduction length M, at most 4
+ * per launch; longer lists go in groups of 4), else as n consecutive calls of the single entry.  One launch pays the ramp,
+ * the final optimiser-stream drain and the ragged last round of tiles once instead of once per weight.  No W of the list
+ * may be read by later kernels of the same backward pass, nor be an operand (dZ, A) of another entry; the entries'
+ * W / exp_avg / exp_avg_sq / db must not overlap. */
+int gdmcf_linear_bwd_weight_adamw_multi_f32(const GdDwAdamw* list, int n, void* stream);
 /* out[m, k] = rowscale[m] * A[m, k], k < K (the scaled activation copy of the weight-gradient product: (rs . dZ)^T A ==
  * dZ^T (rs . A)); with ldo > K also out[m, K] = rowscale[m]: the column gdmcf_linear_bwd_weight_*'s a_scale_col speaks of. */
 int gdmcf_rowscale_f32(const float* A, int64_t lda, const float* rowscale, int M, int K, float* out,
