@@ -320,8 +320,8 @@ def build(force=False, verbose=True):
             text = open(asm).read()
             os.remove(asm)
             bad = lint_vmcnt(text) + lint_store_data(text)
-            if src == "gemm_dr.hip":  # (EPI 5 = fused AdamW: accumulators rotate through the ring there, see lint_vmcnt)
-                bad += [b for b in lint_ring_registers(text) if "ELi5EEEv" not in b.split(":")[0]]
+            if src == "gemm_dr.hip":
+                bad += lint_ring_registers(text)
             if bad:
                 raise RuntimeError(f"{src}: in-flight operand registers touched (see lint_vmcnt / lint_ring_registers):\n  "
                                    + "\n  ".join(bad[:12]))

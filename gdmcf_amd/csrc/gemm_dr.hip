@@ -27,6 +27,13 @@
 //
 // Determinism: the tile -> wave assignment is dynamic, the arithmetic of a tile is not (fixed k order, one wave per tile):
 // results are bit-identical from run to run.
+//
+// The kernels (gdmcf_debug_last_gemm family code in brackets), each behind a route switch of DrRoutes, all on by default; a
+// product a kernel does not take, or whose switch is off, goes to the LDS-tiled kernels (gemm_f32.hip):
+//   dr_tn_kernel        [2]  weight gradient dW = dZ^T A, the pipeline above                                GDMCF_DR_DW
+//   dr_tn_adamw_kernel  [3]  the same with the AdamW update in the epilogue, up to four products per launch  GDMCF_DR_DW, _ADAMW
+//   dr_fat_kernel       [4]  the output layer with a fused row-loss / posterior epilogue                    GDMCF_DR_FAT
+//   dr_kn_kernel        [5]  the input gradient and the cached-W^T forward as split-K slabs                  GDMCF_DR_KN
 #include <stdlib.h>
 
 #include "common.h"
@@ -35,7 +42,6 @@ namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef f32x4 f32x4_dr_u __attribute__((aligned(4)));
 
 // ticket counters: one SET per launch in flight (dr_ticket_slot below), one queue per XCD inside a set, each on a 128-byte line of
 // its own; a queue's last draw resets it, so every set is zero again when its launch has drained
@@ -71,9 +77,6 @@ __device__ __forceinline__ unsigned int dr_ticket_issue(unsigned int* ctr) {
 
 #ifndef GD_ADAMW_DBG
 #define GD_ADAMW_DBG 0
-#endif
-#ifndef DR_ADAM_UB
-#define DR_ADAM_UB 2  // row groups per batch of the fused-AdamW epilogue pipeline (dr_tn_kernel)
 #endif
 
 struct DrArgs {
@@ -113,9 +116,9 @@ struct DrMultiArgs {
 };
 
 // C[M,N] = A[K,M]^T * B[K,N], both operands row-contiguous.  TA / TB: 64-row load units per operand and k-step.
-template <int TA, int TB, int D, int EPI>
+// (The fused-AdamW form of this product: dr_tn_adamw_kernel.)
+template <int TA, int TB, int D>
 __global__ __launch_bounds__(512, 2) void dr_tn_kernel(const DrArgs d) {
-    static_assert(EPI == GD_EPI_STORE, "plain weight-gradient product (the fused-AdamW form: dr_tn_adamw_kernel)");
     constexpr int LPS = TA + TB;  // loads per k-step
     constexpr int R = D + 1;
     static_assert(LPS * D <= 63, "vmcnt is a 6-bit counter");
@@ -829,562 +832,11 @@ __global__ __launch_bounds__(512, 2) void dr_tn_adamw_kernel(const DrMultiArgs d
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// C[M,N] = A[M,K] * B[N,K]^T, both operands K-contiguous (the forward layers, reference models/DNN.py:79-86, with the fused
-// row-loss / posterior / bias-activation epilogues of gaussian_diffusion.py:335, :451-498).
-// A lane loads 16 bytes = four consecutive k of ONE row: lane (j = lane & 15, q = lane >> 4) reads P[row(j)][k0 + 4q .. +3],
-// so a wave instruction covers 16 rows x 16 k and register component s is the operand of the MFMA that takes
-// k in {k0 + s, k0 + 4 + s, k0 + 8 + s, k0 + 12 + s} (A and B permuted alike) -- four MFMA k-steps per load, the unit of the
-// ring is therefore a CHUNK of 16 k.  Which matrix row a lane reads is free: A blocks take rows m0 + 16 i + j, B loads take
-// rows n0 + 4 j + f (f = 0..3), which makes the accumulators
-//     acc[i][f][t] = C[m0 + 16 i + 4 q + t][n0 + 4 r + f]
-// -- again four consecutive columns per lane.  k past K lies inside the next row (no range check helps): the chunks that
-// reach past K are masked with selects (one or two per tile).
-// ---------------------------------------------------------------------------------------------------------------------
-template <int TMB, int NB, int D, int EPI>
-__global__ __launch_bounds__(512, 2) void dr_nt_kernel(const DrArgs d) {
-    static_assert(EPI == GD_EPI_BIAS_ACT || EPI == GD_EPI_LOSS || EPI == GD_EPI_POST, "forward products");
-    static_assert(NB == 4 || NB == 2, "B loads per chunk: 16 NB output columns, NB consecutive ones per lane");
-    constexpr int LPC = TMB + NB;   // loads per chunk
-    constexpr int R = D + 1;
-    constexpr int NM = 4 * TMB * NB;  // MFMAs per chunk
-    constexpr int SP = NM / (LPC + 1);  // the LPC loads of chunk c + D ride behind MFMA 2, 2 + SP, ...; then the cursor step
-    static_assert(SP >= 2 && SP * LPC + 1 < NM, "loads and cursor step must fall inside the chunk");
-    static_assert(LPC * D <= 63, "vmcnt is a 6-bit counter");
-    const GdGemm& g = d.g;
-    const int lane = threadIdx.x & 63;
-    const int r = lane & 15, q = lane >> 4;
-    const int ntiles = d.tiles_m * d.tiles_n;
-    unsigned int* ctr = &g_dr_ticket[d.ctr][0][0];
-    const int n_waves = gridDim.x * 8;
-    int cur = __builtin_amdgcn_readfirstlane(blockIdx.x * 8 + (threadIdx.x >> 6));
-    if (cur >= ntiles) return;
-    if (d.stagger > 0 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)
-        for (int i = 0; i < d.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-    const int NCP = d.ksp;  // chunks run per tile (a multiple of R)
-    const i32x4 srdA = dr_srd(g.A, (uint32_t)(((int64_t)(g.M - 1) * g.lda + g.K) * 4));
-    const i32x4 srdB = dr_srd(g.B, (uint32_t)(((int64_t)(g.N - 1) * g.ldb + g.K) * 4));
-
-    uint32_t offA[TMB], offB[NB];
-    uint32_t kc = 0;  // byte offset of the chunk to load next (soffset, the same for both operands)
-    int l_left = NCP;
-    auto set_cursor = [&](int tile) {
-        const bool ok = tile < ntiles;
-        const int tm = tile % d.tiles_m, tn = tile / d.tiles_m;  // the row tiles of one column panel draw consecutive tickets
-#pragma unroll
-        for (int i = 0; i < TMB; ++i) offA[i] = ok ? (uint32_t)((tm * (16 * TMB) + 16 * i + r) * g.lda + 4 * q) * 4u : 0xFFFFFFF0u;
-#pragma unroll
-        for (int f = 0; f < NB; ++f) offB[f] = ok ? (uint32_t)((tn * (16 * NB) + NB * r + f) * g.ldb + 4 * q) * 4u : 0xFFFFFFF0u;
-        kc = 0;
-        l_left = NCP;
-    };
-    set_cursor(cur);
-    f32x4 xa[R][TMB], xb[R][NB];
-#pragma unroll
-    for (int u = 0; u < D; ++u) {
-#pragma unroll
-        for (int i = 0; i < TMB; ++i) xa[u][i] = dr_load(srdA, offA[i], kc);
-#pragma unroll
-        for (int f = 0; f < NB; ++f) xb[u][f] = dr_load(srdB, offB[f], kc);
-        kc += 64;
-        --l_left;
-    }
-    const int q1 = (NCP / R / 4) * R, q2 = (NCP / R / 2) * R, q3 = (NCP / R * 3 / 4) * R;
-    const int c_mask = g.K >> 4;  // first chunk that reaches past K (== chunks when K % 16 == 0: then only padded chunks)
-    for (;;) {
-        unsigned int tick = dr_ticket_issue(ctr);
-        int nxt = 0;
-        const int tm = cur % d.tiles_m, tn = cur / d.tiles_m;
-        const int m0 = tm * 16 * TMB, n0 = tn * (16 * NB);
-        f32x4 acc[TMB][NB];
-#pragma unroll
-        for (int i = 0; i < TMB; ++i)
-#pragma unroll
-            for (int f = 0; f < NB; ++f) acc[i][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-        __builtin_amdgcn_s_setprio(0);
-        for (int c0 = 0; c0 < NCP; c0 += R) {
-            if (c0 == q1) __builtin_amdgcn_s_setprio(1);
-            else if (c0 == q2) __builtin_amdgcn_s_setprio(2);
-            else if (c0 == q3) __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-            for (int u = 0; u < R; ++u) {
-                const int v = (u + D) % R;
-                dr_wait<LPC*(D - 1)>();
-#pragma unroll
-                for (int i = 0; i < TMB; ++i) asm volatile("" : "+v"(xa[u][i]));
-#pragma unroll
-                for (int f = 0; f < NB; ++f) asm volatile("" : "+v"(xb[u][f]));
-                if (c0 + u >= c_mask) {  // uniform; the last chunk(s) of a tile only: zero every k >= K
-                    const int kq = (c0 + u) * 16 + 4 * q;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const bool keep = kq + e < g.K;
-#pragma unroll
-                        for (int i = 0; i < TMB; ++i) xa[u][i][e] = keep ? xa[u][i][e] : 0.f;
-#pragma unroll
-                        for (int f = 0; f < NB; ++f) xb[u][f][e] = keep ? xb[u][f][e] : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int n = 0; n < NM; ++n) {
-                    const int e = n / (TMB * NB), i = (n / NB) % TMB, f = n % NB;
-                    acc[i][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[u][i][e], xb[u][f][e], acc[i][f], 0, 0, 0);
-                    if (n % SP == 1 && n / SP < LPC) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        const int l = n / SP;
-                        if (l < TMB) xa[v][l] = dr_load(srdA, offA[l], kc);
-                        else xb[v][l - TMB] = dr_load(srdB, offB[l - TMB], kc);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    if (n == SP * LPC + 1) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        kc += 64;
-                        if (--l_left == 0) {
-                            if (NCP < 2 * D + 2) dr_wait<0>();
-                            asm volatile("" : "+v"(tick));
-                            const int tk = __builtin_amdgcn_readfirstlane(tick);
-                            if (tk == ntiles - 1 && lane == 0) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            nxt = n_waves + tk;
-                            set_cursor(nxt);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // ---- epilogue.  acc[i][f][t] = C[m0 + 16 i + 4 q + t][n0 + NB r + f]: the lane owns NB consecutive columns of 4 TMB rows ----
-        typedef float vecnb __attribute__((ext_vector_type(NB)));
-        typedef vecnb vecnb_u __attribute__((aligned(4)));
-        const int n = n0 + NB * r;
-        const bool full = n + NB - 1 < g.N;
-        float biasv[NB];
-#pragma unroll
-        for (int f = 0; f < NB; ++f) biasv[f] = g.bias ? g.bias[min(n + f, g.N - 1)] : 0.f;
-        const bool has_z = (EPI == GD_EPI_POST) && (g.aux2 != nullptr);
-        const bool has_r = (EPI == GD_EPI_POST) && (g.r2 != nullptr);
-        auto put = [&](float* base, int64_t ld, int m, const float (&val)[NB]) {  // NB consecutive columns of row m (m < M)
-            if (full) {
-                vecnb w;
-#pragma unroll
-                for (int f = 0; f < NB; ++f) w[f] = val[f];
-                *reinterpret_cast<vecnb_u*>(base + (int64_t)m * ld + n) = w;
-            } else {
-                for (int f = 0; f < NB; ++f)
-                    if (n + f < g.N) base[(int64_t)m * ld + n + f] = val[f];
-            }
-        };
-#pragma unroll
-        for (int i = 0; i < TMB; ++i) {
-            float racc[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int m = m0 + 16 * i + 4 * q + t;
-                const int mc = min(m, g.M - 1);
-                const bool mok = m < g.M;
-                float v4[NB];
-#pragma unroll
-                for (int f = 0; f < NB; ++f) v4[f] = acc[i][f][t] + biasv[f];
-                racc[t] = 0.f;
-                if (EPI == GD_EPI_BIAS_ACT) {
-                    if (g.act == 1) {
-#pragma unroll
-                        for (int f = 0; f < NB; ++f) v4[f] = tanhf(v4[f]);
-                    }
-                    if (mok) put(g.C, g.ldc, m, v4);
-                } else if (EPI == GD_EPI_LOSS) {
-                    const float c1 = g.r0 ? g.r0[mc] : 1.f;
-                    float tg[NB];
-                    if (g.aux_bits) {
-                        // {0,1} target rows as bitmaps: the lane's columns are NB bits of one word (n is a multiple of NB)
-                        const uint32_t w = g.aux_bits[(int64_t)mc * g.ldbits + min((int64_t)(n >> 5), g.ldbits - 1)];
-#pragma unroll
-                        for (int f = 0; f < NB; ++f) tg[f] = (float)((w >> ((n & 31) + f)) & 1u);
-                    } else {
-#pragma unroll
-                        for (int f = 0; f < NB; ++f) tg[f] = g.aux[(int64_t)mc * g.ldaux + min(n + f, g.N - 1)];
-                    }
-                    float dd[NB], ss = 0.f;
-#pragma unroll
-                    for (int f = 0; f < NB; ++f) {
-                        dd[f] = c1 * v4[f] - tg[f];
-                        if (mok && n + f < g.N) ss += dd[f] * dd[f];
-                    }
-                    if (mok) {
-                        put(g.C, g.ldc, m, dd);
-                        if (g.out2) put(g.out2, g.ldout2, m, v4);
-                    }
-                    racc[t] = ss;
-                } else {  // GD_EPI_POST
-                    const float c1 = g.r0[mc], c2 = g.r1[mc];
-                    const float p1 = has_r ? g.r2[mc] : 0.f, p2 = has_r ? g.r3[mc] : 0.f;
-                    const float sg = has_z ? g.r4[mc] : 0.f;
-                    float pr[NB], mn[NB];
-#pragma unroll
-                    for (int f = 0; f < NB; ++f) {
-                        const int nf = min(n + f, g.N - 1);
-                        const float xt = g.aux[(int64_t)mc * g.ldaux + nf];
-                        const float zz = has_z ? g.aux2[(int64_t)mc * g.ldaux2 + nf] : 0.f;
-                        pr[f] = has_r ? (p1 * xt - p2 * v4[f]) : v4[f];
-                        mn[f] = c1 * pr[f] + c2 * xt;
-                        if (has_z) mn[f] += sg * zz;
-                    }
-                    if (mok) {
-                        put(g.C, g.ldc, m, mn);
-                        if (g.out2) put(g.out2, g.ldout2, m, pr);
-                    }
-                }
-            }
-            if (EPI == GD_EPI_LOSS) {
-                // per-row sum of squares over the tile's columns: the 16 lanes r of a q-group hold one row
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    float sv = racc[t];
-                    sv += __shfl_xor(sv, 1);
-                    sv += __shfl_xor(sv, 2);
-                    sv += __shfl_xor(sv, 4);
-                    sv += __shfl_xor(sv, 8);
-                    const int m = m0 + 16 * i + 4 * q + t;
-                    if (r == 0 && m < g.M) g.rowpart[(int64_t)m * g.ld_rowpart + tn] = sv;
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);  // one block of rows at a time: keeps the epilogue's live registers bounded
-        }
-        if (nxt >= ntiles) break;
-        cur = nxt;
-    }
-    dr_wait<0>();
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-#pragma unroll
-        for (int i = 0; i < TMB; ++i) asm volatile("" ::"v"(xa[u][i]));
-#pragma unroll
-        for (int f = 0; f < NB; ++f) asm volatile("" ::"v"(xb[u][f]));
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// C[M,N] = A[M,K] * B[N,K]^T for a SMALL A and a LARGE B (the output layer with the fused row loss, reference
-// models/DNN.py:79-86 + gaussian_diffusion.py:335: A = hidden activations [batch, hidden], B = the [items, hidden] weight).
-// What dr_nt_kernel showed: a K-contiguous operand must not be fetched straight into the MFMA layout (16 quarter lines per
-// load).  Here
-//   * A comes PRE-TRANSPOSED, At[K, M] (a 1.6 MB copy made by dr_transpose_kernel right before the launch), and is streamed
-//     into registers exactly like dr_tn_kernel's operands: one dwordx4 load = rows m0 .. m0+63 of four k, plus one dword
-//     load for rows m0+64 .. m0+79 -- an 80-row tile (batch 400 = 5 x 80);
-//   * B is fetched in full 128-byte lines (8 lanes per row, 8 rows per load: "piece" u = rows 8u .. 8u+7 of a 32-k chunk),
-//     written to a wave-PRIVATE LDS image (swizzled like gemm_f32.hip's K-contiguous image: conflict-free) and read back as
-//     MFMA fragments with ds_read_b128.  Only the wave's own LDS queue orders the write and the read: no barrier, the eight
-//     waves of a workgroup stay independent (2 x 8 KB per wave, 128 KB per workgroup).
-// A fragment register component s of lane group q is k = 16 h + 4 q + s of its chunk half h, so A's lane group q loads k-row
-// 4 q + s at step s: voffset carries 4 q rows, the scalar offset walks s = 0..3 and then jumps to the next half.
-// One ring for everything, 8 steps (= one chunk) long: the loads of step sigma + 7 (A) and of piece u of chunk c + 2 (B) are
-// issued between the MFMAs of step sigma = (c, u); the piece that has landed by then ((c+1, u+1), issued 7 steps earlier) is
-// written to LDS at the start of the step; fragments are read at steps 3 (second half) and 7 (next chunk's first half).
-//     acc[e][b][t] = C[m0 + 16 q + 4 t + e][n0 + 16 b + r]   (e < 4),      acc[4][b][t] = C[m0 + 64 + 4 q + t][n0 + 16 b + r].
-// The ring is drained at the end of a tile (no operand load is in flight during the epilogue: nothing for hipcc to move);
-// the SIMD partner owns the matrix pipe meanwhile.
-// MEASURED (tools/gemm_probe, Yelp shape): correct and bit-identical to the LDS-tiled kernel, 0.262 ms against
-// 0.2705 ms -- not the 0.22 ms hoped for, so it stays OPT-IN (GDMCF_GEMM_DR bit 3).  Why: (i) 2 690 tiles on 1 024 SIMDs are
-// 2.63 tiles per SIMD: a third of the SIMDs run three tiles, the rest wait (the LDS-tiled kernel has the same 2.63 rounds);
-// (ii) with the loop's loads parked outside the matrices (no memory traffic at all) the kernel is just as slow: the loop is
-// bound by instruction issue -- a buffer_load blocks the SIMD's issue for ~50 cycles, 3 of them per 20 MFMAs (640 cycles) --
-// and a second wave per SIMD does not fill those gaps (one wave per SIMD: 0.199 ms for 2 tiles each, two: 0.200 ms).
-// ---------------------------------------------------------------------------------------------------------------------
-// Fill loads of dr_hl_kernel: with its ~100 live scalars hipcc spills SGPRs into VGPR lanes and reloads a scalar offset with
-// v_readlane right in front of the load that uses it.  An SGPR written by a VALU instruction must not be read by a
-// vector-memory instruction for 5 wait states; hipcc pads its OWN instructions, it cannot see into an asm statement -- the
-// load then uses the register's previous value (found the hard way: pieces of the first two chunks fetched from the
-// previous load's offset).  The guarded forms wait inside the statement; build.py:lint_vmcnt rejects any unguarded case.
-__device__ __forceinline__ f32x4 dr_load_g(i32x4 srd, uint32_t voff, uint32_t soff) {
-    f32x4 v;
-    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(srd), "s"(soff) : "memory");
-    return v;
-}
-__device__ __forceinline__ float dr_load1_g(i32x4 srd, uint32_t voff, uint32_t soff) {
-    float v;
-    asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(srd), "s"(soff) : "memory");
-    return v;
-}
-
-
-__global__ __launch_bounds__(256) void dr_transpose_kernel(const float* __restrict__ A, int64_t lda, int M, int K,
-                                                           float* __restrict__ At, int ldt) {
-    __shared__ float t[32][33];
-    const int k0 = blockIdx.x * 32, m0 = blockIdx.y * 32;
-    const int x = threadIdx.x & 31, y = threadIdx.x >> 5;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + y + 8 * i, k = k0 + x;
-        t[y + 8 * i][x] = (m < M && k < K) ? A[(int64_t)m * lda + k] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = k0 + y + 8 * i, m = m0 + x;
-        if (k < K && m < M) At[(int64_t)k * ldt + m] = t[x][y + 8 * i];
-    }
-}
-
-// Loop loads of dr_hl_kernel as READ-WRITE operands: a slot then is live all the time, so hipcc cannot hand its registers to an
-// accumulator between the ds_write that empties it and the load that refills it.  With "=v" outputs it did exactly that --
-// every MFMA of the loop wrote its result into a different register quadruple than it read (v_mfma v[112:115], .., v[60:63]):
-// legal, and measured no slower, but it mixes the accumulators into the ring and costs 22 registers (227 -> 205).
-__device__ __forceinline__ void dr_load_rw(f32x4& v, i32x4 srd, uint32_t voff, uint32_t soff) {
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(v) : "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dr_load1_rw(float& v, i32x4 srd, uint32_t voff, uint32_t soff) {
-    asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "+v"(v) : "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-// probe ablations (tools/gemm_probe.hip): park the loop's A / B loads outside their matrices (they return 0 without a fetch)
-#ifdef HL_NOA
-#define HL_KA(x) (0x80000000u)
-#else
-#define HL_KA(x) (x)
-#endif
-#ifdef HL_NOB
-#define HL_KB(x) (0x80000000u)
-#else
-#define HL_KB(x) (x)
-#endif
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void dr_hl_kernel(const DrArgs d) {
-    static_assert(EPI == GD_EPI_LOSS, "output layer with the fused row loss");
-    constexpr int LPS = 3;  // loads per step: A dwordx4, A dword, B dwordx4
-    constexpr int D = 7;    // steps in flight beside the one being multiplied; ring = 8 steps = one 32-k chunk
-    static_assert(LPS * D <= 63, "vmcnt is a 6-bit counter");
-    const GdGemm& g = d.g;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 15, q = lane >> 4;
-    extern __shared__ __attribute__((aligned(16))) float dr_lds[];
-    float* const lds = dr_lds + wave * 4096;  // 2 buffers x 64 rows x 32 k
-    // float offsets inside a buffer.  Write: piece u = rows 8u + (lane >> 3), 16-byte slot (lane & 7) ^ ((row >> 1) & 7); the
-    // swizzle term is (lane >> 4) for even u and 4 + (lane >> 4) for odd u.  Read: row 16 b + r, slot (4 h + q) ^ ((r >> 1) & 7).
-    const int w_ev = (lane >> 3) * 32 + (((lane & 7) ^ (lane >> 4)) << 2), w_od = w_ev ^ 16;
-    const int r_h0 = r * 32 + ((q ^ ((r >> 1) & 7)) << 2), r_h1 = r_h0 ^ 16;
-
-    // ---- tiles and tickets: as in dr_tn_kernel (panel = the 80-row tiles of one 64-column slice of B) ----
-    const int n_waves = gridDim.x * (blockDim.x >> 6);
-    const int minor = d.tiles_m, panels = d.tiles_n;
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    int qx = xcc & 7, visited = 0;
-    auto q_tiles = [&](int x) { return ((panels - x + 7) >> 3) * minor; };
-    auto tile_of = [&](int x, int t) { return ((t / minor) * 8 + x) * minor + t % minor; };
-    auto draw_blocking = [&]() {
-        for (;;) {
-            if (visited == 8) return -1;
-            unsigned int* c = &g_dr_ticket[d.ctr][qx][0];
-            unsigned int tk = dr_ticket_issue(c);
-            dr_wait<0>();
-            asm volatile("" : "+v"(tk));
-            const int t = __builtin_amdgcn_readfirstlane(tk);
-            const int n = q_tiles(qx);
-            if (t == n + n_waves - 1 && lane == 0) __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (t < n) return tile_of(qx, t);
-            qx = (qx + 1) & 7;
-            ++visited;
-        }
-    };
-    if (d.stagger > 0 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)  // (second wave of each SIMD; none in a 256-thread launch)
-        for (int i = 0; i < d.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-    int cur = draw_blocking();
-    if (cur < 0) return;
-    const int NCH = d.ksp;  // chunks per tile (even)
-    const i32x4 srdA = dr_srd(g.A, (uint32_t)(((int64_t)(g.K - 1) * g.lda + g.M) * 4));  // At[K, M]
-    const i32x4 srdB = dr_srd(g.B, (uint32_t)(((int64_t)(g.N - 1) * g.ldb + g.K) * 4));
-    const uint32_t sa1 = 4u * (uint32_t)g.lda, sa13 = 13u * sa1;
-    const uint32_t ub8 = 32u * (uint32_t)g.ldb;  // 8 rows of B
-    const int q1 = (NCH / 8) * 2, q2 = (NCH / 4) * 2, q3 = (NCH * 3 / 8) * 2;
-
-    for (;;) {
-        unsigned int* tctr = &g_dr_ticket[d.ctr][qx][0];
-        const bool drew = visited < 8;
-        unsigned int tick = drew ? dr_ticket_issue(tctr) : 0u;
-        const int tm = cur % d.tiles_m, tn = cur / d.tiles_m;
-        const int m0 = tm * 80, n0 = tn * 64;
-        const uint32_t oA4 = (uint32_t)(4 * q * g.lda + m0 + 4 * r) * 4u;
-        const uint32_t oA1 = (uint32_t)(4 * q * g.lda + m0 + 64 + r) * 4u;
-        const uint32_t oB = (uint32_t)(((int64_t)(n0 + (lane >> 3)) * g.ldb + 4 * (lane & 7)) * 4);
-        uint32_t ka = 0;    // A: scalar offset of the next step to issue
-        f32x4 ra4[8], G[8], FB[2][4];
-        float ra1[8];
-        f32x4 acc[5][4];
-#pragma unroll
-        for (int e = 0; e < 5; ++e)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) acc[e][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        __builtin_amdgcn_s_setprio(0);
-        // ---- fill: chunk 0 of B through LDS buffer 0; then, in the order the steady state would have issued them, piece 0 of
-        // chunk 1, and for u = 1..7 the A loads of step u - 1 and piece u of chunk 1 ----
-#pragma unroll
-        for (int u = 0; u < 8; ++u) G[u] = dr_load_g(srdB, oB, (uint32_t)u * ub8);
-        dr_wait<0>();
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            asm volatile("" : "+v"(G[u]));
-            *reinterpret_cast<f32x4*>(lds + u * 256 + ((u & 1) ? w_od : w_ev)) = G[u];
-        }
-        G[0] = dr_load_g(srdB, oB, 128u);
-#pragma unroll
-        for (int u = 1; u < 8; ++u) {
-            ra4[u - 1] = dr_load_g(srdA, oA4, ka);
-            ra1[u - 1] = dr_load1_g(srdA, oA1, ka);
-            ka += ((u - 1) & 3) == 3 ? sa13 : sa1;
-            G[u] = dr_load_g(srdB, oB, 128u + (uint32_t)u * ub8);
-        }
-        dr_wait<21>();
-        asm volatile("" : "=v"(ra4[7]));  // (slot 7 is first loaded by step 0: a defined value for its read-write operand)
-        asm volatile("" : "=v"(ra1[7]));
-        asm volatile("" : "+v"(G[0]));
-        *reinterpret_cast<f32x4*>(lds + 2048 + w_ev) = G[0];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) FB[0][b] = *reinterpret_cast<const f32x4*>(lds + b * 512 + r_h0);
-        uint32_t kb = 256u;  // B: byte offset of chunk c + 2 inside a row
-
-        for (int c0 = 0; c0 < NCH; c0 += 2) {
-            if (c0 == q1) __builtin_amdgcn_s_setprio(1);
-            else if (c0 == q2) __builtin_amdgcn_s_setprio(2);
-            else if (c0 == q3) __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-            for (int uu = 0; uu < 16; ++uu) {
-                const int p = uu >> 3, u = uu & 7, h = u >> 2, sx = u & 3;
-                const int v = (u + 7) & 7;  // ring slot (= position inside its chunk) of step sigma + 7
-                const int w = (u + 1) & 7;  // piece written to LDS in this step: (c+1, u+1), or (c+2, 0) at u = 7
-                // chunks past the end of the tile are never multiplied: park their B loads outside the matrix (returns 0, no fetch)
-                const uint32_t kbs = (c0 + p + 2 < NCH) ? kb : 0x80000000u;
-                dr_wait<LPS * (D - 1)>();
-                asm volatile("" : "+v"(ra4[u]));
-                asm volatile("" : "+v"(ra1[u]));
-                asm volatile("" : "+v"(G[w]));
-                *reinterpret_cast<f32x4*>(lds + ((u < 7) ? (1 - p) : p) * 2048 + w * 256 + ((w & 1) ? w_od : w_ev)) = G[w];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < 20; ++i) {
-                    const int e = i >> 2, b = i & 3;
-                    const float av = e < 4 ? ra4[u][e] : ra1[u];
-                    acc[e][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, FB[h][b][sx], acc[e][b], 0, 0, 0);
-                    if (i == 1) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        dr_load_rw(ra4[v], srdA, oA4, HL_KA(ka));
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else if (i == 5) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        dr_load1_rw(ra1[v], srdA, oA1, HL_KA(ka));
-                        ka += (v & 3) == 3 ? sa13 : sa1;
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else if (i == 9) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        dr_load_rw(G[u], srdB, oB, HL_KB(kbs + (uint32_t)u * ub8));
-                        if (u == 7) kb += 128u;
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else if (i == 13 && u == 3) {
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int bb = 0; bb < 4; ++bb) FB[1][bb] = *reinterpret_cast<const f32x4*>(lds + p * 2048 + bb * 512 + r_h1);
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else if (i == 13 && u == 7) {
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int bb = 0; bb < 4; ++bb) FB[0][bb] = *reinterpret_cast<const f32x4*>(lds + (1 - p) * 2048 + bb * 512 + r_h0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // ---- drain: whatever is still in flight belongs to steps past the tile; its registers stay untouched until it landed ----
-        dr_wait<0>();
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            asm volatile("" ::"v"(ra4[u]));
-            asm volatile("" ::"v"(ra1[u]));
-            asm volatile("" ::"v"(G[u]));
-        }
-        // the next tile (the ticket was issued before the fill: long landed)
-        int nxt = -1;
-        if (drew) {
-            asm volatile("" : "+v"(tick));
-            const int tk = __builtin_amdgcn_readfirstlane(tick);
-            const int nq = q_tiles(qx);
-            if (tk == nq + n_waves - 1 && lane == 0) __hip_atomic_store(tctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk < nq) {
-                nxt = tile_of(qx, tk);
-            } else {
-                qx = (qx + 1) & 7;
-                ++visited;
-                nxt = -2;  // draw after the epilogue (a few times per wave, at the end of the launch)
-            }
-        }
-        // ---- epilogue (gaussian_diffusion.py:335): d = alpha * (acc + bias) - target, stored; per-row sum of d^2 over the tile ----
-        {
-            int ncl[4];
-            bool nok[4];
-            float biasv[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int n = n0 + 16 * b + r;
-                nok[b] = n < g.N;
-                ncl[b] = min(n, g.N - 1);
-                biasv[b] = g.bias ? g.bias[ncl[b]] : 0.f;
-            }
-#pragma unroll
-            for (int e = 0; e < 5; ++e) {
-                float tg[4][4], c1v[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int m = e < 4 ? m0 + 16 * q + 4 * t + e : m0 + 64 + 4 * q + t;
-                    const int mc = min(m, g.M - 1);
-                    c1v[t] = g.r0 ? g.r0[mc] : 1.f;
-                    if (g.aux_bits) {
-                        // {0,1} target rows as bitmaps: the tile's 64 columns are two words of the row (n0 is a multiple of 64)
-                        uint32_t wv[2];
-#pragma unroll
-                        for (int jj = 0; jj < 2; ++jj)
-                            wv[jj] = g.aux_bits[(int64_t)mc * g.ldbits + min((int64_t)((n0 >> 5) + jj), g.ldbits - 1)];
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) tg[t][b] = (float)((wv[b >> 1] >> (16 * (b & 1) + r)) & 1u);
-                    } else {
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) tg[t][b] = g.aux[(int64_t)mc * g.ldaux + ncl[b]];
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int m = e < 4 ? m0 + 16 * q + 4 * t + e : m0 + 64 + 4 * q + t;
-                    const bool mok = m < g.M;
-                    float ss = 0.f;
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        const float vv = acc[e][b][t] + biasv[b];
-                        const float dd = c1v[t] * vv - tg[t][b];
-                        if (mok && nok[b]) {
-                            if (g.out2) g.out2[(int64_t)m * g.ldout2 + ncl[b]] = vv;
-                            g.C[(int64_t)m * g.ldc + ncl[b]] = dd;
-                            ss += dd * dd;
-                        }
-                    }
-                    ss += __shfl_xor(ss, 1);
-                    ss += __shfl_xor(ss, 2);
-                    ss += __shfl_xor(ss, 4);
-                    ss += __shfl_xor(ss, 8);
-                    if (r == 0 && mok) g.rowpart[(int64_t)m * g.ld_rowpart + tn] = ss;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (nxt == -2) nxt = draw_blocking();
-        if (nxt < 0) break;
-        cur = nxt;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
 // C[M,N] = A[M,K] * B[N,K]^T for a batch-sized A and a LARGE B with a fused row-loss / posterior epilogue (the output layer:
 // reference models/DNN.py:83-86 with gaussian_diffusion.py:335 in training, :451-498 in the reverse loop), round 4:
 // ONE FAT TILE PER WAVE, ONE WAVE PER SIMD, ONE PASS.
 //
-// What rounds 2-3 established about this product: the LDS-tiled kernel and the hybrid kernel both end at 0.6 of
+// What rounds 2-3 established about this product: the LDS-tiled kernel and the retired hybrid kernel both end at 0.6 of
 // the matrix rate because (i) 1 345 / 2 690 tiles on 512 / 1 024 slots are 2.63 rounds -- a third of the chip runs three -- and
 // (ii) the loop is bound by instruction ISSUE: v_mfma_f32_16x16x4_f32 shares the vector issue port, so every load, LDS access
 // and barrier beside the MFMAs is matrix time lost (round 4: even another wave's arithmetic does not overlap).  Both have one
@@ -1395,7 +847,7 @@ __global__ __launch_bounds__(512, 2) void dr_hl_kernel(const DrArgs d) {
 //   * A (the hidden activations, L2-resident) is loaded straight into the MFMA layout: lane (j = lane & 15, q = lane >> 4) reads
 //     A[m0 + 16 i + j][k0 + 4 q .. + 3] -- one 16-byte load per row block and chunk; component s is the operand of the MFMA that
 //     takes k = k0 + 4 q + s (A and B permuted alike).  1.6 MB read by every wave: half lines are no concern here (they were for
-//     the STREAMED operand of dr_nt_kernel).
+//     the STREAMED operand of the retired K-contiguous register-streaming kernel).
 //   * B (the weight, streamed from HBM once per row tile: the five row tiles of a column panel run on one XCD) is fetched in
 //     pieces of 16 rows x 64 B, staged in registers for two k steps, written to a wave-PRIVATE LDS image (rows of 16 floats,
 //     16-byte slot s of row r at s ^ 2 ((r >> 2) & 1): conflict-free for the ds_read_b128 lane groups) and read back as
@@ -1819,19 +1271,6 @@ int dr_fat_go(const DrArgs& d, int epi, int n_cu, hipStream_t s) {
     return GDMCF_OK;
 }
 
-void dr_hl_go(const DrArgs& d, int n_cu, hipStream_t s) {
-    // GDMCF_HL_WAVES=4: one wave per SIMD (256 threads; 96 KB of LDS requested so that only one workgroup fits a CU)
-    static const int waves = getenv("GDMCF_HL_WAVES") ? atoi(getenv("GDMCF_HL_WAVES")) : 8;
-    if (waves == 4) hipLaunchKernelGGL((dr_hl_kernel<GD_EPI_LOSS>), dim3(n_cu), dim3(256), 96 * 1024, s, d);
-    else hipLaunchKernelGGL((dr_hl_kernel<GD_EPI_LOSS>), dim3(n_cu), dim3(512), 128 * 1024, s, d);
-}
-
-// tile = 16 TMB rows x 16 NB columns; D chunks in flight beside the one being multiplied (ring of D + 1 slots)
-template <int TMB, int NB, int D, int EPI>
-void dr_nt_go(const DrArgs& d, int n_cu, hipStream_t s) {
-    hipLaunchKernelGGL((dr_nt_kernel<TMB, NB, D, EPI>), dim3(n_cu), dim3(512), 0, s, d);
-}
-
 int dr_cu_count_fwd();
 template <int D, bool NTL>
 int dr_tn_adamw_go(const DrMultiArgs& d, hipStream_t s) {
@@ -1863,7 +1302,7 @@ int dr_tn_adamw_go(const DrMultiArgs& d, hipStream_t s) {
 
 template <int D>
 int dr_tn_go(const DrArgs& d, hipStream_t s) {
-    hipLaunchKernelGGL((dr_tn_kernel<1, 1, D, GD_EPI_STORE>), dim3(dr_cu_count_fwd()), dim3(512), 0, s, d);
+    hipLaunchKernelGGL((dr_tn_kernel<1, 1, D>), dim3(dr_cu_count_fwd()), dim3(512), 0, s, d);
     return GDMCF_OK;
 }
 
@@ -1881,11 +1320,27 @@ static int dr_cu_count() {
     return n_cu;
 }
 
+// Route switches: which products the kernels of this file take (a product whose switch is off goes to the LDS-tiled kernels).
+// Read once, each variable on unless set to 0 (DESIGN.md lists them); tools/gemm_probe.hip assigns to the struct directly.
+struct DrRoutes {
+    bool dw;     // GDMCF_DR_DW: f32 weight gradients, plain and fused-AdamW (dr_tn_kernel, dr_tn_adamw_kernel)
+    bool adamw;  // GDMCF_DR_ADAMW: the fused-AdamW ones among them (dr_tn_adamw_kernel)
+    bool kn;     // GDMCF_DR_KN: the input gradient and the cached-W^T forward (dr_kn_kernel; also sizes the workspace)
+    bool fat;    // GDMCF_DR_FAT: the output layer with the fused row-loss / posterior epilogue (dr_fat_kernel)
+};
+static bool dr_env_on(const char* name) {
+    const char* v = getenv(name);
+    return v == nullptr || atoi(v) != 0;
+}
+static DrRoutes& dr_routes() {
+    static DrRoutes r = {dr_env_on("GDMCF_DR_DW"), dr_env_on("GDMCF_DR_ADAMW"), dr_env_on("GDMCF_DR_KN"), dr_env_on("GDMCF_DR_FAT")};
+    return r;
+}
+
 // dr_kn_kernel: 80 x 128 tiles, one (split, tile) task per wave slot (4 per CU): as many splits as fill the slots once -- or 0 when the
-// product is not one the kernel takes (rows that do not tile by 80 within 12 %, a reduction too short to split, few slots).
+// product is not one the kernel takes (switched off, rows that do not tile by 80 within 12 %, a reduction too short to split, few slots).
 int gd_dr_kn_splits(int M, int N, int K) {
-    static const int on_env = getenv("GDMCF_GEMM_DR") ? atoi(getenv("GDMCF_GEMM_DR")) : 49;
-    if (!(on_env & 32) || M < 16 || N < 64 || K < 4096) return 0;
+    if (!dr_routes().kn || M < 16 || N < 64 || K < 4096) return 0;
     const long tiles = (long)gd_cdiv(M, 80) * gd_cdiv(N, 128);
     if ((long)gd_cdiv(M, 80) * 80 * 100 > (long)M * 112) return 0;  // 80-row tiles: at most 12 % padding
     if ((long)gd_cdiv(N, 128) * 128 * 100 > (long)N * 112) return 0;
@@ -1907,10 +1362,6 @@ int gd_dr_kn_splits(int M, int N, int K) {
 #include <atomic>
 static std::atomic<unsigned> g_dr_seq_eager{0}, g_dr_seq_graph{0};
 static int dr_ticket_slot(hipStream_t s) {
-    // GDMCF_DR_TICKET_SLOT=n pins every launch to set n: the behaviour before round 4, kept as the negative control of
-    // tests/test_gpu_reentrancy.py (overlapping launches then share their queues and lose tiles)
-    static const int pinned = getenv("GDMCF_DR_TICKET_SLOT") ? atoi(getenv("GDMCF_DR_TICKET_SLOT")) : -1;
-    if (pinned >= 0) return pinned & 31;
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) {
         (void)hipGetLastError();  // (the legacy stream while another stream captures: not a capture of this launch)
@@ -1977,13 +1428,6 @@ static int dr_adamw_launch(DrMultiArgs& m, int depth, hipStream_t s) {
     return dr_tn_adamw_go<7>(m, s);
 }
 
-int g_gd_dr_force = -1;  // tools/gemm_probe.hip: overrides GDMCF_GEMM_DR per call when >= 0
-static int dr_on_flags() {
-    static const int on_env = getenv("GDMCF_GEMM_DR") ? atoi(getenv("GDMCF_GEMM_DR")) : 49;
-    return g_gd_dr_force >= 0 ? g_gd_dr_force : on_env;  // bit 0: weight gradients (default), bit 1: forward
-    // products (opt-in: measured SLOWER than the LDS-tiled kernels -- 0.279 vs 0.270 ms for the Yelp loss product: a K-contiguous
-    // operand costs 16 half-line L1 accesses per load instead of 8 full lines, TCP accesses x3.6, 20 % of the wave cycles waiting)
-}
 static int dr_stagger() {
     static const int stagger = getenv("GDMCF_DR_STAGGER") ? atoi(getenv("GDMCF_DR_STAGGER")) : 3;
     return stagger;
@@ -1991,12 +1435,9 @@ static int dr_stagger() {
 // (the fused-AdamW epilogue: hipcc rotates accumulators through ring slots there, which the first, set-based lint
 // (build.py:lint_ring_registers) cannot tell from a copy of in-flight data; the per-register analysis that replaced it for
 // this variant (lint_vmcnt: no instruction touches a register whose load the counted waits do not cover) verifies it clean,
-// and tests/test_gpu_fullsize.py checks every element of W / exp_avg / exp_avg_sq at the full shapes.  GDMCF_GEMM_DR bit 2
-// clear (e.g. =1 with bit 2 masked by GDMCF_DR_NO_FUSED=1) sends the fused products back to the LDS-tiled kernel.)
-static bool dr_fused_on() {
-    static const int no_fused = getenv("GDMCF_DR_NO_FUSED") ? atoi(getenv("GDMCF_DR_NO_FUSED")) : 0;
-    return (dr_on_flags() & 1) && !no_fused;
-}
+// and tests/test_gpu_fullsize.py checks every element of W / exp_avg / exp_avg_sq at the full shapes.  GDMCF_DR_ADAMW=0 sends
+// the fused products back to the LDS-tiled kernel.)
+static bool dr_fused_on() { return dr_routes().dw && dr_routes().adamw; }
 
 // Several weight-gradient products with AdamW as ONE launch of dr_tn_adamw_kernel (gdmcf_linear_bwd_weight_adamw_multi_f32).
 // All or nothing: GD_DR_NOT_TAKEN (nothing launched) unless every product is one the kernel takes, in f32, with the same ring
@@ -2045,8 +1486,8 @@ int gd_gemm_dr_adamw_multi(GdGemm* gs, int n, hipStream_t s) {
 
 // Returns GD_DR_NOT_TAKEN when the product is not one this file handles (the caller falls back to the LDS-tiled kernels).
 int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
-    const int on = dr_on_flags();
-    if (!on || g.bf16) return GD_DR_NOT_TAKEN;
+    const DrRoutes& on = dr_routes();
+    if (g.bf16) return GD_DR_NOT_TAKEN;
     if (g.accumulate || g.C16 || (g.splits > 1 && epi != GD_EPI_SLAB)) return GD_DR_NOT_TAKEN;  // (slabs: dr_kn_kernel sets its own split count)
     const int64_t lim = (int64_t)1 << 32;  // 32-bit byte offsets inside every matrix
     DrArgs d = {};
@@ -2054,7 +1495,7 @@ int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
     d.stagger = dr_stagger();
     // the fused-AdamW product: the one-element case of gd_gemm_dr_adamw_multi
     if (epi == GD_EPI_ADAMW && layA == GD_LAY_MC && layB == GD_LAY_MC) return gd_gemm_dr_adamw_multi(&g, 1, s);
-    if ((on & 1) && layA == GD_LAY_MC && layB == GD_LAY_MC && epi == GD_EPI_STORE) {
+    if (on.dw && layA == GD_LAY_MC && layB == GD_LAY_MC && epi == GD_EPI_STORE) {
         const int n_user = g.N;
         float* bias_db = nullptr;
         int best = 9;
@@ -2075,8 +1516,8 @@ int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
         if (bias_db) g.out2 = nullptr;  // taken: the caller skips its column-sum pass
         return gd_launch_status("gemm_dr");
     }
-    // bit 5 (default on): the input gradient, split-K slabs, both operands straight into registers (dr_kn_kernel)
-    if ((on & 32) && layA == GD_LAY_KC && layB == GD_LAY_MC && epi == GD_EPI_SLAB) {
+    // the input gradient, split-K slabs, both operands straight into registers (dr_kn_kernel)
+    if (on.kn && layA == GD_LAY_KC && layB == GD_LAY_MC && epi == GD_EPI_SLAB) {
         const int splits = gd_dr_kn_splits(g.M, g.N, g.K);
         const size_t need = (size_t)splits * g.M * g.ldc * sizeof(float);
         if (splits > 0 && g.ldc >= g.N && (g.ldc & 3) == 0 && g.ws_cap >= need && g.slab_stride >= (int64_t)g.M * g.ldc &&
@@ -2101,8 +1542,8 @@ int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
             return gd_launch_status("gemm_dr_kn");
         }
     }
-    // bit 4 (default on): the output layer with a fused epilogue as ONE FAT TILE PER WAVE (dr_fat_kernel)
-    if ((on & 16) && layA == GD_LAY_KC && layB == GD_LAY_KC && (epi == GD_EPI_LOSS || epi == GD_EPI_POST)) {
+    // the output layer with a fused epilogue as ONE FAT TILE PER WAVE (dr_fat_kernel)
+    if (on.fat && layA == GD_LAY_KC && layB == GD_LAY_KC && (epi == GD_EPI_LOSS || epi == GD_EPI_POST)) {
         const int n_cu = dr_cu_count();
         const int tiles_m = gd_cdiv(g.M, 80);
         bool ok = (int64_t)g.M * g.lda * 4 < ((int64_t)1 << 31) && (int64_t)g.N * g.ldb * 4 < lim && g.lda >= g.K && g.ldb >= g.K &&
@@ -2130,10 +1571,8 @@ int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
             d.tiles_m = tiles_m;
             d.tiles_n = gd_cdiv(g.N, 16 * nb);
             d.m_fastest = 1;
-            d.ksp = (gd_cdiv(g.K, 16) + 1) & ~1;  // chunks of 16 k
+            d.ksp = gd_cdiv(g.K, 16);  // chunks of 16 k
             {
-                static const int odd_on = getenv("GDMCF_FAT_ODD") ? atoi(getenv("GDMCF_FAT_ODD")) : 1;  // 0: the old even count (A/B)
-                if (odd_on) d.ksp = gd_cdiv(g.K, 16);
                 // x_t prefetch of the reverse step: this many chunks before the end of the k loop (0: off; A/B knob)
                 static const int pf = getenv("GDMCF_FAT_PF") ? atoi(getenv("GDMCF_FAT_PF")) : 10;
                 d.stagger = pf;  // (the field is unused by this kernel otherwise)
@@ -2157,93 +1596,6 @@ int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
             t_gd_last_gemm = 4;
             return gd_launch_status("gemm_dr");
         }
-    }
-    // bit 3: the output layer with the fused row loss on the hybrid kernel (A pre-transposed into the tail of the row-sum scratch)
-    if ((on & 8) && layA == GD_LAY_KC && layB == GD_LAY_KC && epi == GD_EPI_LOSS) {
-        if ((int64_t)g.N * g.ldb * 4 >= ((int64_t)1 << 31) || (int64_t)g.K * g.M * 4 >= lim) return GD_DR_NOT_TAKEN;
-        if (g.lda < g.K || g.ldb < g.K || g.K < 256 || g.M < 64) return GD_DR_NOT_TAKEN;
-        if (g.ldb != g.K && (g.K & 31)) return GD_DR_NOT_TAKEN;  // a chunk that reaches past K reads the next row: it must hold weights, not padding
-        if ((long)gd_cdiv(g.M, 80) * 80 * 100 > (long)g.M * 112) return GD_DR_NOT_TAKEN;  // 80-row tiles: at most 12 % padding
-        const int tiles_m = gd_cdiv(g.M, 80), tiles_n = gd_cdiv(g.N, 64);
-        if ((long)tiles_m * tiles_n < 1024) return GD_DR_NOT_TAKEN;
-        if (g.aux_bits && g.ldbits < (g.N + 31) / 32) return GD_DR_NOT_TAKEN;
-        // scratch: the caller's row-sum buffer holds M x gdmcf_loss_tiles(N) floats; this kernel needs M x tiles_n of them
-        const int64_t used = ((int64_t)g.M * tiles_n + 3) & ~(int64_t)3;
-        if (g.rowpart == nullptr || used + (int64_t)g.K * g.M > (int64_t)g.M * g.ld_rowpart) return GD_DR_NOT_TAKEN;
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dr_hl_kernel<GD_EPI_LOSS>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            if (e != hipSuccess) {
-                gdmcf_set_error("hipFuncSetAttribute(dr_hl_kernel, LDS=128 KB): %s", hipGetErrorString(e));
-                return GDMCF_E_HIP;
-            }
-            attr_set = true;
-        }
-        float* at = g.rowpart + used;
-        d.tiles_m = tiles_m;
-        d.tiles_n = tiles_n;
-        d.m_fastest = 1;
-        d.ksp = (gd_cdiv(g.K, 32) + 1) & ~1;  // chunks of 32 k, an even number of them
-        g.tiles_m = tiles_m;
-        g.tiles_n = tiles_n;
-        g.ld_rowpart = tiles_n;
-        d.g = g;
-        d.ctr = dr_ticket_slot(s);
-        d.g.A = at;
-        d.g.lda = g.M;
-        {
-            GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
-            hipLaunchKernelGGL(dr_transpose_kernel, dim3(gd_cdiv(g.K, 32), gd_cdiv(g.M, 32)), dim3(256), 0, s, g.A, g.lda, g.M, g.K, at, g.M);
-            dr_hl_go(d, dr_cu_count(), s);
-        }
-        t_gd_last_gemm = 5;
-        return gd_launch_status("gemm_dr");
-    }
-    if ((on & 2) && layA == GD_LAY_KC && layB == GD_LAY_KC && (epi == GD_EPI_LOSS || epi == GD_EPI_POST)) {
-        if ((int64_t)g.M * g.lda * 4 >= lim || (int64_t)g.N * g.ldb * 4 >= lim) return GD_DR_NOT_TAKEN;
-        if (g.lda < g.K || g.ldb < g.K || g.K < 256) return GD_DR_NOT_TAKEN;
-        // batch-sized M in blocks of 16 rows: 5 blocks (80 rows) when that pads little (400 = 5 x 80), else 4
-        const int tmb = ((long)gd_cdiv(g.M, 80) * 80 * 100 <= (long)gd_cdiv(g.M, 64) * 64 * 103) ? 5 : 4;
-        // 64-column tiles halve the operand traffic per FLOP, 32-column tiles quantise better over 1 024 SIMDs (Yelp loss product:
-        // 2 690 tiles of 80 x 64 = 2.6 per SIMD against 5 375 of 80 x 32)
-        static const int nb_env = getenv("GDMCF_DR_NB") ? atoi(getenv("GDMCF_DR_NB")) : 0;
-        const int n_cu = dr_cu_count();
-        int nb = 4;
-        {
-            const long t4 = (long)gd_cdiv(g.M, 16 * tmb) * gd_cdiv(g.N, 64);
-            const long per = (t4 + 4 * n_cu - 1) / (4 * n_cu);           // rounds of one tile per SIMD
-            if (t4 * 100 < per * 4 * n_cu * 92 && per < 6) nb = 2;       // the last round would be < 92 % full
-        }
-        if (nb_env == 2 || nb_env == 4) nb = nb_env;
-        d.tiles_m = gd_cdiv(g.M, 16 * tmb);
-        d.tiles_n = gd_cdiv(g.N, 16 * nb);
-        if ((long)d.tiles_m * d.tiles_n < 1024) return GD_DR_NOT_TAKEN;
-        if (epi == GD_EPI_LOSS && (g.ld_rowpart < d.tiles_n || g.rowpart == nullptr)) return GD_DR_NOT_TAKEN;
-        if (epi == GD_EPI_LOSS && g.aux_bits && g.ldbits < (g.N + 31) / 32) return GD_DR_NOT_TAKEN;
-        d.m_fastest = 1;
-        const int nc = gd_cdiv(g.K, 16);
-        const int ring = nb == 4 ? 2 : 3;
-        d.ksp = gd_cdiv(nc, ring) * ring;  // a multiple of the ring size
-        g.tiles_m = d.tiles_m;
-        g.tiles_n = d.tiles_n;
-        d.g = g;
-        d.ctr = dr_ticket_slot(s);
-        {
-            GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
-#define GD_DR_NT(T, NBV, DV)                                                            \
-    do {                                                                                \
-        if (epi == GD_EPI_LOSS) dr_nt_go<T, NBV, DV, GD_EPI_LOSS>(d, n_cu, s);          \
-        else dr_nt_go<T, NBV, DV, GD_EPI_POST>(d, n_cu, s);                             \
-    } while (0)
-            if (tmb == 5 && nb == 4) GD_DR_NT(5, 4, 1);
-            else if (tmb == 5) GD_DR_NT(5, 2, 2);
-            else if (nb == 4) GD_DR_NT(4, 4, 1);
-            else GD_DR_NT(4, 2, 2);
-#undef GD_DR_NT
-        }
-        t_gd_last_gemm = 6;
-        return gd_launch_status("gemm_dr");
     }
     return GD_DR_NOT_TAKEN;
 }

@@ -238,65 +238,6 @@ def test_weight_gradient_product_every_element_against_float64(B, N, K):
         assert torch.equal(dW, outs[0])
 
 
-_HL_SCRIPT = r'''
-import sys, torch
-sys.path.insert(0, {root!r})
-from gdmcf_amd import _lib
-lib = _lib.load()
-dev = "cuda:0"
-for (B, N, K, bits) in [(400, 34395, 1000, 0), (400, 34395, 1000, 1), (400, 94949, 1000, 1), (240, 40000, 520, 0)]:
-    g = torch.Generator(device="cpu").manual_seed(B + N + K + bits)
-    h = torch.randn(B, K, generator=g).to(dev)
-    W = (torch.randn(N, K, generator=g) * 0.05).to(dev)
-    bias = torch.randn(N, generator=g).to(dev)
-    alpha = (torch.rand(B, generator=g) + 0.5).to(dev)
-    tgt = (torch.rand(B, N, generator=g) < 0.02).float().to(dev)
-    ldd = (N + 31) // 32 * 32
-    diff = torch.full((B, ldd), float("nan"), device=dev)
-    nt = lib.gdmcf_loss_tiles(N)
-    rowpart = torch.zeros(B * nt, device=dev)
-    rowsum = torch.zeros(B, device=dev)
-    if bits:
-        words = (N + 31) // 32
-        pad = torch.zeros(B, words * 32, device=dev)
-        pad[:, :N] = tgt
-        packed = (pad.view(B, words, 32).to(torch.int64) << torch.arange(32, device=dev)).sum(-1)  # bit n & 31 of word n >> 5
-        packed = torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed).to(torch.int32).contiguous()
-        _lib.check(lib.gdmcf_linear_loss_fwd_bits_f32(h.data_ptr(), K, W.data_ptr(), K, bias.data_ptr(), packed.data_ptr(), words,
-                                                      alpha.data_ptr(), B, N, K, None, 0, diff.data_ptr(), ldd, rowpart.data_ptr(),
-                                                      rowsum.data_ptr(), _lib.stream_ptr()))
-    else:
-        _lib.check(lib.gdmcf_linear_loss_fwd_f32(h.data_ptr(), K, W.data_ptr(), K, bias.data_ptr(), tgt.data_ptr(), N,
-                                                 alpha.data_ptr(), B, N, K, None, 0, diff.data_ptr(), ldd, rowpart.data_ptr(),
-                                                 rowsum.data_ptr(), _lib.stream_ptr()))
-    torch.cuda.synchronize()
-    ref = alpha.double()[:, None] * (h.double() @ W.double().t() + bias.double()) - tgt.double()
-    err = float((diff[:, :N].double() - ref).abs().max())
-    rs = float(((rowsum.double() - (ref * ref).sum(1)).abs() / (ref * ref).sum(1)).max())
-    print("case", B, N, K, bits, "max err", err, "row sums", rs)
-    used = (B * ((N + 63) // 64) + 3) // 4 * 4  # the hybrid kernel keeps its transposed copy of h behind the row partials:
-    assert torch.equal(rowpart[used:used + K * B].view(K, B), h.t()), "the hybrid kernel did not run"  # proof that it ran
-    assert err <= 2e-5 * float(ref.abs().max()), err
-    assert rs <= 2e-6, rs
-print("HL-OK")
-'''
-
-
-def test_output_layer_loss_product_on_the_opt_in_hybrid_kernel(tmp_path):
-    """csrc/gemm_dr.hip dr_hl_kernel (GDMCF_GEMM_DR bit 3: small operand pre-transposed and register-streamed, large operand
-    through wave-private LDS; DESIGN 4.1c) through the C ABI of the fused loss layer (gaussian_diffusion.py:335): every element
-    of alpha * (h W^T + b) - target and the row sums of its square against float64, float and bitmap targets, Yelp and
-    Amazon-Book widths and a ragged shape.  The switch is read once per process, so the check runs in ONE child process."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = tmp_path / "hl_check.py"
-    script.write_text(_HL_SCRIPT.format(root=root))
-    env = dict(os.environ, GDMCF_GEMM_DR="9")
-    r = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "HL-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
-
-
 @pytest.mark.parametrize("which,B,N,K", [("fwd", 400, 1000, 34405), ("fwd", 400, 1000, 94959), ("dinput", 400, 34395, 1000),
                                          ("dinput", 400, 94949, 1000), ("dinput_lds", 400, 34395, 1000), ("dinput", 230, 20003, 1000),
                                          ("fwd_wt", 400, 1000, 34405), ("fwd_wt", 400, 1000, 94959), ("fwd_wt", 230, 1000, 20003),
@@ -307,8 +248,8 @@ def test_lds_tiled_products_every_element_against_float64_twenty_launches(which,
     lint (build.py:lint_vmcnt) cannot follow -- so its guard is THIS test: the first-layer forward product
     (gdmcf_linear_fwd_f32: split-K slabs + reducer, bias, tanh; reference models/DNN.py:79-81), the input-gradient product
     (gdmcf_linear_bwd_input_f32; main.py:350: on dr_kn_kernel, both operands straight into registers, by default -- a ragged shape
-    with row / column / K tails included -- and on the LDS-tiled kernel with GDMCF_GEMM_DR=17) and the fused-loss product ON THE
-    LDS-TILED KERNEL (GDMCF_GEMM_DR=1: the fat-tile kernel that serves it by default since round 4 is switched off) at the Yelp and Amazon-Book shapes and a ragged one: EVERY
+    with row / column / K tails included -- and on the LDS-tiled kernel with GDMCF_DR_KN=0) and the fused-loss product ON THE
+    LDS-TILED KERNEL (GDMCF_DR_FAT=0 GDMCF_DR_KN=0: the fat-tile kernel that serves it by default since round 4 is switched off) at the Yelp and Amazon-Book shapes and a ragged one: EVERY
     element against float64, then twenty more launches bit for bit (a register consumed before its load has landed shows up as
     a few elements off in SOME launches)."""
     import subprocess
@@ -316,9 +257,9 @@ def test_lds_tiled_products_every_element_against_float64_twenty_launches(which,
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "lds_check.py"
     script.write_text(_LDS_SCRIPT.format(root=root, which=which.replace("_lds", "") if which.startswith("dinput") else which, B=B, N=N, K=K))
-    env = dict(os.environ, GDMCF_GEMM_DR="1") if which == "loss_lds" else dict(os.environ)
+    env = dict(os.environ, GDMCF_DR_FAT="0", GDMCF_DR_KN="0") if which == "loss_lds" else dict(os.environ)
     if which == "dinput_lds":  # the input gradient ON THE LDS-TILED KERNEL (dr_kn_kernel, its default since round 4, switched off)
-        env["GDMCF_GEMM_DR"] = "17"
+        env["GDMCF_DR_KN"] = "0"
     r = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "LDS-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
 
@@ -366,9 +307,9 @@ elif which == "dinput":   # dA[B, K] = rs * (dZ[B, N] W[N, K]) * (1 - act^2)
         _lib.check(lib.gdmcf_linear_bwd_input_f32(dZ.data_ptr(), N, W.data_ptr(), K, rs.data_ptr(), act.data_ptr(), K, 1, B, N, K,
                                                   out.data_ptr(), K, ws.data_ptr(), ws.numel(), st))
         torch.cuda.synchronize()
-        # since the end of round 4 the register-streaming kernel dr_kn_kernel serves this product (5); GDMCF_GEMM_DR=17 -> LDS-tiled (1)
+        # since the end of round 4 the register-streaming kernel dr_kn_kernel serves this product (5); GDMCF_DR_KN=0 -> LDS-tiled (1)
         import os
-        want = 1 if os.environ.get("GDMCF_GEMM_DR") == "17" else 5
+        want = 1 if os.environ.get("GDMCF_DR_KN") == "0" else 5
         assert lib.gdmcf_debug_last_gemm() == want, (lib.gdmcf_debug_last_gemm(), want)
         return out
     ref = rs.double()[:, None] * (dZ.double() @ W.double()) * (1 - act.double() ** 2)

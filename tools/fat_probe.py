@@ -1,5 +1,5 @@
 """Times the output-layer products (fused loss / posterior epilogue) through the C ABI: fat-tile kernel (default) against the
-LDS-tiled kernel (GDMCF_GEMM_DR=1), Yelp and Amazon-Book widths.   python tools/fat_probe.py [reps]"""
+LDS-tiled kernel (GDMCF_DR_FAT=0), Yelp and Amazon-Book widths.   python tools/fat_probe.py [reps]"""
 import os, sys
 import torch
 sys.path.insert(0, ".")
