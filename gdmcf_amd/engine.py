@@ -14,58 +14,19 @@ HBM layout (all float32 row-major, leading dims padded to 64 elements = 256 B):
 """
 
 import ctypes
-import functools
 import os
 
 import torch
 
 from . import _lib
+from . import engine_core as core
+from .engine_core import EngineBase, _Bufs, _ceil64, with_precision
 
 
-def _ceil64(n):
-    return (n + 63) // 64 * 64
-
-
-class _Bufs:
-    pass
-
-
-_GEMM_MODES = {"f32": 0, "bf16": 1, "f32x3": 2}  # include/gdmcf_hip.h GDMCF_GEMM_F32 / _BF16 / _F32X3
-
-
-def _with_precision(fn):
-    """Runs an engine entry point with the library's per-thread GEMM input precision set to this engine's."""
-    @functools.wraps(fn)
-    def wrapped(self, *a, **kw):
-        prev = self.lib.gdmcf_gemm_precision(_GEMM_MODES[self.gemm_dtype])
-        try:
-            return fn(self, *a, **kw)
-        finally:
-            self.lib.gdmcf_gemm_precision(prev)
-    return wrapped
-
-
-class DenoiserEngine:
-    supports_grad_sink = True  # parallel.DataParallelStep may install `grad_sink` (overlapped gradient exchange)
-
+class DenoiserEngine(EngineBase):
     def __init__(self, model):
-        self.model = model
-        self.lib = _lib.load()
-        self.E = int(model.time_emb_dim)
-        self.I = int(model.in_dims[0])
-        self.version = 0
-        self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self.offset = 0
-        self._bufs = {}
+        super().__init__(model)
         self._wshadow = {}
-        self._saved = None
-        # data parallel: called as grad_sink(param, grad) the moment a gradient's kernels are enqueued, so the
-        # all-reduce of the big weight gradients overlaps the rest of the backward (gdmcf_amd/parallel.py).
-        # When set, the engine assigns .grad itself and hands autograd None for that parameter.
-        self.grad_sink = None
-        # single-GPU optimiser-in-backward (FusedAdamW.fuse_into_backward): big weights are updated inside the
-        # weight-gradient GEMM's epilogue; their gradient is never materialised.
-        self.fused_opt = None
         # compute a layer's input gradient before its weight gradient (needed when the weight may be updated as
         # soon as its gradient exists: fused optimiser, single-process early update in parallel.DataParallelStep)
         self.input_grad_first = False
@@ -83,12 +44,11 @@ class DenoiserEngine:
         # 1.692 -> 1.673 ms per Yelp-shape step, 4.276 -> 4.251 ms at the Amazon-Book shape, bit-identical results.  Off by
         # default: two GEMMs sharing the chip cannot be timed one by one (HIP events / rocprof show 0.44 + 0.35 ms for the
         # pair instead of 0.26 + 0.23), and the per-kernel roofline is what bench.py reports.
-        import os as _os
-        self._gemm_side = _os.environ.get("GDMCF_GEMM_SIDE", "0") == "1"
+        self._gemm_side = os.environ.get("GDMCF_GEMM_SIDE", "0") == "1"
         self._side2 = None
         self._side2_used = False
         self._wt = {}  # id(weight) -> (weight, version, transposed copy): the reverse loop's hidden layers (see _transposed)
-        self._wt_on = _os.environ.get("GDMCF_FWD_WT", "1") == "1"
+        self._wt_on = os.environ.get("GDMCF_FWD_WT", "1") == "1"
 
     def _grad_like(self, p):
         if not self.static_grads:
@@ -110,16 +70,6 @@ class DenoiserEngine:
     def flush_weight_waiters(self):
         while self.weight_waiters:
             self.weight_waiters.popitem()[1]()
-
-    @property
-    def gemm_dtype(self):
-        """"f32": exact-f32 MFMA products (parity path);  "bf16": operands rounded to bf16 on chip, f32 accumulate;
-        "f32x3": float32 products from six bf16 MFMAs of three-term operand splits (f32-level error, gemm_split.hip)."""
-        return getattr(self.model, "gemm_dtype", "f32")
-
-    def manual_seed(self, seed):
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.offset = 0
 
     # ------------------------------------------------------------------------------------------
     # bf16 shadows (gemm_dtype == "bf16"): bf16 copies of every GEMM operand, streamed instead of the f32 tensors.
@@ -163,11 +113,7 @@ class DenoiserEngine:
 
     def _layers(self):
         layers = self.model.layer_list()
-        for w, b, _ in layers:
-            _lib.require_gpu(w, "DNN parameters")
-            # (rows of a weight may be further apart than its columns: FusedAdamW.fuse_into_backward seats them on 128-byte lines)
-            if not (w.stride(1) == 1 and w.stride(0) >= w.shape[1] and b.is_contiguous() and w.dtype == torch.float32):
-                raise RuntimeError("gdmcf_amd: DNN parameters must be float32 with unit column stride")
+        self._check_params(layers)
         return layers
 
     def buffers(self, B, device):
@@ -175,115 +121,40 @@ class DenoiserEngine:
         b = self._bufs.get(key)
         if b is not None:
             return b
-        lib, I, E = self.lib, self.I, self.E
         layers = self.model.layer_list()
         f32 = dict(dtype=torch.float32, device=device)
         b = _Bufs()
-        b.ldk = _ceil64(I + E)
+        b.ldk = _ceil64(self.I + self.E)
         b.xin = torch.zeros(B, b.ldk, **f32)
         b.xin2 = None
-        b.temb = torch.zeros(B, max(E, 1), **f32)
-        b.rownorm = torch.zeros(B, **f32)
         b.acts = [torch.zeros(B, _ceil64(w.shape[0]), **f32) for (w, _, _) in layers[:-1]]
         b.dzs = [torch.zeros(B, _ceil64(w.shape[0]), **f32) for (w, _, _) in layers[:-1]]
         b.hs = torch.zeros(B, _ceil64(layers[-1][0].shape[1]), **f32)
-        b.ldi = _ceil64(I)
-        b.diff = torch.zeros(B, b.ldi, **f32)
-        b.xt = None
         b.shadows = None  # bf16 shadows of the GEMM operands among these buffers (created on first bf16 use)
-        b.rowpart = torch.zeros(B, lib.gdmcf_loss_tiles(layers[-1][0].shape[0]), **f32)
-        b.rowsum = torch.zeros(B, **f32)
-        b.gradcoef = torch.zeros(B, **f32)
-        b.rowdiv_mse = torch.full((B,), float(I), **f32)
-        b.lu = torch.zeros(B, dtype=torch.float64, device=device)
-        b.demb = torch.zeros((B + layers[0][0].shape[0]) * max(E, 1), **f32)  # demb [B,E] + gathered W1[:, I:] [n0,E]
-        ws = 0
-        for (w, _, _) in layers:
-            ws = max(ws, lib.gdmcf_linear_ws_bytes(B, w.shape[0], w.shape[1]))
-        b.ws_bytes = int(ws)
-        b.ws = torch.empty(max(ws, 256), dtype=torch.uint8, device=device)
+        self._shared_buffers(b, B, device, layers[-1][0].shape[0], layers[0][0].shape[0], [w for w, _, _ in layers])
         self._bufs[key] = b
         return b
 
     # ------------------------------------------------------------------------------------------
     def _prep(self, bufs, x, ts, ca, cb, noise, drop_mask, training, xt_out=None, xin=None):
-        m, lib = self.model, self.lib
-        B = x.shape[0]
-        if x.dtype != torch.float32 or x.stride(-1) != 1:
-            x = x.float().contiguous()
         xin = bufs.xin if xin is None else xin
-        noise_mode = 0
-        if ca is not None:
-            noise_mode = 1 if noise is not None else 2
-            if noise is not None and (noise.dtype != torch.float32 or noise.stride(-1) != 1):
-                noise = noise.float().contiguous()
-        p = float(m.drop.p)
-        drop_mode = 0
-        keep = None
-        if drop_mask is not None:
-            drop_mode = 1
-            keep = drop_mask if drop_mask.dtype == torch.uint8 else (drop_mask != 0).to(torch.uint8)
-            keep = keep.contiguous()
-        elif training and p > 0.0:
-            drop_mode = 2
-        self.offset += 1
-        rc = lib.gdmcf_dnn_prep_input_f32(
-            x.data_ptr(), x.stride(0), _lib.ptr(ts), _lib.ptr(ca), _lib.ptr(cb), noise_mode, _lib.ptr(noise),
-            noise.stride(0) if noise is not None else 0, drop_mode, _lib.ptr(keep),
-            keep.stride(0) if keep is not None else 0, p, self.seed, self.offset, int(bool(m.norm)),
-            m.emb_layer.weight.data_ptr(), m.emb_layer.bias.data_ptr(), self.E, B, self.I, xin.data_ptr(),
-            xin.stride(0), _lib.ptr(xt_out), xt_out.stride(0) if xt_out is not None else 0, bufs.temb.data_ptr(),
-            bufs.rownorm.data_ptr(), _lib.stream_ptr())
-        _lib.check(rc)
+        keepalive = self._prep_input(bufs, x, self.I, xin, ts, ca, cb, noise, drop_mask, training, xt_out=xt_out)
         if xin is bufs.xin:
             bufs.xin_ones = True  # (the builder leaves 1 in column I + E: the bias column of the first layer's weight gradient)
-        return x, noise, keep  # keep the (possibly converted) inputs alive until the stream has consumed them
+        return keepalive
 
     def _prep_csr(self, bufs, batch, ts, ca, cb, noise, drop_mask, training):
         """First-layer input straight from the device CSR rows of `batch` (data_utils.CsrBatch): no dense x0 anywhere; the
         rows' bitmaps go to bufs.x0bits for the loss epilogue."""
-        m, lib = self.model, self.lib
+        m = self.model
         B, I = batch.shape
         if getattr(bufs, "x0bits", None) is None:
             bufs.x0bits = torch.zeros(B, (I + 31) // 32, dtype=torch.int32, device=batch.device)
-        noise_mode = 0
-        if ca is not None:
-            noise_mode = 1 if noise is not None else 2
-            if noise is not None and (noise.dtype != torch.float32 or noise.stride(-1) != 1):
-                noise = noise.float().contiguous()
-        p = float(m.drop.p)
-        drop_mode, keep = 0, None
-        if drop_mask is not None:
-            drop_mode = 1
-            keep = (drop_mask if drop_mask.dtype == torch.uint8 else (drop_mask != 0).to(torch.uint8)).contiguous()
-        elif training and p > 0.0:
-            drop_mode = 2
         self.offset += 1
-        c = batch.csr
-        _lib.check(lib.gdmcf_dnn_prep_input_csr_f32(
-            c.indptr.data_ptr(), c.indices.data_ptr(), batch.row_ids.data_ptr(), _lib.ptr(ts), _lib.ptr(ca), _lib.ptr(cb),
-            noise_mode, _lib.ptr(noise), noise.stride(0) if noise is not None else 0, drop_mode, _lib.ptr(keep),
-            keep.stride(0) if keep is not None else 0, p, self.seed, self.offset, m.emb_layer.weight.data_ptr(),
-            m.emb_layer.bias.data_ptr(), self.E, B, I, bufs.xin.data_ptr(), bufs.xin.stride(0), bufs.temb.data_ptr(),
-            bufs.x0bits.data_ptr(), bufs.x0bits.stride(0), _lib.stream_ptr()))
+        keepalive = core.prep_input_csr(self.lib, batch, ts, ca, cb, noise, drop_mask, float(m.drop.p), training, self.seed,
+                                        self.offset, m.emb_layer, self.E, bufs.xin, bufs.temb, bufs.x0bits, _lib.stream_ptr())
         bufs.xin_ones = True
-        return batch, noise, keep
-
-    def _eps_target(self, bufs, spec, ts, x0, noise):
-        """(target, alpha, rowdiv) of the eps parameterisation in one launch (gdmcf_eps_target_f32; reference
-        gaussian_diffusion.py:344-348).  A noise tensor this package drew itself (spec["noise_owned"]) IS the target: only its
-        t == 0 rows are rewritten; a caller's tensor is left alone."""
-        B, dev = ts.shape[0], ts.device
-        if x0.dtype != torch.float32 or x0.stride(-1) != 1:
-            x0 = x0.float().contiguous()
-        target = noise if spec.get("noise_owned", False) else torch.empty(B, self.I, dtype=torch.float32, device=dev)
-        alpha = torch.empty(B, dtype=torch.float32, device=dev)
-        rowdiv = torch.empty(B, dtype=torch.float32, device=dev)
-        _lib.check(self.lib.gdmcf_eps_target_f32(
-            noise.data_ptr(), noise.stride(0), bufs.xt.data_ptr(), bufs.xt.stride(0), x0.data_ptr(), x0.stride(0), ts.data_ptr(),
-            spec["r1_0"].data_ptr(), spec["r2_0"].data_ptr(), int(bool(spec.get("t0_likelihood", True))), B, self.I,
-            target.data_ptr(), target.stride(0), alpha.data_ptr(), rowdiv.data_ptr(), _lib.stream_ptr()))
-        return target, alpha, rowdiv
+        return keepalive
 
     def _transposed(self, w):
         """W^T of a large weight, [in, out] row-major on 128-byte rows, cached per weight VERSION: the reverse-diffusion loop of an
@@ -299,29 +170,27 @@ class DenoiserEngine:
         return rec[2]
 
     def _hidden_forward(self, bufs, layers, B, xin=None, frozen=False):
-        """All layers but the last; returns (A, lda, K) feeding the last layer.  frozen: the caller runs many forward passes over
+        """All layers but the last; returns the activation feeding the last layer.  frozen: the caller runs many forward passes over
         unchanged weights (reverse loop): large layers go through their cached transposes."""
         lib, st = self.lib, _lib.stream_ptr()
-        A, lda = (bufs.xin if xin is None else xin), bufs.ldk
+        A = bufs.xin if xin is None else xin
         for li, (w, bias, act) in enumerate(layers[:-1]):
             N, K = w.shape
             out = bufs.acts[li]
             self._use_weight(w)
             if frozen and self._wt_on and self.gemm_dtype == "f32" and K >= 4096 and w.numel() >= (1 << 20):
                 wt = self._transposed(w)
-                _lib.check(lib.gdmcf_linear_fwd_wt_f32(A.data_ptr(), lda, wt.data_ptr(), wt.stride(0), bias.data_ptr(), act, B, N, K,
+                _lib.check(lib.gdmcf_linear_fwd_wt_f32(A.data_ptr(), A.stride(0), wt.data_ptr(), wt.stride(0), bias.data_ptr(), act, B, N, K,
                                                        out.data_ptr(), out.stride(0), bufs.ws.data_ptr(), bufs.ws_bytes, st))
             else:
-                _lib.check(lib.gdmcf_linear_fwd_f32(A.data_ptr(), lda, w.data_ptr(), w.stride(0), bias.data_ptr(), act, B,
-                                                    N, K, out.data_ptr(), out.stride(0), bufs.ws.data_ptr(),
-                                                    bufs.ws_bytes, st))
-            A, lda = out, out.stride(0)
-        return A, lda
+                core.linear_fwd(lib, bufs, A, w, bias, act, B, N, K, out, st)
+            A = out
+        return A
 
     # ------------------------------------------------------------------------------------------
     # fused training forward / backward
     # ------------------------------------------------------------------------------------------
-    @_with_precision
+    @with_precision
     def train_forward(self, spec):
         x0, ts = spec["x_start"], spec["ts"]
         csr = spec.get("csr")
@@ -351,37 +220,24 @@ class DenoiserEngine:
         else:
             target = x0c
             rowdiv = bufs.rowdiv_mse
-        A, lda = self._hidden_forward(bufs, layers, B)
+        A = self._hidden_forward(bufs, layers, B)
         w, bias, _ = layers[-1]
         N, K = w.shape
         self._use_weight(w)
         if csr is not None:  # the target rows are bitmaps written by the CSR-fed input builder
-            _lib.check(lib.gdmcf_linear_loss_fwd_bits_f32(A.data_ptr(), lda, w.data_ptr(), w.stride(0), bias.data_ptr(),
+            _lib.check(lib.gdmcf_linear_loss_fwd_bits_f32(A.data_ptr(), A.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr(),
                                                           bufs.x0bits.data_ptr(), bufs.x0bits.stride(0), None, B, N, K, None,
                                                           0, bufs.diff.data_ptr(), bufs.ldi, bufs.rowpart.data_ptr(),
                                                           bufs.rowsum.data_ptr(), st))
         else:
-            _lib.check(lib.gdmcf_linear_loss_fwd_f32(A.data_ptr(), lda, w.data_ptr(), w.stride(0), bias.data_ptr(),
-                                                     target.data_ptr(), target.stride(0), _lib.ptr(alpha), B, N, K, None,
-                                                     0, bufs.diff.data_ptr(), bufs.ldi, bufs.rowpart.data_ptr(),
-                                                     bufs.rowsum.data_ptr(), st))
-        loss = torch.empty(B, dtype=torch.float64, device=dev)
-        pt = spec["pt"]
+            core.loss_layer(lib, bufs, A, w, bias, target, alpha, B, N, K, st)
         # the tail also emits mean(loss) and gradcoef/B: the reference's step takes the mean next (main.py:348), and its
         # backward scales every row by 1/B -- two launches less per step (DataParallelStep uses both)
-        self.last_loss_mean = torch.empty((), dtype=torch.float64, device=dev)
-        if getattr(bufs, "rowscale_mean", None) is None:
-            bufs.rowscale_mean = torch.zeros(B, dtype=torch.float32, device=dev)
-        _lib.check(lib.gdmcf_row_loss_finish_mean_f64(bufs.rowsum.data_ptr(), rowdiv.data_ptr(), _lib.ptr(alpha),
-                                                      ts.data_ptr(), spec["weight_t"].data_ptr(), pt.data_ptr(), B,
-                                                      spec["T"], spec["H"], spec["Lt_history"].data_ptr(),
-                                                      spec["Lt_count"].data_ptr(), int(spec["update_history"]),
-                                                      bufs.lu.data_ptr(), loss.data_ptr(), bufs.gradcoef.data_ptr(),
-                                                      self.last_loss_mean.data_ptr(), bufs.rowscale_mean.data_ptr(), st))
-        self._saved = dict(kind="train", B=B, bufs=bufs, layers=layers, keepalive=(keepalive, target, alpha, rowdiv, pt))
+        loss, self.last_loss_mean = core.loss_tail(lib, bufs, spec, B, rowdiv, alpha, st, mean=True)
+        self._saved = dict(kind="train", B=B, bufs=bufs, layers=layers, keepalive=(keepalive, target, alpha, rowdiv, spec["pt"]))
         return loss
 
-    @_with_precision
+    @with_precision
     def train_backward(self, gloss):
         """gloss: d(total)/d(loss_b) as a tensor [B] (what autograd hands over), or a Python float when every row has
         the same upstream gradient (mean reduction: 1/B) -- then no autograd graph is needed at all."""
@@ -391,16 +247,14 @@ class DenoiserEngine:
         bufs = sv["bufs"]
         if isinstance(gloss, float) and gloss == 1.0 / sv["B"] and getattr(bufs, "rowscale_mean", None) is not None:
             rowscale = bufs.rowscale_mean  # gradcoef * (float)(1/B), written by the loss tail: same bits as the product below
-        elif isinstance(gloss, float):
-            rowscale = bufs.gradcoef * gloss
         else:
-            rowscale = (gloss.to(torch.float32) * bufs.gradcoef).contiguous()
-        return self._backward(sv, bufs.diff, bufs.ldi, rowscale)
+            rowscale = self._rowscale_of(bufs, gloss)
+        return self._backward(sv, bufs.diff, rowscale)
 
     # ------------------------------------------------------------------------------------------
     # plain forward / backward (model(x, t))
     # ------------------------------------------------------------------------------------------
-    @_with_precision
+    @with_precision
     def forward_plain(self, x, timesteps, training, drop_mask=None):
         self.flush_weight_waiters()
         B, dev = x.shape[0], x.device
@@ -411,25 +265,24 @@ class DenoiserEngine:
         self.version += 1
         ts = timesteps.to(device=dev, dtype=torch.int64).contiguous()
         keepalive = self._prep(bufs, x, ts, None, None, None, drop_mask, training)
-        A, lda = self._hidden_forward(bufs, layers, B)
+        A = self._hidden_forward(bufs, layers, B)
         w, bias, act = layers[-1]
         N, K = w.shape
         out = torch.empty(B, N, dtype=torch.float32, device=dev)
-        _lib.check(lib.gdmcf_linear_fwd_f32(A.data_ptr(), lda, w.data_ptr(), w.stride(0), bias.data_ptr(), act, B, N,
-                                            K, out.data_ptr(), out.stride(0), bufs.ws.data_ptr(), bufs.ws_bytes, st))
+        core.linear_fwd(lib, bufs, A, w, bias, act, B, N, K, out, st)
         self._saved = dict(kind="plain", B=B, bufs=bufs, layers=layers, keepalive=(keepalive, ts))
         return out
 
-    @_with_precision
+    @with_precision
     def backward_plain(self, gout):
         sv = self._saved
         g = gout.to(torch.float32)
         if g.stride(-1) != 1:
             g = g.contiguous()
-        return self._backward(sv, g, g.stride(0), None)
+        return self._backward(sv, g, None)
 
     # ------------------------------------------------------------------------------------------
-    def _backward(self, sv, dz_last, ld_last, rowscale):
+    def _backward(self, sv, dz_last, rowscale):
         """Gradients in model.parameters() order: emb_layer (w, b), in_layers..., out_layers...
         dz_last is d(loss)/d(last layer output) up to the per-row factor `rowscale`.
 
@@ -444,74 +297,42 @@ class DenoiserEngine:
         grads_b = [None] * L
         dWe = dbe = None
         fused = self.fused_opt if self.grad_sink is None else None
-        dz, lddz, rs = dz_last, ld_last, rowscale
+        dz, rs = dz_last, rowscale
         # f32 products of fused weights: queued and issued as ONE launch after every input gradient (one ramp, one optimiser-stream
         # drain and one ragged last round of tiles per step instead of one per weight).  Their operands -- the per-layer dzs, the
         # row-scaled copy bufs.hs (written for the last layer only) and the activations -- are not written again before that.
         # GDMCF_DW_MULTI=0: one launch per weight, where its layer's backward issues it.
         dw_queue = [] if (fused is not None and self.gemm_dtype == "f32" and os.environ.get("GDMCF_DW_MULTI", "1") != "0") else None
 
-        def input_grad(li, w, A_prev, lda_prev, N, K):
+        def input_grad(li, w, A_prev):
             nonlocal dWe, dbe
+            N, K = w.shape
             if li > 0:
                 dprev = bufs.dzs[li - 1]
-                act_prev = layers[li - 1][2]
-                _lib.check(lib.gdmcf_linear_bwd_input_f32(dz.data_ptr(), lddz, w.data_ptr(), w.stride(0), _lib.ptr(rs),
-                                                          A_prev.data_ptr(), lda_prev, act_prev, B, N, K,
-                                                          dprev.data_ptr(), dprev.stride(0), bufs.ws.data_ptr(),
-                                                          bufs.ws_bytes, st))
-                return dprev, dprev.stride(0), None
+                self._input_grad(bufs, B, w, N, K, dz, rs, A_prev, layers[li - 1][2], dprev, st)
+                return dprev
             dWe = self._grad_like(m.emb_layer.weight)
             dbe = self._grad_like(m.emb_layer.bias)
-            _lib.check(lib.gdmcf_emb_bwd_f32(dz.data_ptr(), lddz, w.data_ptr(), w.stride(0), self.I, self.E,
-                                             bufs.temb.data_ptr(), B, w.shape[0], bufs.demb.data_ptr(), dWe.data_ptr(),
-                                             dbe.data_ptr(), st))
-            return None, 0, None
+            core.emb_bwd(lib, bufs, dz, w, self.I, self.E, B, N, dWe, dbe, st)
+            return None
 
-        def weight_grad(li, w, bias, A_prev, lda_prev, N, K):
+        def weight_grad(li, w, bias, A_prev):
             db = self._grad_like(bias)
-            A_use, lda_use = A_prev, lda_prev
-            # 1: column K of A_use holds the row scale (written by gdmcf_rowscale_f32 below: the copy has room for it) -- or, for
-            # the first layer without a row scale, the 1 the input builder leaves in xin's first padding column
-            scol = int(rs is None and li == 0 and getattr(bufs, "xin_ones", False) and lda_use > K)
-            if rs is not None:
-                # (rs . dZ)^T A == dZ^T (rs . A): scale the small activation instead of the big dZ
-                _lib.check(lib.gdmcf_rowscale_f32(A_prev.data_ptr(), lda_prev, rs.data_ptr(), B, K, bufs.hs.data_ptr(),
-                                                  bufs.hs.stride(0), st))
-                A_use, lda_use = bufs.hs, bufs.hs.stride(0)
-                scol = int(lda_use > K)
+            # without a row scale, the first layer's input already holds 1 in its first padding column (the input builder's)
+            scol = int(rs is None and li == 0 and getattr(bufs, "xin_ones", False) and A_prev.stride(0) > w.shape[1])
+            A_use, scol = self._row_scaled(bufs, B, w.shape[1], A_prev, rs, scol, st)
             fs = fused.fused_state(w) if fused is not None else None
-            if fs is not None:
-                if fs["exp_avg"].stride() != w.stride() or fs["exp_avg_sq"].stride() != w.stride():
-                    raise RuntimeError("gdmcf_amd: the moments of a fused weight must share its leading dimension")
-                if dw_queue is not None:
-                    dw_queue.append((_lib.GdDwAdamw(
-                        dz.data_ptr(), lddz, A_use.data_ptr(), lda_use, _lib.ptr(rs), scol, B, N, K, w.data_ptr(), w.stride(0),
-                        fs["exp_avg"].data_ptr(), fs["exp_avg_sq"].data_ptr(), db.data_ptr(), fs["lr"], fs["beta1"],
-                        fs["beta2"], fs["eps"], fs["weight_decay"], fs["step"], fs["grad_scale"]), w))
-                else:
-                    _lib.check(lib.gdmcf_linear_bwd_weight_adamw_f32(
-                        dz.data_ptr(), lddz, A_use.data_ptr(), lda_use, _lib.ptr(rs), scol, B, N, K, w.data_ptr(), w.stride(0),
-                        fs["exp_avg"].data_ptr(), fs["exp_avg_sq"].data_ptr(), db.data_ptr(), fs["lr"], fs["beta1"],
-                        fs["beta2"], fs["eps"], fs["weight_decay"], fs["step"], fs["grad_scale"], st))
-                    if not (self.gemm_dtype == "bf16" and _lib.shadow_info(w.data_ptr()) is not None):
-                        torch.autograd.graph.increment_version(w)  # updated in the GEMM epilogue (bf16: shadow too)
-                dW = None
+            dW = self._grad_like(w) if fs is None else None
+            if fs is None and self._gemm_side and self.grad_sink is None and li == L - 1 and L > 1:
+                # the last layer's weight-gradient GEMM on a second stream, beside the input-gradient GEMM
+                if self._side2 is None:
+                    self._side2 = torch.cuda.Stream()
+                self._side2.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(self._side2):
+                    self._weight_grad(bufs, B, w, dz, rs, A_use, scol, dW, db, None, _lib.stream_ptr())
+                self._side2_used = True
             else:
-                dW = self._grad_like(w)
-                if self._gemm_side and self.grad_sink is None and li == L - 1 and L > 1:
-                    # the last layer's weight-gradient GEMM on a second stream, beside the input-gradient GEMM
-                    if self._side2 is None:
-                        self._side2 = torch.cuda.Stream()
-                    self._side2.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(self._side2):
-                        _lib.check(lib.gdmcf_linear_bwd_weight_f32(dz.data_ptr(), lddz, A_use.data_ptr(), lda_use, _lib.ptr(rs),
-                                                                   scol, B, N, K, dW.data_ptr(), dW.stride(0), db.data_ptr(), 0,
-                                                                   _lib.stream_ptr()))
-                    self._side2_used = True
-                else:
-                    _lib.check(lib.gdmcf_linear_bwd_weight_f32(dz.data_ptr(), lddz, A_use.data_ptr(), lda_use, _lib.ptr(rs),
-                                                               scol, B, N, K, dW.data_ptr(), dW.stride(0), db.data_ptr(), 0, st))
+                self._weight_grad(bufs, B, w, dz, rs, A_use, scol, dW, db, fs, st, queue=dw_queue)
             grads_w[li], grads_b[li] = dW, db
             if self.grad_sink is not None:
                 self.grad_sink(w, dW)
@@ -520,18 +341,14 @@ class DenoiserEngine:
 
         for li in range(L - 1, -1, -1):
             w, bias, _ = layers[li]
-            N, K = w.shape
-            if li > 0:
-                A_prev, lda_prev = bufs.acts[li - 1], bufs.acts[li - 1].stride(0)
-            else:
-                A_prev, lda_prev = bufs.xin, bufs.ldk
+            A_prev = bufs.acts[li - 1] if li > 0 else bufs.xin
             if fused is not None or self.input_grad_first:
-                nxt = input_grad(li, w, A_prev, lda_prev, N, K)
-                weight_grad(li, w, bias, A_prev, lda_prev, N, K)
+                nxt = input_grad(li, w, A_prev)
+                weight_grad(li, w, bias, A_prev)
             else:
-                weight_grad(li, w, bias, A_prev, lda_prev, N, K)
-                nxt = input_grad(li, w, A_prev, lda_prev, N, K)
-            dz, lddz, rs = nxt
+                weight_grad(li, w, bias, A_prev)
+                nxt = input_grad(li, w, A_prev)
+            dz, rs = nxt, None
         if dw_queue:
             arr = (_lib.GdDwAdamw * len(dw_queue))(*[e for e, _ in dw_queue])
             _lib.check(lib.gdmcf_linear_bwd_weight_adamw_multi_f32(ctypes.addressof(arr), len(dw_queue), st))
@@ -552,7 +369,7 @@ class DenoiserEngine:
     # ------------------------------------------------------------------------------------------
     # reverse diffusion loop (reference gaussian_diffusion.py:161-220)
     # ------------------------------------------------------------------------------------------
-    @_with_precision
+    @with_precision
     def p_sample_loop(self, x_start, steps, T, tabs32, eps_mode, sampling_noise, noise0=None, step_noise=None,
                       capture=None, draw_noise=None):
         """tabs32: dict of float32 device tables [T] (sqrt_ab, sqrt_1mab, c1, c2, r1, r2, sigma).  draw_noise(like) -> [B, I]
@@ -595,7 +412,7 @@ class DenoiserEngine:
             bufs.step_tabs_key = key
         stabs, step_ts = bufs.step_tabs, bufs.step_ts
 
-        def posterior(i, n, A, lda, xt, xn):
+        def posterior(i, n, A, xt, xn):
             c1, c2 = stabs["c1"][i], stabs["c2"][i]
             r1 = r2 = sg = z = None
             if eps_mode:
@@ -605,11 +422,7 @@ class DenoiserEngine:
                 z = step_noise[n] if step_noise is not None else draw_noise(xt[:, :I])
                 z = z.contiguous()
             pred = torch.empty(B, I, dtype=torch.float32, device=dev) if capture is not None else None
-            _lib.check(lib.gdmcf_linear_posterior_fwd_f32(
-                A.data_ptr(), lda, w.data_ptr(), w.stride(0), bias.data_ptr(), xt.data_ptr(), xt.stride(0),
-                c1.data_ptr(), c2.data_ptr(), _lib.ptr(r1), _lib.ptr(r2), _lib.ptr(sg), _lib.ptr(z),
-                z.stride(0) if z is not None else 0, B, N, K, xn.data_ptr(), xn.stride(0), _lib.ptr(pred),
-                pred.stride(0) if pred is not None else 0, st))
+            core.posterior_fwd(lib, A, w, bias, xt, c1, c2, r1, r2, sg, z, B, N, K, xn, pred, st)
             keep.append((c1, c2, r1, r2, sg, z))
             if capture is not None:
                 capture.setdefault("pred_xstart", []).append(pred)
@@ -628,9 +441,9 @@ class DenoiserEngine:
                                                       m.emb_layer.bias.data_ptr(), self.E, B, I, cur.data_ptr(),
                                                       cur.stride(0), bufs.temb.data_ptr(), st))
                 keep.append(ts)
-                A, lda = self._hidden_forward(bufs, layers, B, xin=cur, frozen=True)
+                A = self._hidden_forward(bufs, layers, B, xin=cur, frozen=True)
                 out = torch.empty(B, I, dtype=torch.float32, device=dev) if i == 0 else None
-                posterior(i, n, A, lda, cur, out if out is not None else nxt)
+                posterior(i, n, A, cur, out if out is not None else nxt)
                 cur, nxt = nxt, cur
         else:
             # F.normalize needs the row norms of every x_t: keep x_t separate and rebuild the layer input per step
@@ -641,10 +454,10 @@ class DenoiserEngine:
             for n, i in enumerate(range(T - 1, -1, -1)):
                 ts = step_ts[i]
                 keep.append(self._prep(bufs, xt[:, :I], ts, None, None, None, None, False, xin=bufs.xin))
-                A, lda = self._hidden_forward(bufs, layers, B, xin=bufs.xin, frozen=True)
+                A = self._hidden_forward(bufs, layers, B, xin=bufs.xin, frozen=True)
                 out = torch.empty(B, I, dtype=torch.float32, device=dev) if i == 0 else None
                 xn = out if out is not None else (bufs.diff if xt is bufs.xt else bufs.xt)
-                posterior(i, n, A, lda, xt, xn)
+                posterior(i, n, A, xt, xn)
                 xt = xn
         self._saved = None
         del keep

@@ -1,0 +1,354 @@
+"""What the four denoiser engines share (engine.DenoiserEngine for DNN; onehot.OneHotEngine and its two subclasses):
+  * one call helper per C entry point of include/gdmcf_hip.h that more than one engine uses.  A 2-D operand is a tensor, or
+    the pair (pointer, leading dimension) where the caller addresses a column range of a buffer; `st` is the stream.
+  * `EngineBase`: Philox position, buffer cache, the buffers every backbone has, parameter layout check, the fused
+    optimiser's state, the input builder with its Philox step, the weight-gradient step (row scale, product) and the input gradient
+    of one layer.
+  * `TrainLoss`: the autograd function of the fused training loss.
+PyTorch is used for device memory and streams only; every arithmetic step is a HIP kernel.
+"""
+import functools
+
+import torch
+
+from . import _lib
+
+
+def _ceil64(n):
+    return (int(n) + 63) // 64 * 64
+
+
+class _Bufs:
+    pass
+
+
+_GEMM_MODES = {"f32": 0, "bf16": 1, "f32x3": 2}  # include/gdmcf_hip.h GDMCF_GEMM_F32 / _BF16 / _F32X3
+
+
+def with_precision(fn):
+    """Runs an engine entry point with the library's per-thread GEMM input precision set to this engine's."""
+    @functools.wraps(fn)
+    def wrapped(self, *a, **kw):
+        prev = self.lib.gdmcf_gemm_precision(_GEMM_MODES[self.gemm_dtype])
+        try:
+            return fn(self, *a, **kw)
+        finally:
+            self.lib.gdmcf_gemm_precision(prev)
+    return wrapped
+
+
+def _pl(a):
+    """(pointer, leading dimension) of a 2-D operand; (None, 0) for an absent one."""
+    if type(a) is tuple:
+        return a
+    return (None, 0) if a is None else (a.data_ptr(), a.stride(0))
+
+
+def _f32_rows(t):
+    """`t` as float32 with unit column stride (itself when it already is)."""
+    return t if t.dtype == torch.float32 and t.stride(-1) == 1 else t.float().contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# input builder
+# ------------------------------------------------------------------------------------------------------------------
+def _prep_modes(B, ca, noise, drop_mask, drop_p, training):
+    """(noise_mode, noise, drop_mode, keep): 0 none / 1 given tensor / 2 in-kernel Philox draw, with the given tensors in
+    the layout the builders read (float32 noise, uint8 mask)."""
+    noise_mode = 0
+    if ca is not None:
+        noise_mode = 1 if noise is not None else 2
+        if noise is not None:
+            noise = _f32_rows(noise)
+    drop_mode, keep = 0, None
+    if drop_mask is not None:
+        drop_mode = 1
+        keep = drop_mask.reshape(B, -1)
+        keep = (keep if keep.dtype == torch.uint8 else (keep != 0).to(torch.uint8)).contiguous()
+    elif training and drop_p > 0.0:
+        drop_mode = 2
+    return noise_mode, noise, drop_mode, keep
+
+
+def prep_input(lib, x, I, ts, ca, cb, noise, drop_mask, drop_p, training, seed, offset, norm, emb, E, xin, xt_out, temb,
+               rownorm, st):
+    """gdmcf_dnn_prep_input_f32 on a [B, I] operand: xin = [ drop(normalize(q_sample(x))) | emb(t) | 1 | 0-pad ].  `emb`: the
+    timestep-embedding layer (None with E == 0: no embedding columns).  Returns (x, noise, keep) as the kernel reads them:
+    the caller keeps them referenced until the stream has consumed them."""
+    B = x.shape[0]
+    x = _f32_rows(x)
+    noise_mode, noise, drop_mode, keep = _prep_modes(B, ca, noise, drop_mask, drop_p, training)
+    (nz, ldn), (kp, ldkp), (xi, ldx), (xo, ldxo) = _pl(noise), _pl(keep), _pl(xin), _pl(xt_out)
+    _lib.check(lib.gdmcf_dnn_prep_input_f32(
+        x.data_ptr(), x.stride(0), _lib.ptr(ts), _lib.ptr(ca), _lib.ptr(cb), noise_mode, nz, ldn, drop_mode, kp, ldkp, drop_p,
+        seed, offset, int(bool(norm)), emb.weight.data_ptr() if emb is not None else None,
+        emb.bias.data_ptr() if emb is not None else None, E, B, I, xi, ldx, xo, ldxo, _lib.ptr(temb), _lib.ptr(rownorm), st))
+    return x, noise, keep
+
+
+def prep_input_csr(lib, batch, ts, ca, cb, noise, drop_mask, drop_p, training, seed, offset, emb, E, xin, temb, x0bits, st):
+    """gdmcf_dnn_prep_input_csr_f32: the same first-layer input straight from the device CSR rows of `batch`
+    (data_utils.CsrBatch), whose bitmaps go to `x0bits`.  Returns (batch, noise, keep) to keep referenced."""
+    B, I = batch.shape
+    noise_mode, noise, drop_mode, keep = _prep_modes(B, ca, noise, drop_mask, drop_p, training)
+    (nz, ldn), (kp, ldkp) = _pl(noise), _pl(keep)
+    c = batch.csr
+    _lib.check(lib.gdmcf_dnn_prep_input_csr_f32(
+        c.indptr.data_ptr(), c.indices.data_ptr(), batch.row_ids.data_ptr(), _lib.ptr(ts), _lib.ptr(ca), _lib.ptr(cb),
+        noise_mode, nz, ldn, drop_mode, kp, ldkp, drop_p, seed, offset, emb.weight.data_ptr(), emb.bias.data_ptr(), E, B, I,
+        xin.data_ptr(), xin.stride(0), temb.data_ptr(), x0bits.data_ptr(), x0bits.stride(0), st))
+    return batch, noise, keep
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# dense layers.  W is [N, K] row-major (rows at least K apart), `bufs` lends the split-K workspace.
+# ------------------------------------------------------------------------------------------------------------------
+def linear_fwd(lib, bufs, A, W, bias, act, B, N, K, out, st):
+    """out = act(A @ W^T + bias)"""
+    (a, lda), (w, ldw), (o, ldo) = _pl(A), _pl(W), _pl(out)
+    _lib.check(lib.gdmcf_linear_fwd_f32(a, lda, w, ldw, _lib.ptr(bias), act, B, N, K, o, ldo, bufs.ws.data_ptr(),
+                                        bufs.ws_bytes, st))
+
+
+def linear_bwd_input(lib, bufs, dz, W, rs, A_prev, act_prev, B, N, K, d_prev, st):
+    """d_prev = ((rs .) dz @ W) * act_prev'(A_prev)"""
+    (z, ldz), (w, ldw), (a, lda), (d, ldd) = _pl(dz), _pl(W), _pl(A_prev), _pl(d_prev)
+    _lib.check(lib.gdmcf_linear_bwd_input_f32(z, ldz, w, ldw, _lib.ptr(rs), a, lda, act_prev, B, N, K, d, ldd,
+                                              bufs.ws.data_ptr(), bufs.ws_bytes, st))
+
+
+def linear_bwd_weight(lib, dz, A, rs, scol, B, N, K, dW, db, st):
+    """dW = dz^T A, db = column sums of dz (out of the product when column K of A holds the row scale: `scol`)"""
+    (z, ldz), (a, lda) = _pl(dz), _pl(A)
+    _lib.check(lib.gdmcf_linear_bwd_weight_f32(z, ldz, a, lda, _lib.ptr(rs), scol, B, N, K, dW.data_ptr(), dW.stride(0),
+                                               _lib.ptr(db), 0, st))
+
+
+def adamw_args(fs, w):
+    """FusedAdamW.fused_state(w) as the argument run (exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
+    grad_scale) that every kernel with an AdamW epilogue takes."""
+    if fs["exp_avg"].stride() != w.stride() or fs["exp_avg_sq"].stride() != w.stride():
+        raise RuntimeError("gdmcf_amd: the moments of a fused weight must share its leading dimension")
+    return (fs["exp_avg"].data_ptr(), fs["exp_avg_sq"].data_ptr(), fs["lr"], fs["beta1"], fs["beta2"], fs["eps"],
+            fs["weight_decay"], fs["step"], fs["grad_scale"])
+
+
+def dw_adamw_args(dz, A, rs, scol, B, N, K, w, db, fs):
+    """Arguments of one fused weight-gradient + AdamW product (w and its moments updated in the epilogue, dW never
+    stored): those of gdmcf_linear_bwd_weight_adamw_f32 up to the stream, and the fields of a _lib.GdDwAdamw entry."""
+    (z, ldz), (a, lda) = _pl(dz), _pl(A)
+    ad = adamw_args(fs, w)
+    return (z, ldz, a, lda, _lib.ptr(rs), scol, B, N, K, w.data_ptr(), w.stride(0), ad[0], ad[1], _lib.ptr(db)) + ad[2:]
+
+
+def linear_bwd_weight_adamw(lib, args, st):
+    _lib.check(lib.gdmcf_linear_bwd_weight_adamw_f32(*args, st))
+
+
+def rowscale(lib, A, rs, B, K, out, st):
+    """out[:, :K] = rs . A[:, :K]; a wider `out` also receives rs itself in column K"""
+    (a, lda), (o, ldo) = _pl(A), _pl(out)
+    _lib.check(lib.gdmcf_rowscale_f32(a, lda, rs.data_ptr(), B, K, o, ldo, st))
+
+
+def emb_bwd(lib, bufs, dz, W, I_cols, E, B, N, dWe, dbe, st):
+    """Gradients of emb_layer from the E timestep-embedding columns (behind column I_cols) of a first layer W [N, .]"""
+    (z, ldz), (w, ldw) = _pl(dz), _pl(W)
+    _lib.check(lib.gdmcf_emb_bwd_f32(z, ldz, w, ldw, I_cols, E, bufs.temb.data_ptr(), B, N, bufs.demb.data_ptr(),
+                                     dWe.data_ptr(), dbe.data_ptr(), st))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# output layers
+# ------------------------------------------------------------------------------------------------------------------
+def loss_layer(lib, bufs, A, W, bias, target, alpha, B, N, K, st):
+    """Last product fused with the per-row loss: bufs.diff = alpha * (A @ W^T + bias) - target, its row sums of squares in
+    bufs.rowsum (the output itself is never stored)."""
+    (a, lda), (w, ldw) = _pl(A), _pl(W)
+    _lib.check(lib.gdmcf_linear_loss_fwd_f32(a, lda, w, ldw, _lib.ptr(bias), target.data_ptr(), target.stride(0),
+                                             _lib.ptr(alpha), B, N, K, None, 0, bufs.diff.data_ptr(), bufs.ldi,
+                                             bufs.rowpart.data_ptr(), bufs.rowsum.data_ptr(), st))
+
+
+def loss_tail(lib, bufs, spec, B, rowdiv, alpha, st, mean=False):
+    """The float64 loss tail (timestep weights, history FIFO, 1/pt) over bufs.rowsum: returns loss [B]; bufs.gradcoef
+    receives d(loss_b)/d(rowsum_b).  mean: the tail also emits mean(loss) and, into bufs.rowscale_mean (float32 [B], made on
+    first use), gradcoef / B; returns (loss, mean(loss))."""
+    ts = spec["ts"]
+    loss = torch.empty(B, dtype=torch.float64, device=ts.device)
+    args = (bufs.rowsum.data_ptr(), rowdiv.data_ptr(), _lib.ptr(alpha), ts.data_ptr(), spec["weight_t"].data_ptr(),
+            spec["pt"].data_ptr(), B, spec["T"], spec["H"], spec["Lt_history"].data_ptr(), spec["Lt_count"].data_ptr(),
+            int(spec["update_history"]), bufs.lu.data_ptr(), loss.data_ptr(), bufs.gradcoef.data_ptr())
+    if not mean:
+        _lib.check(lib.gdmcf_row_loss_finish_f64(*args, st))
+        return loss
+    loss_mean = torch.empty((), dtype=torch.float64, device=ts.device)
+    if getattr(bufs, "rowscale_mean", None) is None:
+        bufs.rowscale_mean = torch.zeros(B, dtype=torch.float32, device=ts.device)
+    _lib.check(lib.gdmcf_row_loss_finish_mean_f64(*args, loss_mean.data_ptr(), bufs.rowscale_mean.data_ptr(), st))
+    return loss, loss_mean
+
+
+def posterior_fwd(lib, A, W, bias, x_t, c1, c2, r1, r2, sigma, z, B, N, K, x_next, pred, st):
+    """Output layer with the posterior mean of one reverse step (reference gaussian_diffusion.py:451-471 / :495-498) in the
+    GEMM epilogue: x_next = c1 * x0_hat + c2 * x_t [+ sigma * z], x0_hat = the output (or r1 * x_t - r2 * output);
+    `pred` (optional) receives x0_hat.  The coefficients are per-row vectors [B]."""
+    (a, lda), (w, ldw), (zp, ldz), (pp, ldp) = _pl(A), _pl(W), _pl(z), _pl(pred)
+    _lib.check(lib.gdmcf_linear_posterior_fwd_f32(
+        a, lda, w, ldw, _lib.ptr(bias), x_t.data_ptr(), x_t.stride(0), c1.data_ptr(), c2.data_ptr(), _lib.ptr(r1),
+        _lib.ptr(r2), _lib.ptr(sigma), zp, ldz, B, N, K, x_next.data_ptr(), x_next.stride(0), pp, ldp, st))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+class TrainLoss(torch.autograd.Function):
+    """loss[B] (float64) of an engine's fused q_sample -> denoiser -> weighted row-MSE path."""
+
+    @staticmethod
+    def forward(ctx, eng, spec, *params):
+        loss = eng.train_forward(spec)
+        ctx.eng, ctx.version = eng, eng.version
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        eng = ctx.eng
+        if ctx.version != eng.version:
+            raise RuntimeError("gdmcf_amd: activations were overwritten by a later forward; "
+                               "call backward before the next training_losses/forward")
+        return (None, None, *eng.train_backward(gloss))
+
+
+class EngineBase:
+    supports_grad_sink = True  # parallel.DataParallelStep may install `grad_sink` (overlapped gradient exchange)
+
+    def __init__(self, model):
+        self.model = model
+        self.lib = _lib.load()
+        self.E = int(model.time_emb_dim)
+        self.I = int(model.in_dims[0])
+        self.version = 0
+        self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        self.offset = 0
+        self._bufs = {}
+        self._saved = None
+        # data parallel: called as grad_sink(param, grad) the moment a gradient's kernels are enqueued, so the
+        # all-reduce of the big weight gradients overlaps the rest of the backward (gdmcf_amd/parallel.py).
+        # When set, the engine assigns .grad itself and hands autograd None for that parameter.
+        self.grad_sink = None
+        # single-GPU optimiser-in-backward (FusedAdamW.fuse_into_backward): the weights it took over are updated inside the
+        # epilogue of the kernel that forms their gradient, which is never materialised (see _fused_state); ignored while a
+        # data-parallel grad_sink is installed
+        self.fused_opt = None
+
+    @property
+    def gemm_dtype(self):
+        """"f32": exact-f32 MFMA products (parity path);  "bf16": operands rounded to bf16 on chip, f32 accumulate;
+        "f32x3": float32 products from six bf16 MFMAs of three-term operand splits (f32-level error, gemm_split.hip)."""
+        return getattr(self.model, "gemm_dtype", "f32")
+
+    def manual_seed(self, seed):
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.offset = 0
+
+    def _check_params(self, layers):
+        """`layers`: (weight, bias, activation) of every dense layer, as the kernels read them."""
+        what = type(self.model).__name__ + " parameters"
+        for w, b, _ in layers:
+            _lib.require_gpu(w, what)
+            # (rows of a weight may lie further apart than its columns: FusedAdamW.fuse_into_backward seats them on 128-byte lines)
+            if not (w.stride(1) == 1 and w.stride(0) >= w.shape[1] and b.is_contiguous() and w.dtype == torch.float32):
+                raise RuntimeError(f"gdmcf_amd: {what} must be float32 with unit column stride")
+
+    def _shared_buffers(self, b, B, device, n_loss, n_first, weights):
+        """The buffers every backbone has: embedding columns, loss layer, loss tail, embedding backward, GEMM workspace.
+        n_loss: columns of the loss layer; n_first: most rows of a first-layer weight; weights: every [N, K] weight that
+        goes through the dense layers."""
+        lib, I, E = self.lib, self.I, self.E
+        f32 = dict(dtype=torch.float32, device=device)
+        b.temb = torch.zeros(B, max(E, 1), **f32)
+        b.rownorm = torch.zeros(B, **f32)
+        b.ldi = _ceil64(I)
+        b.diff = torch.zeros(B, b.ldi, **f32)
+        b.xt = None
+        b.rowpart = torch.zeros(B, lib.gdmcf_loss_tiles(n_loss), **f32)
+        b.rowsum = torch.zeros(B, **f32)
+        b.gradcoef = torch.zeros(B, **f32)
+        b.rowdiv_mse = torch.full((B,), float(I), **f32)
+        b.lu = torch.zeros(B, dtype=torch.float64, device=device)
+        b.demb = torch.zeros((B + n_first) * max(E, 1), **f32)  # demb [B,E] + gathered W1[:, I:] [n_first,E]
+        b.ws_bytes = 0
+        self._grow_workspace(b, B, device, [w.shape for w in weights])
+
+    def _grow_workspace(self, b, B, device, shapes):
+        ws = max([b.ws_bytes] + [self.lib.gdmcf_linear_ws_bytes(B, n, k) for n, k in shapes])
+        if ws > b.ws_bytes or getattr(b, "ws", None) is None:
+            b.ws_bytes = int(ws)
+            b.ws = torch.empty(max(ws, 256), dtype=torch.uint8, device=device)
+
+    # -- forward ------------------------------------------------------------------------------------------------------
+    def _prep_input(self, bufs, x, I, xin, ts, ca, cb, noise, drop_mask, training, xt_out=None):
+        """The input builder on a [B, I] operand at the next Philox position; returns (x, noise, keep) to keep referenced."""
+        m = self.model
+        self.offset += 1
+        return prep_input(self.lib, x, I, ts, ca, cb, noise, drop_mask, float(m.drop.p), training, self.seed, self.offset,
+                          m.norm, m.emb_layer, self.E, xin, xt_out, bufs.temb, bufs.rownorm, _lib.stream_ptr())
+
+    def _eps_target(self, bufs, spec, ts, x0, noise):
+        """(target, alpha, rowdiv) of the eps parameterisation in one launch (gdmcf_eps_target_f32; reference
+        gaussian_diffusion.py:344-348).  A noise tensor this package drew itself (spec["noise_owned"]) IS the target: only its
+        t == 0 rows are rewritten; a caller's tensor is left alone."""
+        B, dev = ts.shape[0], ts.device
+        x0 = _f32_rows(x0)
+        target = noise if spec.get("noise_owned", False) else torch.empty(B, self.I, dtype=torch.float32, device=dev)
+        alpha = torch.empty(B, dtype=torch.float32, device=dev)
+        rowdiv = torch.empty(B, dtype=torch.float32, device=dev)
+        _lib.check(self.lib.gdmcf_eps_target_f32(
+            noise.data_ptr(), noise.stride(0), bufs.xt.data_ptr(), bufs.xt.stride(0), x0.data_ptr(), x0.stride(0), ts.data_ptr(),
+            spec["r1_0"].data_ptr(), spec["r2_0"].data_ptr(), int(bool(spec.get("t0_likelihood", True))), B, self.I,
+            target.data_ptr(), target.stride(0), alpha.data_ptr(), rowdiv.data_ptr(), _lib.stream_ptr()))
+        return target, alpha, rowdiv
+
+    # -- backward -----------------------------------------------------------------------------------------------------
+    def _rowscale_of(self, bufs, gloss):
+        """Per-row factor of bufs.diff in the backward: d(total)/d(loss_b) * d(loss_b)/d(rowsum_b)."""
+        if isinstance(gloss, float):  # mean reduction: the same upstream gradient 1/B on every row
+            return bufs.gradcoef * gloss
+        return (gloss.to(torch.float32) * bufs.gradcoef).contiguous()
+
+    def _fused_state(self, w):
+        """FusedAdamW.fused_state(w) when the fused optimiser took `w` over (then the caller updates w in the kernel that
+        forms its gradient, after every other reader of w in this backward), else None."""
+        fused = self.fused_opt if self.grad_sink is None else None
+        return fused.fused_state(w) if fused is not None else None
+
+    def _row_scaled(self, bufs, B, K, A, rs, scol, st):
+        """First half of a layer's weight-gradient step: (A, scol) as the product reads them.  With a per-row factor `rs`
+        on dz, (rs . dZ)^T A == dZ^T (rs . A): the small activation A [B, K] is scaled into bufs.hs instead of the big dZ,
+        and the copy's column K (when it has one) holds rs itself, so that db comes out of the product (scol = 1)."""
+        if rs is None:
+            return A, scol
+        rowscale(self.lib, A, rs, B, K, bufs.hs, st)
+        return bufs.hs, int(bufs.hs.stride(0) > K)
+
+    def _weight_grad(self, bufs, B, w, dz, rs, A, scol, dW, db, fs, st, queue=None):
+        """Second half: the product for w [N, K] from dz = d(loss)/d(pre-activation) up to the per-row factor `rs` (or None)
+        and (A, scol) of _row_scaled.  Plain (fs None): dW and db are written.  Fused (fs = _fused_state(w)): w and its
+        moments are updated in the product's epilogue, only db is written; with `queue` the product is not launched but
+        appended as (GdDwAdamw entry, w) for the caller's gdmcf_linear_bwd_weight_adamw_multi_f32, which then bumps the
+        versions."""
+        N, K = w.shape
+        if fs is None:
+            linear_bwd_weight(self.lib, dz, A, rs, scol, B, N, K, dW, db, st)
+            return
+        args = dw_adamw_args(dz, A, rs, scol, B, N, K, w, db, fs)
+        if queue is not None:
+            queue.append((_lib.GdDwAdamw(*args), w))
+            return
+        linear_bwd_weight_adamw(self.lib, args, st)
+        # updated through a raw pointer.  bf16 with a registered shadow: the epilogue refreshed the shadow too, and an
+        # unchanged version keeps the engine from casting the weight again
+        if not (self.gemm_dtype == "bf16" and _lib.shadow_info(w.data_ptr()) is not None):
+            torch.autograd.graph.increment_version(w)
+
+    def _input_grad(self, bufs, B, W, N, K, dz, rs, A_prev, act_prev, d_prev, st):
+        linear_bwd_input(self.lib, bufs, dz, W, rs, A_prev, act_prev, B, N, K, d_prev, st)

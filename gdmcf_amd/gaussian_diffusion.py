@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import _lib
 from .DNN import DNN
+from .engine_core import TrainLoss, prep_input
 
 _SCHEDULE_KIND = {"linear": 0, "linear-var": 1, "cosine": 2, "binomial": 3}
 
@@ -24,24 +25,6 @@ _SCHEDULE_KIND = {"linear": 0, "linear-var": 1, "cosine": 2, "binomial": 3}
 class ModelMeanType(enum.Enum):
     START_X = enum.auto()  # the model predicts x_0
     EPSILON = enum.auto()  # the model predicts epsilon
-
-
-class _TrainLoss(torch.autograd.Function):
-    """loss[B] (float64) of the fused q_sample -> denoiser -> weighted row-MSE path."""
-
-    @staticmethod
-    def forward(ctx, eng, spec, *params):
-        loss = eng.train_forward(spec)
-        ctx.eng, ctx.version = eng, eng.version
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        eng = ctx.eng
-        if ctx.version != eng.version:
-            raise RuntimeError("gdmcf_amd: activations were overwritten by a later forward; "
-                               "call backward before the next training_losses/forward")
-        return (None, None, *eng.train_backward(gloss))
 
 
 class GaussianDiffusion(nn.Module):
@@ -160,21 +143,16 @@ class GaussianDiffusion(nn.Module):
         _lib.require_gpu(x_start, "x_start")
         if noise is not None:
             assert noise.shape == x_start.shape
-        lib = _lib.load()
         B, I = x_start.shape
         x = x_start.float().contiguous()
-        ldo = (I + 3) // 4 * 4
-        out = torch.empty(B, ldo, dtype=torch.float32, device=x.device)
+        out = torch.empty(B, (I + 3) // 4 * 4, dtype=torch.float32, device=x.device)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         nz = None if noise is None else noise.float().contiguous()
         self._q_calls = getattr(self, "_q_calls", 0) + 1
-        rc = lib.gdmcf_dnn_prep_input_f32(
-            x.data_ptr(), x.stride(0), t.data_ptr(), self._t32["sqrt_ab"].data_ptr(),
-            self._t32["sqrt_1mab"].data_ptr(), 1 if nz is not None else 2, _lib.ptr(nz),
-            nz.stride(0) if nz is not None else 0, 0, None, 0, 0.0, int(torch.initial_seed()) & (2 ** 63 - 1),
-            (1 << 40) + self._q_calls, 0, None, None, 0, B, I, out.data_ptr(), ldo, None, 0, None, None,
-            _lib.stream_ptr())
-        _lib.check(rc)
+        # the input builder without dropout, normalisation and embedding columns (E = 0)
+        prep_input(_lib.load(), x, I, t, self._t32["sqrt_ab"], self._t32["sqrt_1mab"], nz, None, 0.0, False,
+                   int(torch.initial_seed()) & (2 ** 63 - 1), (1 << 40) + self._q_calls, False, None, 0, out, None, None, None,
+                   _lib.stream_ptr())
         return out[:, :I]
 
     # -- the reference's per-step pieces, for callers that use them directly -----------------------
@@ -234,6 +212,17 @@ class GaussianDiffusion(nn.Module):
                 x_start = x_start.dense()
         batch_size, device = x_start.size(0), x_start.device
         assert x_start.dim() == 2 and x_start.size(1) == model.in_dims[0], "x_start must be [B, n_items]"
+        spec = self._train_spec(x_start, reweight, ts, pt, noise, drop_mask)
+        if drop_mask is None and self.rng == "torch" and model.training and model.drop.p > 0:
+            spec["drop_mask"] = torch.bernoulli(torch.full_like(x_start, 1.0 - model.drop.p, dtype=torch.float32)).to(torch.uint8)
+        if csr_batch is not None:
+            spec.update(x_start=None, csr=csr_batch)
+        return self._fused_loss(model, spec, batch_size, device)
+
+    def _train_spec(self, x_start, reweight, ts, pt, noise, drop_mask):
+        """What an engine's train_forward needs of one training step: timesteps (drawn here unless given), schedule
+        coefficients, the noise when it has to exist in HBM, per-timestep loss weights, the importance-sampling history."""
+        batch_size, device = x_start.size(0), x_start.device
         if ts is None:
             ts, pt = self.sample_timesteps(batch_size, device, "importance")
         ts = ts.to(device=device, dtype=torch.int64).contiguous()
@@ -249,28 +238,28 @@ class GaussianDiffusion(nn.Module):
                 noise, noise_owned = self._draw_noise(x_start, eps_mode), True  # eps is the target: must exist in HBM
         elif eps_mode:
             raise NotImplementedError("noise_scale == 0 with mean_type EPSILON")
-        if drop_mask is None and self.rng == "torch" and model.training and model.drop.p > 0:
-            drop_mask = torch.bernoulli(torch.full_like(x_start, 1.0 - model.drop.p, dtype=torch.float32)).to(torch.uint8)
         if reweight == True:  # noqa: E712  (the reference's own test)
             if self.noise_scale == 0.0:
-                raise AttributeError("GaussianDiffusion has no schedule tables (noise_scale == 0): the SNR weights of "
+                raise AttributeError(f"{type(self).__name__} has no schedule tables (noise_scale == 0): the SNR weights of "
                                      "reweight=True do not exist -- the reference fails the same way (:340, :525-530)")
             weight_t = self._weights["eps" if eps_mode else "x0"]
         else:
             # the reference leaves `loss` undefined here (NameError); DiffRec semantics: unit weights on the mse
             # (for the eps target that also means no x0-likelihood term on the t == 0 rows)
             weight_t = self._weights["one"]
-        spec = dict(x_start=None if csr_batch is not None else x_start, csr=csr_batch, ts=ts, pt=pt, ca=ca, cb=cb, noise=noise,
-                    noise_owned=noise_owned,
-                    drop_mask=drop_mask, eps_mode=eps_mode,
-                    weight_t=weight_t, T=self.steps, H=self.history_num_per_term, Lt_history=self.Lt_history,
-                    Lt_count=self.Lt_count, update_history=self.update_history, t0_likelihood=(reweight == True))  # noqa: E712
+        spec = dict(x_start=x_start, ts=ts, pt=pt, ca=ca, cb=cb, noise=noise, noise_owned=noise_owned, drop_mask=drop_mask,
+                    eps_mode=eps_mode, weight_t=weight_t, T=self.steps, H=self.history_num_per_term,
+                    Lt_history=self.Lt_history, Lt_count=self.Lt_count, update_history=self.update_history,
+                    t0_likelihood=(reweight == True))  # noqa: E712
         if eps_mode:
             spec["r1_0"] = self._t32["r1"][0]
             spec["r2_0"] = self._t32["r2"][0]
+        return spec
+
+    def _fused_loss(self, model, spec, batch_size, device):
         eng = model.engine
-        loss = _TrainLoss.apply(eng, spec, *model.param_list())
-        self.last_ts, self.last_loss_unscaled = ts, eng.buffers(batch_size, device).lu
+        loss = TrainLoss.apply(eng, spec, *model.param_list())
+        self.last_ts, self.last_loss_unscaled = spec["ts"], eng.buffers(batch_size, device).lu
         return {"loss": loss}
 
     # -- sampling --------------------------------------------------------------------------------
@@ -363,46 +352,16 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
                         drop_mask=None, ts_U=None, sampled=None, drop_mask_U=None):
         if not self.CatOneHot:
             return super().training_losses(model, x_start, reweight, index, ts=ts, pt=pt, noise=noise, drop_mask=drop_mask)
-        from .onehot import _OneHotTrainLoss
         _lib.require_gpu(x_start, "x_start")
         model = self._onehot_model(model)
         batch_size, device = x_start.size(0), x_start.device
         assert x_start.dim() == 2 and x_start.size(1) == model.in_dims[0], "x_start must be [B, n_items]"
         if sampled is None and ts_U is None:
             ts_U, _ = self.sample_timesteps(batch_size, device, "importance")  # first draw: the one-hot rows' noise level
-        if ts is None:
-            ts, pt = self.sample_timesteps(batch_size, device, "importance")  # second draw: what the model sees
-        ts = ts.to(device=device, dtype=torch.int64).contiguous()
-        pt = pt.to(device=device, dtype=torch.float64).contiguous()
-        eps_mode = self.mean_type == ModelMeanType.EPSILON
-        if self.mean_type not in (ModelMeanType.START_X, ModelMeanType.EPSILON):
-            raise NotImplementedError(self.mean_type)
-        ca = cb = None
-        noise_owned = False
-        if self.noise_scale != 0.0:
-            ca, cb = self._t32["sqrt_ab"], self._t32["sqrt_1mab"]
-            if noise is None and (eps_mode or self.rng == "torch"):
-                noise, noise_owned = self._draw_noise(x_start, eps_mode), True
-        elif eps_mode:
-            raise NotImplementedError("noise_scale == 0 with mean_type EPSILON")
-        if reweight == True:  # noqa: E712
-            if self.noise_scale == 0.0:
-                raise AttributeError("GaussianDiffusionDiscrete has no schedule tables (noise_scale == 0)")
-            weight_t = self._weights["eps" if eps_mode else "x0"]
-        else:
-            weight_t = self._weights["one"]
-        spec = dict(x_start=x_start, ts=ts, pt=pt, ca=ca, cb=cb, noise=noise, noise_owned=noise_owned, drop_mask=drop_mask,
-                    eps_mode=eps_mode,
-                    weight_t=weight_t, T=self.steps, H=self.history_num_per_term, Lt_history=self.Lt_history,
-                    Lt_count=self.Lt_count, update_history=self.update_history, t0_likelihood=(reweight == True),  # noqa: E712
-                    ts_U=ts_U, sampled=sampled, drop_mask_U=drop_mask_U, discrete=self.discrete, index=index)
-        if eps_mode:
-            spec["r1_0"] = self._t32["r1"][0]
-            spec["r2_0"] = self._t32["r2"][0]
-        eng = model.engine
-        loss = _OneHotTrainLoss.apply(eng, spec, *model.param_list())
-        self.last_ts, self.last_loss_unscaled = ts, eng.buffers(batch_size, device).lu
-        return {"loss": loss}
+        # (the builder's own draw is the second one: what the model sees)
+        spec = self._train_spec(x_start, reweight, ts, pt, noise, drop_mask)
+        spec.update(ts_U=ts_U, sampled=sampled, drop_mask_U=drop_mask_U, discrete=self.discrete, index=index)
+        return self._fused_loss(model, spec, batch_size, device)
 
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,
                  capture=None, sampled0=None, graph_sampled=None, graph_pick=None):

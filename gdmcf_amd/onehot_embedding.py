@@ -17,7 +17,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .onehot import DNNOneHot, OneHotEngine, _ceil64
+from . import engine_core as core
+from .engine_core import _ceil64, with_precision
+from .onehot import DNNOneHot, OneHotEngine
 
 
 def nt_xent_loss(z1, z2, temperature=0.1, eps=1e-5):
@@ -34,7 +36,7 @@ class OneHotEmbeddingEngine(OneHotEngine):
         b = super().buffers(B, device)
         if hasattr(b, "ucat"):
             return b
-        m, lib = self.model, self.lib
+        m = self.model
         f32 = dict(dtype=torch.float32, device=device)
         b.h12 = b.h1 + b.h2
         b.eu = m.embedding_user.weight.shape[1]
@@ -51,10 +53,7 @@ class OneHotEmbeddingEngine(OneHotEngine):
         b.rn_u = torch.zeros(B, **f32)
         b.rn_v = torch.zeros(self.I, **f32)
         b.Vhat = torch.zeros(self.I, ldD, **f32)
-        ws = max(b.ws_bytes, lib.gdmcf_linear_ws_bytes(B, self.I, b.D))
-        if ws > b.ws_bytes:
-            b.ws_bytes = int(ws)
-            b.ws = torch.empty(ws, dtype=torch.uint8, device=device)
+        self._grow_workspace(b, B, device, [(self.I, b.D)])
         return b
 
     def _scores_operands(self, bufs, br1, br2, B, index):
@@ -67,15 +66,13 @@ class OneHotEmbeddingEngine(OneHotEngine):
                                              bufs.ucat.data_ptr() + 4 * bufs.h12, ld, st))
         u = self._user_vector(bufs, B)  # what is scored against the items: ucat itself, or a subclass's function of it
         _lib.check(lib.gdmcf_row_norms_f32(u.data_ptr(), u.stride(0), B, bufs.D, None, bufs.rn_u.data_ptr(), st))
-        _lib.check(lib.gdmcf_rowscale_f32(u.data_ptr(), u.stride(0), bufs.rn_u.data_ptr(), B, bufs.D, bufs.uhat.data_ptr(),
-                                          bufs.uhat.stride(0), st))
+        core.rowscale(lib, u, bufs.rn_u, B, bufs.D, bufs.uhat, st)
         # V / |v| only changes with the item table (every optimiser step while training; never during evaluation, where
         # the reverse loop calls the model T times per batch): rebuilt when the parameter's version counter moved
         key = (V.data_ptr(), V._version)
         if getattr(bufs, "vhat_key", None) != key:
             _lib.check(lib.gdmcf_row_norms_f32(V.data_ptr(), V.stride(0), self.I, bufs.D, None, bufs.rn_v.data_ptr(), st))
-            _lib.check(lib.gdmcf_rowscale_f32(V.data_ptr(), V.stride(0), bufs.rn_v.data_ptr(), self.I, bufs.D,
-                                              bufs.Vhat.data_ptr(), bufs.Vhat.stride(0), st))
+            core.rowscale(lib, V, bufs.rn_v, self.I, bufs.D, bufs.Vhat, st)
             bufs.vhat_key = key
 
     def _user_vector(self, bufs, B):
@@ -103,8 +100,7 @@ class OneHotEmbeddingEngine(OneHotEngine):
         index = self._index_on(spec["index"], dev, B)
         x0, target, alpha, rowdiv, keep = self._train_inputs(spec, bufs)
         self._scores_operands(bufs, br1, br2, B, index)
-        loss = self._loss_layer(spec, bufs, B, bufs.uhat.data_ptr(), bufs.uhat.stride(0), bufs.Vhat.data_ptr(),
-                                bufs.Vhat.stride(0), None, self.I, bufs.D, target, alpha, rowdiv)
+        loss = self._loss_layer(spec, bufs, B, bufs.uhat, bufs.Vhat, None, self.I, bufs.D, target, alpha, rowdiv)
         # NT-Xent term between the two hidden activations (reference torch expressions, [B, B] work)
         with torch.enable_grad():
             h = bufs.ucat[:, : bufs.h1].detach().clone().requires_grad_(True)
@@ -136,20 +132,18 @@ class OneHotEmbeddingEngine(OneHotEngine):
         # by the pass that forms its gradient
         fsV, fsU = self._fused_state(V), self._fused_state(Wu)
         # scores = uhat @ Vhat^T: gradient w.r.t. Vhat, then through V / |v|
-        dV, _ = self._weight_grad(bufs, B, V, None, bufs.diff.data_ptr(), bufs.ldi, rs, bufs.uhat.data_ptr(), bufs.uhat.stride(0))
+        dV, _ = self._dense_grads(bufs, B, V, None, bufs.diff, rs, bufs.uhat)
         if fsV is None:
             _lib.check(lib.gdmcf_normalize_rows_bwd_f32(dV.data_ptr(), dV.stride(0), bufs.Vhat.data_ptr(), bufs.Vhat.stride(0),
                                                         bufs.rn_v.data_ptr(), self.I, bufs.D, dV.data_ptr(), dV.stride(0), st))
         else:
             _lib.check(lib.gdmcf_normalize_rows_bwd_adamw_f32(
                 dV.data_ptr(), dV.stride(0), bufs.Vhat.data_ptr(), bufs.Vhat.stride(0), bufs.rn_v.data_ptr(), self.I, bufs.D,
-                V.data_ptr(), V.stride(0), fsV["exp_avg"].data_ptr(), fsV["exp_avg_sq"].data_ptr(), fsV["lr"], fsV["beta1"],
-                fsV["beta2"], fsV["eps"], fsV["weight_decay"], fsV["step"], fsV["grad_scale"], st))
+                V.data_ptr(), V.stride(0), *core.adamw_args(fsV, V), st))
             torch.autograd.graph.increment_version(V)  # (also what rebuilds the cached V / |v| at the next forward)
             dV = None
         # ... w.r.t. uhat, then through u / |u|
-        self._input_grad(bufs, B, bufs.Vhat.data_ptr(), bufs.Vhat.stride(0), self.I, bufs.D, bufs.diff.data_ptr(), bufs.ldi, rs,
-                         bufs.ucat.data_ptr(), bufs.ucat.stride(0), 0, bufs.du.data_ptr(), bufs.du.stride(0))
+        self._input_grad(bufs, B, bufs.Vhat, self.I, bufs.D, bufs.diff, rs, bufs.ucat, 0, bufs.du, st)
         _lib.check(lib.gdmcf_normalize_rows_bwd_f32(bufs.du.data_ptr(), bufs.du.stride(0), bufs.uhat.data_ptr(),
                                                     bufs.uhat.stride(0), bufs.rn_u.data_ptr(), B, bufs.D, bufs.du.data_ptr(),
                                                     bufs.du.stride(0), st))
@@ -163,8 +157,7 @@ class OneHotEmbeddingEngine(OneHotEngine):
         else:
             _lib.check(lib.gdmcf_scatter_rows_adamw_f32(
                 bufs.du.data_ptr() + 4 * bufs.h12, bufs.du.stride(0), index.data_ptr(), B, Wu.shape[0], bufs.eu, Wu.data_ptr(),
-                Wu.stride(0), fsU["exp_avg"].data_ptr(), fsU["exp_avg_sq"].data_ptr(), fsU["lr"], fsU["beta1"], fsU["beta2"],
-                fsU["eps"], fsU["weight_decay"], fsU["step"], fsU["grad_scale"], st))
+                Wu.stride(0), *core.adamw_args(fsU, Wu), st))
             torch.autograd.graph.increment_version(Wu)
             dWu = None
         # hidden activations: + NT-Xent gradient, times tanh'
@@ -181,33 +174,16 @@ class OneHotEmbeddingEngine(OneHotEngine):
         sv["keepalive"] = (sv["keepalive"], gc)
         return res + [dV, dWu]
 
+    @with_precision
     def forward_plain(self, x, timesteps, x_U, training, drop_mask=None, drop_mask_U=None, index=None, posterior=None):
-        prev = self.lib.gdmcf_gemm_precision(self._precision())
-        try:
-            B, dev = x.shape[0], x.device
-            br1, br2, _ = self._chains()
-            bufs = self.buffers(B, dev)
-            lib, st = self.lib, _lib.stream_ptr()
-            self.version += 1
-            self._saved = None
-            index = self._index_on(index, dev, B)
-            ts = timesteps.to(device=dev, dtype=torch.int64).contiguous()
-            if x.dtype != torch.float32 or x.stride(-1) != 1:
-                x = x.float().contiguous()
-            xu = x_U.reshape(B, -1)
-            if xu.shape[1] != 2 * self.I:
-                raise RuntimeError("gdmcf_amd.DNNOneHotEmbedding: x_U must hold two columns per item")
-            if xu.dtype != torch.float32 or xu.stride(-1) != 1:
-                xu = xu.float().contiguous()
-            keep = (self._prep(bufs, x, self.I, bufs.xin1, ts, None, None, None, drop_mask, training),
-                    self._prep(bufs, xu, 2 * self.I, bufs.xin2, ts, None, None, None, drop_mask_U, training))
-            self._scores_operands(bufs, br1, br2, B, index)
-            res = self._last_layer(bufs.uhat.data_ptr(), bufs.uhat.stride(0), bufs.Vhat.data_ptr(), bufs.Vhat.stride(0), None,
-                                   0, B, self.I, bufs.D, x, posterior, bufs, st)
-            del keep
-            return res
-        finally:
-            self.lib.gdmcf_gemm_precision(prev)
+        br1, br2, _ = self._chains()
+        B = x.shape[0]
+        index = self._index_on(index, x.device, B)
+        bufs, x, keep = self._plain_inputs(x, timesteps, x_U, training, drop_mask, drop_mask_U)
+        self._scores_operands(bufs, br1, br2, B, index)
+        res = self._last_layer(bufs, bufs.uhat, bufs.Vhat, None, 0, B, self.I, bufs.D, x, posterior)
+        del keep
+        return res
 
 
 class DNNOneHotEmbedding(DNNOneHot):

@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .onehot import _ceil64
+from . import engine_core as core
+from .engine_core import _ceil64
 from .onehot_embedding import DNNOneHotEmbedding, OneHotEmbeddingEngine
 
 
@@ -38,13 +39,8 @@ class OneHotGCNEngine(OneHotEmbeddingEngine):
             b.dz1 = torch.zeros_like(b.z1)
         b.z2 = torch.zeros(B, b.ucat.stride(0), **f32)
         b.dtmp = torch.zeros(B, b.ucat.stride(0), **f32)
-        ws = b.ws_bytes
-        for conv in self._convs():
-            w = conv.lin.weight
-            ws = max(ws, self.lib.gdmcf_linear_ws_bytes(B, w.shape[0], w.shape[1]), self.lib.gdmcf_linear_ws_bytes(B, w.shape[1], w.shape[0]))
-        if ws > b.ws_bytes:
-            b.ws_bytes = int(ws)
-            b.ws = torch.empty(ws, dtype=torch.uint8, device=device)
+        shapes = [tuple(conv.lin.weight.shape) for conv in self._convs()]
+        self._grow_workspace(b, B, device, shapes + [s[::-1] for s in shapes])
         return b
 
     def _convs(self):
@@ -55,9 +51,7 @@ class OneHotGCNEngine(OneHotEmbeddingEngine):
 
     def _linear(self, bufs, B, A, conv, out):
         w, bias = conv.lin.weight, conv.bias
-        _lib.check(self.lib.gdmcf_linear_fwd_f32(A.data_ptr(), A.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr(), 0, B,
-                                                 w.shape[0], w.shape[1], out.data_ptr(), out.stride(0), bufs.ws.data_ptr(),
-                                                 bufs.ws_bytes, _lib.stream_ptr()))
+        core.linear_fwd(self.lib, bufs, A, w, bias, 0, B, w.shape[0], w.shape[1], out, _lib.stream_ptr())
 
     def _user_vector(self, bufs, B):
         m, D = self.model, bufs.D
@@ -75,7 +69,7 @@ class OneHotGCNEngine(OneHotEmbeddingEngine):
         return bufs.ublend
 
     def _user_vector_backward(self, bufs, B):
-        m, D, lib, st = self.model, bufs.D, self.lib, _lib.stream_ptr()
+        m, D, st = self.model, bufs.D, _lib.stream_ptr()
         if m.gcn_layers == 0:
             return {m.sumW: torch.zeros_like(m.sumW)}
         convs = self._convs()
@@ -87,22 +81,14 @@ class OneHotGCNEngine(OneHotEmbeddingEngine):
 
         def layer_backward(conv, dz, A, dA):
             w, bias = conv.lin.weight, conv.bias
-            N, K = w.shape
             fs = self._fused_state(w)
-            dW, db = None, torch.empty_like(bias)
+            db = torch.empty_like(bias)
+            dW = torch.empty_like(w) if fs is None else None
             if fs is None:
-                dW = torch.empty_like(w)
-                _lib.check(lib.gdmcf_linear_bwd_weight_f32(dz.data_ptr(), dz.stride(0), A.data_ptr(), A.stride(0), None, 0, B, N,
-                                                           K, dW.data_ptr(), dW.stride(0), db.data_ptr(), 0, st))
-            _lib.check(lib.gdmcf_linear_bwd_input_f32(dz.data_ptr(), dz.stride(0), w.data_ptr(), w.stride(0), None, A.data_ptr(),
-                                                      A.stride(0), 0, B, N, K, dA.data_ptr(), dA.stride(0), bufs.ws.data_ptr(),
-                                                      bufs.ws_bytes, st))
+                self._weight_grad(bufs, B, w, dz, None, A, 0, dW, db, None, st)
+            self._input_grad(bufs, B, w, w.shape[0], w.shape[1], dz, None, A, 0, dA, st)
             if fs is not None:  # fused optimiser: after the input gradient, which reads w
-                _lib.check(lib.gdmcf_linear_bwd_weight_adamw_f32(
-                    dz.data_ptr(), dz.stride(0), A.data_ptr(), A.stride(0), None, 0, B, N, K, w.data_ptr(), w.stride(0),
-                    fs["exp_avg"].data_ptr(), fs["exp_avg_sq"].data_ptr(), db.data_ptr(), fs["lr"], fs["beta1"], fs["beta2"],
-                    fs["eps"], fs["weight_decay"], fs["step"], fs["grad_scale"], st))
-                torch.autograd.graph.increment_version(w)
+                self._weight_grad(bufs, B, w, dz, None, A, 0, None, db, fs, st)
             grads[w], grads[bias] = dW, db
 
         if m.gcn_layers == 2:
