@@ -97,6 +97,9 @@ _SIGNATURES = {
     "gdmcf_linear_loss_fwd_bits_f32": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, P, c_int, c_int, c_int, P, c_int64, P,
                                                c_int64, P, P, P]),
     "gdmcf_scale_f32": (c_int, [P, c_int64, c_float, P, P]),
+    "gdmcf_onehot_prep_input_csr_f32": (c_int, [P, P, P, P, c_float, P, c_int64, c_uint64, c_uint64, P, c_int64, P, c_int, P,
+                                                c_int64, c_float, c_uint64, P, P, c_int, c_int, c_int, P, c_int64, P, P,
+                                                c_int64, P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

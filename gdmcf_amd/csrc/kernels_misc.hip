@@ -146,6 +146,60 @@ __device__ __forceinline__ void xt4(const PrepArgs& a, int b, int col, float ca,
     }
 }
 
+// One-hot CSR source (gdmcf_onehot_prep_input_csr_f32): the builder's "row" is the [2I] one-hot image of a {0,1} CSR row under the
+// discrete transition noise of onehot_noise_kernel -- columns (2i, 2i + 1) of item i -- formed on the fly: no dense row, no xU.
+struct OneHotSrc {
+    const int64_t* ts_U;   // [B] timesteps of the class draws (may be NULL when the classes are given)
+    const uint8_t* sampled;  // given classes [B, lds] or NULL: drawn (stream 3, `offset`)
+    int64_t lds;
+    uint8_t* sampled_out;  // optional [B, ldso]
+    int64_t ldso;
+    float p1_off;     // (float)(1 - e)
+    uint64_t offset;  // Philox offset of the class draws (the builder's own `PrepArgs::offset` is the dropout's)
+    int items;        // I (PrepArgs::I is 2I here)
+};
+
+// the two class uniforms of the items (col >> 1, (col >> 1) + 1) behind a group of four one-hot columns: words (0, 1) or (2, 3)
+// -- by (col >> 2) & 1 -- of the stream-3 block onehot_noise_kernel draws for the four items (col >> 3) * 4 ..
+__device__ __forceinline__ void onehot_uniforms(const PrepArgs& a, const OneHotSrc& o, int b, int col, uint32_t (&u)[2]) {
+    const uint4 r = philox4x32_10(make_uint4((uint32_t)(col >> 3), (uint32_t)b, 3u, (uint32_t)o.offset),
+                                  make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32)));
+    const bool hi = (col >> 2) & 1;
+    u[0] = hi ? r.z : r.x;
+    u[1] = hi ? r.w : r.y;
+}
+
+// the four one-hot columns col .. col + 3 of row b: exactly what onehot_noise_kernel writes to xU[b, col .. col + 3] (same
+// `a`, same unfused p1 arithmetic, same comparison).  bm: the workgroup's 2048 items as bits; u: onehot_uniforms (drawn classes).
+template <bool FULL>
+__device__ __forceinline__ void onehot4(const PrepArgs& a, const OneHotSrc& o, int b, int col, float an, const uint32_t (&u)[2],
+                                        float (&v)[4], const uint32_t* bm, int bm_col0) {
+    const int it = (col - bm_col0) >> 1;  // even: both items' bits sit in one word
+    const uint32_t w = bm[it >> 5] >> (it & 31);
+    const int i0 = col >> 1;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const bool in = FULL || col + 2 * j < a.I;
+        const int c0 = in && ((w >> j) & 1u);
+        int s = 0;
+        if (o.sampled) {
+            if (in) s = o.sampled[(int64_t)b * o.lds + i0 + j] != 0;
+        } else {
+            float p1;
+            {
+#pragma clang fp contract(off)
+                const float q = (1.f - an) * o.p1_off;
+                p1 = (c0 ? an : 0.f) + q;
+            }
+            s = ((float)(u[j] >> 8) * 5.9604644775390625e-8f) < p1;
+        }
+        if (o.sampled_out && in) o.sampled_out[(int64_t)b * o.ldso + i0 + j] = (uint8_t)s;
+        const float keep = (in && s == c0) ? 1.f : 0.f;
+        v[2 * j] = c0 ? 0.f : keep;
+        v[2 * j + 1] = c0 ? keep : 0.f;
+    }
+}
+
 __global__ __launch_bounds__(256) void prep_rowss_kernel(PrepArgs a, float* __restrict__ rownorm) {
     if (a.step_state) a.offset = a.step_state->prep_offset;
     const int b = blockIdx.x;
@@ -173,8 +227,12 @@ __global__ __launch_bounds__(256) void prep_rowss_kernel(PrepArgs a, float* __re
 // are fetched once per thread and each workgroup moves 16 KB in and out instead of 4 KB.
 constexpr int PREP_G = 4;
 
-__global__ __launch_bounds__(256) void prep_input_kernel(PrepArgs a) {
-    if (a.step_state) a.offset = a.step_state->prep_offset;
+// SRC 0: dense rows / CSR rows (prep_input_kernel).  SRC 1: the one-hot image of CSR rows (onehot_prep_input_csr_kernel) -- a
+// compile-time source, so that the SRC 0 kernel's ISA is what it was (the builder is instruction-fetch- and VALU-issue-bound,
+// profiles/r04_prep_input_ablation.txt); dropout, embedding columns, the 1 behind them and the padding are this one body.
+template <int SRC>
+__device__ __forceinline__ void prep_input_body(PrepArgs a, const OneHotSrc o) {
+    if (SRC == 0 && a.step_state) a.offset = a.step_state->prep_offset;
     const int b = blockIdx.y;
     const int64_t t = a.ts ? a.ts[b] : 0;
     float ca = 1.f, cb = 0.f;
@@ -187,7 +245,25 @@ __global__ __launch_bounds__(256) void prep_input_kernel(PrepArgs a) {
     __shared__ float s_temb[256];
     __shared__ uint32_t s_bm[256 * PREP_G * 4 / 32];  // CSR source: this workgroup's 4096 columns of row b as bits
     const int bm_col0 = blockIdx.x * (256 * PREP_G * 4);
-    if (a.csr_indptr) {
+    if (SRC == 1) {
+        // the workgroup's 4096 one-hot columns are 2048 items: their bits, marked from the CSR row as below
+        constexpr int SPAN = 256 * PREP_G * 2;
+        const int item0 = bm_col0 >> 1;
+        if (threadIdx.x < SPAN / 32) s_bm[threadIdx.x] = 0u;
+        __syncthreads();
+        const int64_t r = a.csr_rows[b];
+        const int64_t beg = a.csr_indptr[r], end = a.csr_indptr[r + 1];
+        for (int64_t k = beg + threadIdx.x; k < end; k += 256) {
+            const int ci = a.csr_indices[k];
+            const int c = ci - item0;
+            if (c >= 0 && c < SPAN && ci < o.items) atomicOr(&s_bm[c >> 5], 1u << (c & 31));
+        }
+        __syncthreads();
+        if (a.bits_out && threadIdx.x < SPAN / 32) {
+            const int64_t w = (int64_t)(item0 >> 5) + threadIdx.x;
+            if (w < a.ldbits) a.bits_out[(int64_t)b * a.ldbits + w] = s_bm[threadIdx.x];
+        }
+    } else if (a.csr_indptr) {
         if (threadIdx.x < 256 * PREP_G * 4 / 32) s_bm[threadIdx.x] = 0u;
         __syncthreads();
         const int64_t r = a.csr_rows[b];
@@ -202,7 +278,7 @@ __global__ __launch_bounds__(256) void prep_input_kernel(PrepArgs a) {
             if (w < a.ldbits) a.bits_out[(int64_t)b * a.ldbits + w] = s_bm[threadIdx.x];
         }
     }
-    const uint32_t* bm = a.csr_indptr ? s_bm : nullptr;
+    const uint32_t* bm = (SRC == 1 || a.csr_indptr) ? s_bm : nullptr;
     const bool has_emb = a.E > 0 && a.E <= 256 && (int)((blockIdx.x + 1) * (256 * PREP_G * 4)) > a.I;
     if (has_emb) {
         if ((int)threadIdx.x < a.E) s_temb[threadIdx.x] = temb_value((float)t, threadIdx.x, a.E);
@@ -212,6 +288,29 @@ __global__ __launch_bounds__(256) void prep_input_kernel(PrepArgs a) {
     const int col_base = (blockIdx.x * (256 * PREP_G) + threadIdx.x) * 4;  // group u of this thread: col_base + 1024 u
     // ---- the hot path: whole groups of four item columns (all but the last group or two of a row) ----
     uint4 dr = make_uint4(0u, 0u, 0u, 0u);  // dropout uniforms of a PAIR of column groups (u, u + 1): 16 bits per element
+    // SRC 1, drawn classes.  A group of four columns is two items: half a stream-3 block, whose other half belongs to the
+    // neighbouring lane's group (lanes 2k and 2k + 1 hold the columns of the four items of one block, for every u).  The block
+    // is SHARED, not computed twice: of the pair's PREP_G blocks the even lane computes those of u = 0, 1 and the odd lane
+    // those of u = 2, 3, and each hands the other the half it needs with one lane swap per word (own[k] / got[k]: block of
+    // u = 2 * parity + k resp. u = 2 * (1 - parity) + k).  That keeps the builder at PREP_G / 2 class blocks + PREP_G / 2 dropout
+    // blocks per thread -- what onehot_noise_kernel plus the dense builder spend per four columns -- where the straightforward
+    // form doubles the class blocks (+ 50 % Philox in a VALU-issue-bound kernel).  All lanes of the workgroup get here (no
+    // divergence before the swaps); the rolled tail pass below, which is divergent, draws its own block instead.
+    uint32_t own[PREP_G / 2][2] = {}, got[PREP_G / 2][2] = {};
+    float an = 1.f;
+    const int par = threadIdx.x & 1;
+    if (SRC == 1 && !o.sampled) {
+        an = __fdiv_rn((float)o.ts_U[b], (float)a.B);
+#pragma unroll
+        for (int k = 0; k < PREP_G / 2; ++k) {
+            const int colk = col_base + (2 * par + k) * 1024;
+            const uint4 r = philox4x32_10(make_uint4((uint32_t)(colk >> 3), (uint32_t)b, 3u, (uint32_t)o.offset), key);
+            own[k][0] = par ? r.z : r.x;
+            own[k][1] = par ? r.w : r.y;
+            got[k][0] = __shfl_xor(par ? r.x : r.z, 1);
+            got[k][1] = __shfl_xor(par ? r.y : r.w, 1);
+        }
+    }
 #pragma unroll
     for (int u = 0; u < PREP_G; ++u) {
         const int col = col_base + u * 1024;
@@ -221,12 +320,18 @@ __global__ __launch_bounds__(256) void prep_input_kernel(PrepArgs a) {
         const int dsh = 16 * (u & 1);
         const uint32_t du[4] = {(dr.x >> dsh) & 0xFFFFu, (dr.y >> dsh) & 0xFFFFu, (dr.z >> dsh) & 0xFFFFu, (dr.w >> dsh) & 0xFFFFu};
         float v[4];
-        xt4<true>(a, b, col, ca, cb, v, bm, bm_col0);
-        if (a.xt_out) {
+        if (SRC == 1) {
+            const bool mine = par == (u >> 1);
+            const uint32_t cu[2] = {mine ? own[u & 1][0] : got[u & 1][0], mine ? own[u & 1][1] : got[u & 1][1]};
+            onehot4<true>(a, o, b, col, an, cu, v, bm, bm_col0);
+        } else {
+            xt4<true>(a, b, col, ca, cb, v, bm, bm_col0);
+        }
+        if (SRC == 0 && a.xt_out) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) a.xt_out[(int64_t)b * a.ldxt + col + j] = v[j];
         }
-        if (a.rownorm) {
+        if (SRC == 0 && a.rownorm) {
             const float dn = fmaxf(a.rownorm[b], 1e-12f);
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = v[j] / dn;
@@ -255,12 +360,18 @@ __global__ __launch_bounds__(256) void prep_input_kernel(PrepArgs a) {
         if (col + 3 < a.I || col >= a.ldxin) continue;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         if (col < a.I) {
-            xt4(a, b, col, ca, cb, v, bm, bm_col0);
-            if (a.xt_out) {
+            if (SRC == 1) {
+                uint32_t cu[2] = {0u, 0u};
+                if (!o.sampled) onehot_uniforms(a, o, b, col, cu);
+                onehot4<false>(a, o, b, col, an, cu, v, bm, bm_col0);
+            } else {
+                xt4(a, b, col, ca, cb, v, bm, bm_col0);
+            }
+            if (SRC == 0 && a.xt_out) {
                 for (int j = 0; j < 4; ++j)
                     if (col + j < a.I) a.xt_out[(int64_t)b * a.ldxt + col + j] = v[j];
             }
-            if (a.rownorm) {
+            if (SRC == 0 && a.rownorm) {
                 const float dn = fmaxf(a.rownorm[b], 1e-12f);
                 for (int j = 0; j < 4; ++j) v[j] = v[j] / dn;
             }
@@ -301,6 +412,10 @@ __global__ __launch_bounds__(256) void prep_input_kernel(PrepArgs a) {
         if (oc < a.ldxin && col <= oc && oc < col + 4) a.xin[(int64_t)b * a.ldxin + oc] = 1.f;
     }
 }
+
+__global__ __launch_bounds__(256) void prep_input_kernel(PrepArgs a) { prep_input_body<0>(a, OneHotSrc{}); }
+
+__global__ __launch_bounds__(256) void onehot_prep_input_csr_kernel(PrepArgs a, OneHotSrc o) { prep_input_body<1>(a, o); }
 
 // One-hot rows with discrete transition noise (reference gaussian_diffusion.py:770-831 with :597-614, :999-1038, and the
 // `x_tU & one_hot(x_start)` of :849 / :686): item i of row b has class c0 = x0[b,i]; a class s is drawn from row c0 of
@@ -1256,6 +1371,55 @@ int gdmcf_dnn_prep_input_csr_f32(const int64_t* indptr, const int32_t* indices, 
         hipLaunchKernelGGL(prep_input_kernel, grid, dim3(256), 0, s, a);
     }
     return gd_launch_status("prep_input_csr");
+}
+
+int gdmcf_onehot_prep_input_csr_f32(const int64_t* indptr, const int32_t* indices, const int64_t* rows, const int64_t* ts_U,
+                                    float discrete, const uint8_t* sampled, int64_t lds, uint64_t seed, uint64_t offset_noise,
+                                    uint8_t* sampled_out, int64_t ldso, const int64_t* ts, int drop_mode, const uint8_t* keep,
+                                    int64_t ldkeep, float drop_p, uint64_t offset_prep, const float* emb_w, const float* emb_b,
+                                    int E, int B, int I, float* xin, int64_t ldxin, float* temb_out, uint32_t* bits_out,
+                                    int64_t ldbits, void* stream) {
+    GD_CHECK_SHAPE(B > 0 && I > 0 && E >= 0 && I <= 0x3FFFFFFF, "onehot_prep_input_csr: empty batch / too many items");
+    const int I2 = 2 * I;
+    GD_CHECK_SHAPE(ldxin >= (int64_t)I2 + E && (ldxin % 4) == 0 && gd_aligned16(xin),
+                   "onehot_prep_input_csr: xin must be 16B aligned, ld%4==0, ld >= 2I+E");
+    GD_CHECK_ARG(indptr && indices && rows, "onehot_prep_input_csr: CSR arrays / row ids missing");
+    GD_CHECK_ARG(!bits_out || ldbits >= (I + 31) / 32, "onehot_prep_input_csr: ldbits < ceil(I/32)");
+    GD_CHECK_ARG((sampled ? lds >= I : ts_U != nullptr) && (!sampled_out || ldso >= I),
+                 "onehot_prep_input_csr: classes / ts_U missing or bad leading dimension");
+    GD_CHECK_ARG(drop_mode >= 0 && drop_mode <= 2, "onehot_prep_input_csr: bad mode");
+    GD_CHECK_ARG(drop_mode != 1 || (keep && ldkeep >= I2), "onehot_prep_input_csr: explicit keep-mask missing");
+    GD_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "onehot_prep_input_csr: dropout p out of range");
+    GD_CHECK_ARG(E == 0 || (emb_w && emb_b && ts), "onehot_prep_input_csr: embedding weights / ts missing");
+    // both Philox offsets are by-value arguments: this entry has no device-side step state to read them from
+    GD_CHECK_ARG(t_gd_step_state == nullptr, "onehot_prep_input_csr: not available while a graph step state is bound");
+    PrepArgs a;
+    a.x = nullptr; a.ldx = 0; a.ts = ts; a.ca = nullptr; a.cb = nullptr; a.noise_mode = 0; a.noise = nullptr;
+    a.ldn = 0; a.drop_mode = drop_mode; a.keep = keep; a.ldkeep = ldkeep; a.drop_scale = 1.0f / (1.0f - drop_p);
+    a.keep_thresh = (uint32_t)fmin(fmax(rint((1.0 - (double)drop_p) * 65536.0), 0.0), 65536.0);
+    a.seed = seed; a.offset = offset_prep; a.step_state = nullptr; a.rownorm = nullptr; a.emb_w = emb_w; a.emb_b = emb_b; a.E = E; a.B = B;
+    a.I = I2; a.xin = xin; a.ldxin = ldxin; a.xt_out = nullptr; a.ldxt = 0; a.temb_out = temb_out;
+    a.xin16 = nullptr; a.ldxin16 = 0;
+    a.csr_indptr = indptr; a.csr_indices = indices; a.csr_rows = rows; a.bits_out = bits_out; a.ldbits = ldbits;
+    GdShadow sh;
+    if (gd_shadow_lookup(xin, &sh) && sh.rows == B && sh.cols == I2 + E) {
+        a.xin16 = (unsigned short*)sh.p16;
+        a.ldxin16 = sh.ld16;
+    }
+    OneHotSrc o;
+    o.ts_U = ts_U; o.sampled = sampled; o.lds = lds; o.sampled_out = sampled_out; o.ldso = ldso;
+    o.p1_off = (float)(1.0 - (double)discrete);  // as gdmcf_onehot_noise_f32: 1 - e formed in double, rounded once
+    o.offset = offset_noise; o.items = I;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(gd_cdiv((int)(ldxin / 4), 256 * PREP_G), B);
+    {
+        // algorithmic bytes: write xin (+ given classes / keep-mask, the classes written back); the rows are a few hundred bytes of CSR
+        const double bytes = (double)B * I * ((sampled ? 1.0 : 0.0) + (sampled_out ? 1.0 : 0.0) + (drop_mode == 1 ? 2.0 : 0.0)) +
+                             (double)B * ldxin * 4.0;
+        GdProfScope prof(7, bytes, s);
+        hipLaunchKernelGGL(onehot_prep_input_csr_kernel, grid, dim3(256), 0, s, a, o);
+    }
+    return gd_launch_status("onehot_prep_input_csr");
 }
 
 int gdmcf_dnn_emb_cols_f32(const int64_t* ts, const float* emb_w, const float* emb_b, int E, int B, int I, float* xin,

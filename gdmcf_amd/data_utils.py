@@ -73,11 +73,17 @@ class DeviceCSR:
 
 class CsrBatch:
     """A batch of interaction rows that stays sparse: rows `row_ids` of a DeviceCSR.  Hand it to
-    `GaussianDiffusion.training_losses` in place of the dense `[B, n_items]` tensor of the reference's loop
-    (main.py:343-346): the input builder then reads the few hundred bytes of CSR per row instead of a dense row, and the loss
-    takes its {0,1} target from bitmaps (gdmcf_dnn_prep_input_csr_f32 / gdmcf_linear_loss_fwd_bits_f32; same arithmetic,
-    bit-identical losses and gradients).  Configurations that need the dense row (F.normalize, the eps target, the
-    one-hot variants, values other than 1) densify it themselves (`dense()`)."""
+    `GaussianDiffusion.training_losses` / `GaussianDiffusionDiscrete.training_losses` in place of the dense `[B, n_items]`
+    tensor of the reference's loop (main.py:343-346): the input builder then reads the few hundred bytes of CSR per row
+    instead of a dense row, and the loss takes its {0,1} target from bitmaps (gdmcf_dnn_prep_input_csr_f32 /
+    gdmcf_linear_loss_fwd_bits_f32; same arithmetic, bit-identical losses and gradients).  The one-hot variants
+    (`CatOneHot=True`: DNNOneHot, DNNOneHotEmbedding, DNNOneHotEmbeddingGCN) stay sparse too: their second branch's input, the
+    one-hot image under the discrete noise, comes from the same CSR rows (gdmcf_onehot_prep_input_csr_f32) and the [B, 2I]
+    image is never stored.
+    Stays sparse: x0 target, `model.norm` false, all interaction values 1, rng == "philox" (or the noise given).  Anything
+    else -- F.normalize, the eps target, values other than 1, torch-drawn noise -- is densified inside `training_losses`
+    (`dense()`) and goes on as a dense batch, with the same results.  The reverse loop (`p_sample`, `driver.evaluate`) takes
+    dense rows only (it needs the dense x_t anyway)."""
 
     def __init__(self, csr, row_ids):
         self.csr = csr

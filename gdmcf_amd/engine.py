@@ -225,10 +225,7 @@ class DenoiserEngine(EngineBase):
         N, K = w.shape
         self._use_weight(w)
         if csr is not None:  # the target rows are bitmaps written by the CSR-fed input builder
-            _lib.check(lib.gdmcf_linear_loss_fwd_bits_f32(A.data_ptr(), A.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr(),
-                                                          bufs.x0bits.data_ptr(), bufs.x0bits.stride(0), None, B, N, K, None,
-                                                          0, bufs.diff.data_ptr(), bufs.ldi, bufs.rowpart.data_ptr(),
-                                                          bufs.rowsum.data_ptr(), st))
+            core.loss_layer_bits(lib, bufs, A, w, bias, bufs.x0bits, None, B, N, K, st)
         else:
             core.loss_layer(lib, bufs, A, w, bias, target, alpha, B, N, K, st)
         # the tail also emits mean(loss) and gradcoef/B: the reference's step takes the mean next (main.py:348), and its

@@ -100,6 +100,24 @@ def prep_input_csr(lib, batch, ts, ca, cb, noise, drop_mask, drop_p, training, s
     return batch, noise, keep
 
 
+def onehot_prep_input_csr(lib, batch, ts_U, discrete, sampled, seed, offset_noise, ts, drop_mask, drop_p, training,
+                          offset_prep, emb, E, xin, temb, st, sampled_out=None, x0bits=None):
+    """gdmcf_onehot_prep_input_csr_f32: the second branch's input [ drop(one-hot image under the discrete noise) | emb(t) | 1 |
+    0-pad ] straight from the device CSR rows of `batch` -- what gdmcf_onehot_noise_f32 + prep_input on its [B, 2I] image
+    leave in `xin`, without that image.  `sampled`: the given classes (uint8 [B, I]) or None (drawn at `offset_noise` from
+    ts_U); the dropout draws at `offset_prep`.  Returns (batch, sampled, keep) to keep referenced."""
+    B, I = batch.shape
+    _, _, drop_mode, keep = _prep_modes(B, None, None, drop_mask, drop_p, training)
+    (sp, lds), (kp, ldkp), (so, ldso), (xb, ldb) = _pl(sampled), _pl(keep), _pl(sampled_out), _pl(x0bits)
+    c = batch.csr
+    _lib.check(lib.gdmcf_onehot_prep_input_csr_f32(
+        c.indptr.data_ptr(), c.indices.data_ptr(), batch.row_ids.data_ptr(), _lib.ptr(ts_U), float(discrete), sp, lds, seed,
+        offset_noise, so, ldso, _lib.ptr(ts), drop_mode, kp, ldkp, drop_p, offset_prep,
+        emb.weight.data_ptr() if emb is not None else None, emb.bias.data_ptr() if emb is not None else None, E, B, I,
+        xin.data_ptr(), xin.stride(0), _lib.ptr(temb), xb, ldb, st))
+    return batch, sampled, keep
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # dense layers.  W is [N, K] row-major (rows at least K apart), `bufs` lends the split-K workspace.
 # ------------------------------------------------------------------------------------------------------------------
@@ -168,6 +186,14 @@ def loss_layer(lib, bufs, A, W, bias, target, alpha, B, N, K, st):
     _lib.check(lib.gdmcf_linear_loss_fwd_f32(a, lda, w, ldw, _lib.ptr(bias), target.data_ptr(), target.stride(0),
                                              _lib.ptr(alpha), B, N, K, None, 0, bufs.diff.data_ptr(), bufs.ldi,
                                              bufs.rowpart.data_ptr(), bufs.rowsum.data_ptr(), st))
+
+
+def loss_layer_bits(lib, bufs, A, W, bias, x0bits, alpha, B, N, K, st):
+    """loss_layer with the {0,1} target rows given as bitmaps (the CSR-fed input builders write them): same arithmetic."""
+    (a, lda), (w, ldw) = _pl(A), _pl(W)
+    _lib.check(lib.gdmcf_linear_loss_fwd_bits_f32(a, lda, w, ldw, _lib.ptr(bias), x0bits.data_ptr(), x0bits.stride(0),
+                                                  _lib.ptr(alpha), B, N, K, None, 0, bufs.diff.data_ptr(), bufs.ldi,
+                                                  bufs.rowpart.data_ptr(), bufs.rowsum.data_ptr(), st))
 
 
 def loss_tail(lib, bufs, spec, B, rowdiv, alpha, st, mean=False):

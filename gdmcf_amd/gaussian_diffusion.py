@@ -354,6 +354,17 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
             return super().training_losses(model, x_start, reweight, index, ts=ts, pt=pt, noise=noise, drop_mask=drop_mask)
         _lib.require_gpu(x_start, "x_start")
         model = self._onehot_model(model)
+        from .data_utils import CsrBatch
+        csr_batch = None
+        if isinstance(x_start, CsrBatch):
+            # rows left sparse: only what the CSR-fed kernels cover, otherwise densify here.  (rng == "torch"
+            # draws the noise with torch.randn_like of the dense rows, unless the noise is given or there is none.)
+            sparse_ok = (self.mean_type == ModelMeanType.START_X and not model.norm and x_start.csr.values is None
+                         and (self.rng == "philox" or noise is not None or self.noise_scale == 0.0))
+            if sparse_ok:
+                csr_batch = x_start
+            else:
+                x_start = x_start.dense()
         batch_size, device = x_start.size(0), x_start.device
         assert x_start.dim() == 2 and x_start.size(1) == model.in_dims[0], "x_start must be [B, n_items]"
         if sampled is None and ts_U is None:
@@ -361,6 +372,8 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         # (the builder's own draw is the second one: what the model sees)
         spec = self._train_spec(x_start, reweight, ts, pt, noise, drop_mask)
         spec.update(ts_U=ts_U, sampled=sampled, drop_mask_U=drop_mask_U, discrete=self.discrete, index=index)
+        if csr_batch is not None:
+            spec.update(x_start=None, csr=csr_batch)
         return self._fused_loss(model, spec, batch_size, device)
 
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,

@@ -9,6 +9,12 @@ branch), the dense layers, the fused loss epilogue, the weight / input gradient 
 branch writes straight into its column range of one [B, h1 + h2] buffer, and the gradient of that buffer is read back
 by column range.
 
+Training rows may arrive as a `data_utils.CsrBatch` (x0 target, no F.normalize): branch 1 is then fed by
+`gdmcf_dnn_prep_input_csr_f32`, branch 2 by `gdmcf_onehot_prep_input_csr_f32` (discrete noise, dropout and embedding columns in
+one launch), the loss target is the rows' bitmaps; no dense row and no [B, 2I] image exist, and the Philox positions are
+those of the dense route, so the two routes are the same run bit for bit.  The reverse loop and `GraphedTrainStep` do not
+take sparse rows.
+
 `gemm_dtype="bf16"` rounds the GEMM operands to bf16 on chip (from the f32 tensors: no bf16 shadows here).  Data parallel: the engine hands every gradient to `DataParallelStep`'s sink as soon as its
 kernels are enqueued (overlapped all-reduce, or the sharded optimiser with its all-gathers waited for at the end of the
 step).  Constructor, parameter names and initialisation draw order are the reference's, so checkpoints interchange.
@@ -45,7 +51,8 @@ class OneHotEngine(EngineBase):
         b.ld1, b.ld2 = _ceil64(I + E), _ceil64(2 * I + E)
         b.xin1 = torch.zeros(B, b.ld1, **f32)
         b.xin2 = torch.zeros(B, b.ld2, **f32)
-        b.xU = torch.zeros(B, 2 * I, **f32)
+        b.xU = None  # the [B, 2I] one-hot image of the dense route: made on its first step (_xU), never by a run on CSR rows
+        b.x0bits = None
         b.h1, b.h2 = br1[-1][0].shape[0], br2[-1][0].shape[0]
         b.hcat = torch.zeros(B, _ceil64(b.h1 + b.h2), **f32)
         b.dhcat = torch.zeros_like(b.hcat)
@@ -59,6 +66,18 @@ class OneHotEngine(EngineBase):
         return b
 
     # -- input builders ---------------------------------------------------------------------------------------------
+    @staticmethod
+    def _batch_of(spec):
+        """(B, device) of a training step's rows: a dense [B, I] tensor, or a data_utils.CsrBatch under spec["csr"]."""
+        x = spec.get("csr")
+        x = spec["x_start"] if x is None else x
+        return x.shape[0], x.device
+
+    def _xU(self, bufs, B, device):
+        if bufs.xU is None:
+            bufs.xU = torch.zeros(B, 2 * self.I, dtype=torch.float32, device=device)
+        return bufs.xU
+
     def onehot_rows(self, x0, ts_U, sampled, discrete, out=None):
         """x_tU of the reference (:841-849 / :672-686) as the [B, 2I] float image the second branch reads."""
         B = x0.shape[0]
@@ -102,6 +121,8 @@ class OneHotEngine(EngineBase):
     def _train_inputs(self, spec, bufs):
         """Both branch inputs (xin1: noised rows, xin2: one-hot image; dropout, normalize, embedding columns) and the
         loss target.  Returns (x0, target, alpha, rowdiv, keepalive)."""
+        if spec.get("csr") is not None:
+            return self._train_inputs_csr(spec, bufs)
         x0, ts = spec["x_start"], spec["ts"]
         B, dev = x0.shape[0], x0.device
         x0 = core._f32_rows(x0)
@@ -112,7 +133,7 @@ class OneHotEngine(EngineBase):
                 bufs.xt = torch.zeros(B, bufs.ldi, dtype=torch.float32, device=dev)
             xt_out = bufs.xt
         training = self.model.training
-        _, s8 = self.onehot_rows(x0, spec["ts_U"], spec["sampled"], spec["discrete"], out=bufs.xU)
+        _, s8 = self.onehot_rows(x0, spec["ts_U"], spec["sampled"], spec["discrete"], out=self._xU(bufs, B, dev))
         _, noise, keep1 = self._prep_input(bufs, x0, self.I, bufs.xin1, ts, spec["ca"], spec["cb"], spec["noise"],
                                            spec["drop_mask"], training, xt_out=xt_out)
         _, _, keep2 = self._prep_input(bufs, bufs.xU, 2 * self.I, bufs.xin2, ts, None, None, None, spec["drop_mask_U"], training)
@@ -123,14 +144,41 @@ class OneHotEngine(EngineBase):
             target, rowdiv = x0, bufs.rowdiv_mse
         return x0, target, alpha, rowdiv, (s8, noise, keep1, keep2)
 
+    def _train_inputs_csr(self, spec, bufs):
+        """_train_inputs for rows that stay sparse (spec["csr"]: data_utils.CsrBatch; x0 target, no F.normalize): xin1 and the
+        rows' bitmaps (the loss target, bufs.x0bits) from gdmcf_dnn_prep_input_csr_f32, xin2 from
+        gdmcf_onehot_prep_input_csr_f32 -- no dense row, no one-hot image.  The Philox position advances as on the dense
+        route (class draws, branch 1, branch 2), so both routes draw the same numbers from the same seed."""
+        batch, ts, m = spec["csr"], spec["ts"], self.model
+        B, I = batch.shape
+        dev, st, p, training = batch.device, _lib.stream_ptr(), float(m.drop.p), m.training
+        if bufs.x0bits is None:
+            bufs.x0bits = torch.zeros(B, (I + 31) // 32, dtype=torch.int32, device=dev)
+        s8, ts_U, sampled = None, spec["ts_U"], spec["sampled"]
+        if sampled is not None:
+            s8 = (sampled if sampled.dtype == torch.uint8 else (sampled != 0).to(torch.uint8)).contiguous()
+        elif ts_U is not None:
+            ts_U = ts_U.to(device=dev, dtype=torch.int64).contiguous()
+        self.offset += 3
+        off_noise, off1, off2 = self.offset - 2, self.offset - 1, self.offset
+        _, noise, keep1 = core.prep_input_csr(self.lib, batch, ts, spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"], p,
+                                              training, self.seed, off1, m.emb_layer, self.E, bufs.xin1, bufs.temb, bufs.x0bits, st)
+        _, _, keep2 = core.onehot_prep_input_csr(self.lib, batch, ts_U, spec["discrete"], s8, self.seed, off_noise, ts,
+                                                 spec["drop_mask_U"], p, training, off2, m.emb_layer, self.E, bufs.xin2,
+                                                 bufs.temb, st)
+        return None, bufs.x0bits, None, bufs.rowdiv_mse, (batch, s8, ts_U, noise, keep1, keep2)
+
     def _loss_layer(self, spec, bufs, B, A, W, bias, N, K, target, alpha, rowdiv):
         """Last product fused with the per-row loss, then the float64 loss tail (weights, history FIFO, 1/pt)."""
         lib, st = self.lib, _lib.stream_ptr()
-        core.loss_layer(lib, bufs, A, W, bias, target, alpha, B, N, K, st)
+        if spec.get("csr") is not None:  # the target rows are the bitmaps the CSR-fed builder wrote
+            core.loss_layer_bits(lib, bufs, A, W, bias, target, alpha, B, N, K, st)
+        else:
+            core.loss_layer(lib, bufs, A, W, bias, target, alpha, B, N, K, st)
         return core.loss_tail(lib, bufs, spec, B, rowdiv, alpha, st)
 
     def _train_forward(self, spec):
-        B, dev = spec["x_start"].shape[0], spec["x_start"].device
+        B, dev = self._batch_of(spec)
         br1, br2, out = self._chains()
         bufs = self.buffers(B, dev)
         self.version += 1

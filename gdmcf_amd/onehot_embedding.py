@@ -93,7 +93,7 @@ class OneHotEmbeddingEngine(OneHotEngine):
         return index
 
     def _train_forward(self, spec):
-        B, dev = spec["x_start"].shape[0], spec["x_start"].device
+        B, dev = self._batch_of(spec)
         br1, br2, out = self._chains()
         bufs = self.buffers(B, dev)
         self.version += 1

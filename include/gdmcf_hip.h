@@ -130,6 +130,24 @@ int gdmcf_dnn_prep_input_csr_f32(const int64_t* indptr, const int32_t* indices, 
 int gdmcf_onehot_noise_f32(const float* x0, int64_t ldx, const int64_t* ts, int B, int I, float discrete,
                            const uint8_t* sampled, int64_t lds, uint64_t seed, uint64_t offset,
                            float* xU, int64_t ldu, uint8_t* sampled_out, int64_t ldso, void* stream);
+/* The second branch's first-layer input straight from device CSR rows: replaces, for training on rows that stay sparse,
+ * the same reference lines as gdmcf_onehot_noise_f32 (gaussian_diffusion.py:841-849, :770-831, models/DNN.py:444) together
+ * with the input builder of branch 2 (models/DNN.py:446-455: dropout, timestep embedding, cat) -- in ONE launch, for row b =
+ * row rows[b] of the {0,1} matrix (indptr int64, indices int32):
+ *   xin[b, :] = [ drop( xU[b, 0:2I] ) | emb_w @ temb(ts[b]) + emb_b (E columns) | 1 | 0 up to ldxin ]
+ * with xU as defined above, i.e. exactly what gdmcf_onehot_noise_f32 followed by gdmcf_dnn_prep_input_f32(I = 2I, ca = cb = NULL,
+ * normalize = 0) leave in xin -- bit for bit, for equal inputs, seed and offsets -- without xU and without any dense row.
+ * Class draws: `sampled` given (ts_U may be NULL), or drawn with the counters of gdmcf_onehot_noise_f32 (stream 3) at
+ * offset_noise from a = (float)ts_U[b]/B; sampled_out (optional, uint8 [B, ldso]) receives them.  Dropout over the 2I columns:
+ * drop_mode / keep / drop_p as gdmcf_dnn_prep_input_f32 (stream 1) at offset_prep.  ts: the timesteps of the embedding
+ * columns; temb_out as there.  bits_out (optional): the rows as bitmaps, as gdmcf_dnn_prep_input_csr_f32 writes them.
+ * Both offsets are by-value: the entry refuses to run while a graph step state is bound (gdmcf_graph_state_bind).            */
+int gdmcf_onehot_prep_input_csr_f32(const int64_t* indptr, const int32_t* indices, const int64_t* rows, const int64_t* ts_U,
+                                    float discrete, const uint8_t* sampled, int64_t lds, uint64_t seed, uint64_t offset_noise,
+                                    uint8_t* sampled_out, int64_t ldso, const int64_t* ts, int drop_mode, const uint8_t* keep,
+                                    int64_t ldkeep, float drop_p, uint64_t offset_prep, const float* emb_w, const float* emb_b,
+                                    int E, int B, int I, float* xin, int64_t ldxin, float* temb_out, uint32_t* bits_out,
+                                    int64_t ldbits, void* stream);
 
 /* ---- N(0,1) fill --------------------------------------------------------------------------------
  * replaces `noise = th.randn_like(x_start)` where the noise itself is needed in memory: the eps TARGET of
