@@ -107,6 +107,12 @@ def main():
         model.load_lightgcn_embeddings(lg)
         say(f"LightGCN: {args.lightgcn_init} BPR steps in {time.perf_counter() - t0:.2f} s (last mf loss {float(mf.detach()):.4f}); "
             f"tables handed to {type(model).__name__}", flush=True)
+        # what the graph model itself recommends: propagated tables ranked on the device (fused score product + masked top-k)
+        from gdmcf_amd.lightgcn import get_metrics
+        with torch.no_grad():
+            lg_u, lg_i, _, _ = lg.propagate_through_layers()
+        lg_recall, _, lg_ndcg, _ = get_metrics(lg_u, lg_i, U, I, train, test, 20)
+        say(f"LightGCN: Recall@20 {lg_recall:.4f} NDCG@20 {lg_ndcg:.4f} on the test split (get_metrics)", flush=True)
     opt = gdmcf_amd.FusedAdamW(model.parameters(), lr=args.lr, weight_decay=0.0)
     gen = torch.Generator().manual_seed(0)
     from gdmcf_amd.parallel import DataParallelStep

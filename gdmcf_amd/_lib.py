@@ -100,6 +100,8 @@ _SIGNATURES = {
     "gdmcf_onehot_prep_input_csr_f32": (c_int, [P, P, P, P, c_float, P, c_int64, c_uint64, c_uint64, P, c_int64, P, c_int, P,
                                                 c_int64, c_float, c_uint64, P, P, c_int, c_int, c_int, P, c_int64, P, P,
                                                 c_int64, P]),
+    "gdmcf_score_topk_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gdmcf_score_topk_f32": (c_int, [P, c_int64, P, c_int, P, c_int64, c_int, c_int, P, P, c_int, P, P, P, c_size_t, P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

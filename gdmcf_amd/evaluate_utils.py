@@ -35,6 +35,55 @@ def masked_topk(prediction, k, mask_indptr=None, mask_indices=None, return_value
     return (val, idx) if return_values else idx
 
 
+def score_topk(user_emb, item_emb, k, mask_indptr=None, mask_indices=None, user_ids=None, return_values=False, check_ids=True):
+    """masked_topk(user_emb[user_ids] @ item_emb.T, k, mask_indptr, mask_indices) without the score matrix (reference
+    lightGCN.py:75-90: the product, the dense -inf mask of the training interactions and torch.topk): one fused kernel,
+    gdmcf_score_topk_f32, keeps the scores on chip.
+
+    user_emb float32 [U, d], item_emb float32 [I, d] on the GPU; `user_ids` (int64, optional) picks the rows of user_emb,
+    otherwise every row is ranked.  The CSR mask has one row per RANKED row (`mask_indptr` int64 [n_rows + 1], `mask_indices`
+    int32 item ids).  Same return convention, tie rule (lowest item index first) and degenerate-row convention (masked
+    items count as -inf) as masked_topk.  `check_ids=False` skips the range check of `user_ids` (a device-to-host
+    synchronisation): for callers that built the ids on the host and know them to lie in [0, U)."""
+    _lib.require_gpu(user_emb, "user embeddings")
+    _lib.require_gpu(item_emb, "item embeddings")
+    for t, what in ((mask_indptr, "mask_indptr"), (mask_indices, "mask_indices"), (user_ids, "user_ids")):
+        if t is not None:
+            _lib.require_gpu(t, what)
+    lib = _lib.load()
+    prep = lambda t: t if (t.dtype == torch.float32 and t.stride(-1) == 1) else t.float().contiguous()
+    ue, ie = prep(user_emb.detach()), prep(item_emb.detach())
+    assert ue.dim() == 2 and ie.dim() == 2 and ue.shape[1] == ie.shape[1], "user_emb [U, d] and item_emb [I, d] must share d"
+    dev = ue.device
+    I, d = ie.shape
+    ids = None
+    if user_ids is not None:
+        ids = user_ids.to(device=dev, dtype=torch.int64).contiguous()
+        if check_ids and ids.numel():
+            lo, hi = torch.aminmax(ids)  # (one synchronising copy)
+            lo, hi = torch.stack((lo, hi)).tolist()
+            if not (0 <= lo and hi < ue.shape[0]):
+                raise IndexError("score_topk: user_ids out of range")
+    n_rows = ids.numel() if ids is not None else ue.shape[0]
+    if not 1 <= k <= I:
+        raise AssertionError("selected index k out of range")
+    ip = ix = None
+    if mask_indptr is not None:
+        ip = mask_indptr.to(device=dev, dtype=torch.int64).contiguous()
+        ix = mask_indices.to(device=dev, dtype=torch.int32).contiguous()
+        assert ip.numel() == n_rows + 1, "mask_indptr must have one entry per ranked row plus one"
+    idx = torch.empty(n_rows, k, dtype=torch.int64, device=dev)
+    val = torch.empty(n_rows, k, dtype=torch.float32, device=dev) if return_values else None
+    if n_rows == 0:
+        return (val, idx) if return_values else idx
+    nbytes = int(lib.gdmcf_score_topk_ws_bytes(n_rows, I, d, k))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    _lib.check(lib.gdmcf_score_topk_f32(ue.data_ptr(), ue.stride(0), _lib.ptr(ids), n_rows, ie.data_ptr(), ie.stride(0), I, d,
+                                        _lib.ptr(ip), _lib.ptr(ix), k, idx.data_ptr(), _lib.ptr(val), _lib.ptr(ws), nbytes,
+                                        _lib.stream_ptr()))
+    return (val, idx) if return_values else idx
+
+
 def csr_rows_to_device(csr, rows, device):
     """(indptr int64, indices int32) device tensors for `csr[rows]` (a scipy CSR history matrix)."""
     sub = csr[rows]

@@ -526,6 +526,87 @@ class LightGCN(nn.Module):
         return fu[users], fi[pos_items], fi[neg_items], iu[users], ii[pos_items], ii[neg_items]
 
 
+    @torch.no_grad()
+    def recommend(self, users, k, history=None):
+        """The k best items of `users` (int64 ids, any device / array) by the propagated embeddings, best first: int64
+        [len(users), k] on the GPU.  `history` (scipy CSR or data_utils.DeviceCSR, one row per user of the MODEL): the
+        interactions of the asked users are excluded, as the reference's get_metrics excludes the training set
+        (lightGCN.py:77-86).  One propagation + evaluate_utils.score_topk: no [users, items] score matrix."""
+        from .evaluate_utils import score_topk
+        fu, fi, _, _ = self.propagate_through_layers()
+        ids = torch.as_tensor(np.asarray(users.cpu() if torch.is_tensor(users) else users), dtype=torch.int64)
+        if ids.numel() and not (0 <= int(ids.min()) and int(ids.max()) < self.n_users):  # (on the host: no device sync)
+            raise IndexError("recommend: user ids out of range")
+        ids = ids.to(fu.device)
+        ip, ix = _history_rows(history, ids)
+        return score_topk(fu, fi, k, ip, ix, user_ids=ids, check_ids=False)
+
+
+def _history_rows(history, ids):
+    """(indptr int64, indices int32) on ids' device: the rows `ids` of `history` (scipy CSR or DeviceCSR), or (None, None)."""
+    if history is None:
+        return None, None
+    from .data_utils import DeviceCSR
+    if isinstance(history, DeviceCSR):
+        hp = history.indptr.to(ids.device)
+        beg, end = hp[ids], hp[ids + 1]
+        ln = end - beg
+        ip = torch.zeros(ids.numel() + 1, dtype=torch.int64, device=ids.device)
+        torch.cumsum(ln, 0, out=ip[1:])
+        pos = torch.arange(int(ip[-1]), device=ids.device) - torch.repeat_interleave(ip[:-1] - beg, ln)
+        return ip, history.indices.to(ids.device)[pos].to(torch.int32)
+    sub = sp.csr_matrix(history)[ids.cpu().numpy()]
+    return (torch.from_numpy(sub.indptr.astype(np.int64)).to(ids.device),
+            torch.from_numpy(sub.indices.astype(np.int32)).to(ids.device))
+
+
+def ranking_terms(hit, n_gt):
+    """Per-user (recall, precision, ndcg, map) terms of the reference's get_metrics (lightGCN.py:98-125) from the hit matrix
+    `hit` [U, K] (hit[u, j] = the j-th recommendation of u is a test item) and the users' test-set sizes `n_gt` [U] (> 0):
+    float64 tensors on hit's device (any device: this is the arithmetic get_metrics runs on the GPU)."""
+    hit = hit.to(torch.float64)
+    n_gt = n_gt.to(torch.float64)
+    K = hit.shape[1]
+    j = torch.arange(K, device=hit.device, dtype=torch.float64)
+    gain = 1.0 / torch.log(j + 2.0)
+    recall = hit.sum(1) / n_gt
+    precision = hit.sum(1) / K
+    idcg = ((j[None, :] < torch.clamp(n_gt, max=K)[:, None]).to(torch.float64) * gain).sum(1)
+    ndcg = (hit * gain).sum(1) / idcg
+    ap = (hit * torch.cumsum(hit, 1) / (j + 1.0)).sum(1) / n_gt
+    return recall, precision, ndcg, ap
+
+
+def get_metrics(user_emb, item_emb, n_users, n_items, train_csr, test_csr, K):
+    """(recall, precision, ndcg, map) @K of reference lightGCN.py:67-127 from the final embeddings: the users with at least
+    one test interaction are ranked over all items but their training ones (`train_csr`, `test_csr`: scipy CSR [n_users,
+    n_items]), each metric is the plain mean over those users.  Ranking by the fused gdmcf_score_topk_f32 (no score matrix, no
+    dense mask); the hit matrix and the per-user terms are float64 on the device, the ranked lists never reach the host."""
+    from .evaluate_utils import score_topk
+    _lib.require_gpu(user_emb, "user embeddings")
+    _lib.require_gpu(item_emb, "item embeddings")
+    dev = user_emb.device
+    test = sp.csr_matrix(test_csr).astype(np.float32)
+    test.sum_duplicates()
+    test.sort_indices()
+    assert test.shape == (n_users, n_items) and user_emb.shape[0] == n_users and item_emb.shape[0] == n_items
+    users = np.nonzero(np.diff(test.indptr) > 0)[0].astype(np.int64)
+    if len(users) == 0:
+        raise ValueError("get_metrics: no user has a test interaction")
+    ids = torch.from_numpy(users).to(dev)
+    ip, ix = _history_rows(train_csr, ids)
+    top = score_topk(user_emb, item_emb, K, ip, ix, user_ids=ids, check_ids=False)  # [U_test, K]; ids: rows of test_csr
+    gt = test[users]
+    n_gt = torch.from_numpy(np.diff(gt.indptr).astype(np.int64)).to(dev)
+    # membership: (row, item) keys of the ground truth are sorted (CSR order), the recommendations are looked up in them
+    rows = np.repeat(np.arange(len(users), dtype=np.int64), np.diff(gt.indptr))
+    gkeys = torch.from_numpy(rows * n_items + gt.indices.astype(np.int64)).to(dev)
+    pkeys = torch.arange(len(users), device=dev, dtype=torch.int64)[:, None] * n_items + top
+    pos = torch.searchsorted(gkeys, pkeys.reshape(-1)).clamp_(max=gkeys.numel() - 1)
+    hit = (gkeys[pos] == pkeys.reshape(-1)).reshape(pkeys.shape)
+    return tuple(float(t.mean()) for t in ranking_terms(hit, n_gt))
+
+
 class _PropagateMean(torch.autograd.Function):
     """mean over layers of A~^l E0.  d(mean)/d(E0) applied to a cotangent G is mean_l (A~^l)^T G = mean_l A~^l G
     because the normalised adjacency is symmetric (reference lightGCN.py:149-164): the backward pass is the

@@ -51,7 +51,8 @@ int gdmcf_debug_last_gemm(void);
  * calls; gdmcf_prof_collect synchronises them and returns (tag, milliseconds, work) triples,
  * where work = algorithmic FLOPs (GEMM tags) or bytes (HBM-bound tags) of that launch.
  * Tags: 1 linear_fwd gemm, 2 loss_fwd gemm, 3 posterior gemm, 4 bwd_input gemm, 5 bwd_weight gemm,
- * 6 adamw (also normalize_rows_bwd_adamw / scatter_rows_adamw), 7 prep_input, 8 spmm, 9 topk.
+ * 6 adamw (also normalize_rows_bwd_adamw / scatter_rows_adamw), 7 prep_input, 8 spmm, 9 topk, 12 score_topk (work = the
+ * 2 n_rows n_items d FLOPs of the score product).
  * on: 1 = record, 2 = pause (stop recording, keep the records), 0 = off and discard.           */
 int gdmcf_prof_enable(int on);
 int gdmcf_prof_collect(int cap, int* tags_host, float* ms_host, double* work_host);
@@ -434,6 +435,22 @@ int gdmcf_adamw_bf16s_f32(const int64_t* table, const int64_t* shadow_table, int
 int gdmcf_topk_masked_f32(const float* pred, int64_t ldp, int B, int I, const int64_t* mask_indptr,
                           const int32_t* mask_indices, int k, int64_t* idx_out, float* val_out,
                           void* stream);
+
+/* ---- LightGCN ranking: score product fused with the masked top-k (lightGCN.py:67-127, get_metrics) -----------
+ * replaces `relevance_score = user_emb @ item_emb.T`, the dense -inf mask of the training interactions added to it and
+ * `torch.topk(relevance_score, K)` (lightGCN.py:75-90) without the [n_rows, n_items] score matrix (nor the mask) ever being
+ * stored: row r's scores dot(user_emb[user_ids[r]], item_emb[i]) (float32, v_mfma_f32_16x16x4_f32) are selected from while
+ * they are MFMA accumulators.  out_idx [n_rows, k] / out_val [n_rows, k] (optional) are exactly what gdmcf_topk_masked_f32
+ * returns for the materialised matrix: descending score, equal scores in ascending item index, the items of row r's mask
+ * (CSR over the n_rows rows of the CALL: mask_indptr int64 [n_rows+1], mask_indices int32; NULL = none) count as -inf, so
+ * they appear -- lowest index first, value -inf -- only when fewer than k items are unmasked.  user_ids NULL = rows
+ * 0..n_rows-1 of user_emb.  Any n_rows, n_items, 1 <= d <= 4096, 1 <= k <= min(n_items, 1024).  Deterministic (same bits
+ * from run to run).  ws: gdmcf_score_topk_ws_bytes bytes (k candidates per row and item slab when few rows are asked for; 0
+ * when the row tiles fill the chip; never more than 5 % of 4 n_rows n_items).                                            */
+size_t gdmcf_score_topk_ws_bytes(int n_rows, int n_items, int d, int k);
+int gdmcf_score_topk_f32(const float* user_emb, int64_t ldu, const int64_t* user_ids, int n_rows, const float* item_emb,
+                         int64_t ldi, int n_items, int d, const int64_t* mask_indptr, const int32_t* mask_indices, int k,
+                         int64_t* out_idx, float* out_val, void* ws, size_t ws_bytes, void* stream);
 
 /* Ranking metrics of reference evaluate_utils.py:6-52 (computeTopNAccuracy) on the device: per user and per cut-off
  * N of topN_host (ascending, at most 8) the four terms precision = hits/N, recall = hits/|GT|, NDCG = dcg/idcg,
