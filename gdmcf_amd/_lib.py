@@ -102,6 +102,9 @@ _SIGNATURES = {
                                                 c_int64, P]),
     "gdmcf_score_topk_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "gdmcf_score_topk_f32": (c_int, [P, c_int64, P, c_int, P, c_int64, c_int, c_int, P, P, c_int, P, P, P, c_size_t, P]),
+    "gdmcf_bpr_sample_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_uint64, c_uint64, P, P, P, P]),
+    "gdmcf_bpr_loss_f32": (c_int, [P, c_int64, P, c_int64, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P]),
+    "gdmcf_bpr_grad_f32": (c_int, [c_int, P, P, P, P, c_int, c_int, c_int, P, P, c_int64, c_int, P, c_int64, c_float, P, c_int64, P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -53,6 +53,25 @@ struct GdProfScope {
 static inline int gd_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool gd_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ---- Philox4x32-10 (kernels_misc.hip, bpr.hip) ------------------------------------------------------------
+// Counter-based: any element can be regenerated in any kernel, so noise and dropout masks never have to be stored.  Counter
+// word z is the STREAM id: 0-6 are the draws of kernels_misc.hip, 7 is the BPR triple sampler (bpr.hip).
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
+    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        // (one 32 x 32 -> 64 product per word pair: v_mad_u64_u32 where hipcc picks it -- half the quarter-rate multiplies of a
+        // v_mul_lo_u32 / v_mul_hi_u32 pair)
+        const uint64_t p0 = (uint64_t)M0 * (uint64_t)c.x, p1 = (uint64_t)M1 * (uint64_t)c.z;
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
+        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
+        k.x += W0;
+        k.y += W1;
+    }
+    return c;
+}
+
 // ---- bf16 shadow registry (capi.hip) ----------------------------------------------------------------------
 struct GdShadow {
     void* p16;

@@ -10,25 +10,7 @@
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------
-// Philox4x32-10 (counter-based: any element can be regenerated in any kernel, so noise and
-// dropout masks never have to be stored).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        // (one 32 x 32 -> 64 product per word pair: v_mad_u64_u32 where hipcc picks it -- half the quarter-rate multiplies of a
-        // v_mul_lo_u32 / v_mul_hi_u32 pair)
-        const uint64_t p0 = (uint64_t)M0 * (uint64_t)c.x, p1 = (uint64_t)M1 * (uint64_t)c.z;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += W0;
-        k.y += W1;
-    }
-    return c;
-}
+// (Philox4x32-10, the generator of every draw below: common.h)
 
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
     const float u1 = ((float)a + 1.0f) * 2.3283064365386963e-10f;  // (0,1]

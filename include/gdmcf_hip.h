@@ -535,6 +535,44 @@ int gdmcf_graph_state_tick(void* state_dev, void* stream);
 /* out = acc * scale */
 int gdmcf_scale_f32(const float* acc, int64_t n, float scale, float* out, void* stream);
 
+/* ---- LightGCN BPR training step (lightGCN.py:207-251, :287-300; csrc/bpr.hip) -------------------------------------------
+ * Notation: M [N, d] the propagated mean table, E0 [N, d] the parameter, N = n_users + n_items, item i = node n_users + i,
+ * B triples (users[j], pos[j], neg[j]) of int64 ids (pos / neg are ITEM ids), x_j = <M[u_j], M[neg_j]> - <M[u_j], M[pos_j]>.
+ * No float atomics anywhere: same inputs, same bits.
+ *
+ * gdmcf_bpr_sample_f32 replaces the reference's per-user `random.choice(x)` / `sample_neg(x)` (lightGCN.py:225-229,
+ * :244-246): for each users[j] one interacted and one non-interacted item of the training CSR (indptr int64 [n_users+1],
+ * indices int32, every row sorted and free of duplicates), one thread per triple, Philox4x32-10 with counter
+ * (j, 0, 7, (uint32)offset) and key seed -- stream id 7.  pos[j] is uniform over the row; neg[j] is uniform over the
+ * n_items - deg items NOT in the row, drawn exactly (no rejection loop): r uniform in [0, n_items - deg), i = the smallest
+ * index with row[i] - i > r (binary search; i = deg when there is none), neg = r + i -- the distribution of sample_neg.
+ * Integers come from 32-bit words by multiply-high, floor(w n / 2^32): the bias of any outcome is at most n / 2^32.
+ * A user outside [0, n_users), or with deg == 0 or deg == n_items, gets pos = neg = -1 and *flag (int32, optional) = 1.   */
+int gdmcf_bpr_sample_f32(const int64_t* indptr, const int32_t* indices, const int64_t* users, int B, int n_users, int n_items,
+                         uint64_t seed, uint64_t offset, int64_t* pos, int64_t* neg, int32_t* flag, void* stream);
+/* gdmcf_bpr_loss_f32 replaces the six row gathers of LightGCN.forward (lightGCN.py:200-201) and bpr_loss (:207-219):
+ *   coef[j] = sigmoid(x_j) / B           the derivative of mean_j softplus(x_j) (torch's softplus: linear above 20)
+ *   *mf     = mean_j softplus(x_j)
+ *   *reg    = 0.5 (sum_j |E0[u_j]|^2 + |E0[pos_j]|^2 + |E0[neg_j]|^2) / B
+ * One lane group per triple (16 lanes x float4 at d = 64), then ONE fixed-order reduction of the per-triple partials in
+ * ws (float [2 B]).  Any d >= 1 (float4 loads when d % 4 == 0 and the rows are 16-byte aligned).  A triple with an id out
+ * of range contributes nothing, gets coef 0 and sets *flag (int32, optional) = 1.                                        */
+int gdmcf_bpr_loss_f32(const float* M, int64_t ldm, const float* E0, int64_t lde, int d, const int64_t* users, const int64_t* pos,
+                       const int64_t* neg, int B, int n_users, int n_items, float* coef, float* ws, float* mf, float* reg,
+                       int32_t* flag, void* stream);
+/* gdmcf_bpr_grad_f32 replaces what autograd runs behind `final_loss.backward()` (lightGCN.py:299) up to the propagation:
+ * the six index_put_(accumulate) scatters into zeroed tables.  Entry e in [0, 3 B) of the batch is (role e / B: 0 user,
+ * 1 pos, 2 neg; triple e % B); order int32 [3 B] lists the entries sorted by node, entries of one node in ascending e.
+ * One lane group per entry; the first entry of a node's run walks the run and is the row's only writer.
+ *   mode 0: out[node] = sum over the run of  user: coef_j (src[neg_j] - src[pos_j]),  pos: -coef_j src[u_j],
+ *           neg: +coef_j src[u_j]   with src = M: the cotangent of the propagated table.  Rows of no entry are not written.
+ *   mode 1: out[node] += scale * (entries in the run) * src[node]   with src = E0, scale = decay / B: the regulariser's
+ *           gradient, added to the propagated cotangent; zero_rows (optional, [N, ld_zero]): row node of it is cleared
+ *           in the same pass (a persistent cotangent table is all zero again afterwards).                                 */
+int gdmcf_bpr_grad_f32(int mode, const int32_t* order, const int64_t* users, const int64_t* pos, const int64_t* neg, int B,
+                       int n_users, int n_items, const float* coef, const float* src, int64_t ld_src, int d, float* out,
+                       int64_t ld_out, float scale, float* zero_rows, int64_t ld_zero, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
