@@ -105,6 +105,11 @@ _SIGNATURES = {
     "gdmcf_bpr_sample_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_uint64, c_uint64, P, P, P, P]),
     "gdmcf_bpr_loss_f32": (c_int, [P, c_int64, P, c_int64, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P]),
     "gdmcf_bpr_grad_f32": (c_int, [c_int, P, P, P, P, c_int, c_int, c_int, P, P, c_int64, c_int, P, c_int64, c_float, P, c_int64, P]),
+    "gdmcf_cat_prep_input_f32": (c_int, [P, c_int64, P, c_int64, P, P, P, c_int, P, c_int64, c_int, P, c_int64, c_float, c_uint64,
+                                         c_uint64, P, P, P, P, c_int, c_int, c_int, P, c_int64, P, c_int64, P, P]),
+    "gdmcf_cat_grad_ws_bytes": (c_size_t, [c_int, c_int]),
+    "gdmcf_cat_grad_f32": (c_int, [P, c_int64, P, c_int64, P, c_int64, c_int, P, c_int64, c_float, c_uint64, c_uint64, c_int, c_int,
+                                   P, c_size_t, P, P, P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,0 +1,194 @@
+"""Backbone `DNNCat` (reference models/DNN.py:180-265) on the HIP path: the plain `DNN` with one learnable layer in front,
+`cat_layer = Linear(3, 1)`, which mixes per user x item the noised value x_t[b,i] with the item's two one-hot columns
+x_U[b,i,0:2] into one scalar; dropout, the time embedding and the MLP follow unchanged.  It is driven by
+`GaussianDiffusionDiscrete(CatOneHot=True)` with `indexIn` off, like `DNNOneHot`, and reads the same [B, 2I] one-hot image
+(`gdmcf_onehot_noise_f32`).
+
+Downstream of the mix this is `DenoiserEngine`'s layer chain.  Two things differ (csrc/cat.hip):
+  * the input step: `gdmcf_cat_prep_input_f32` forms x_t, the mix and the dropout in one pass and writes the first layer's input
+    and x_t -- no [B, I, 3] tensor, no element-wise passes in front of the first GEMM;
+  * the tail of the backward pass: the first layer's input is a function of parameters, so dxin = dZ1 . W1[:, 0:I]
+    (`gdmcf_linear_bwd_input_f32` on the first I columns of W1, its leading dimension) and `gdmcf_cat_grad_f32`, which reduces
+    it to cat_layer's four gradients.  The keep-mask is recomputed there from the builder's Philox position, not stored.
+
+Not built (each raises NotImplementedError): `norm=True`, GEMM inputs other than f32, AdamW fused into the backward pass
+(dxin reads W1: the first layer's update must not run before it), the graphed step, CSR-fed rows (densified by
+`training_losses`), data parallel.  Constructor, parameter names and initialisation draw order are the reference's, so
+checkpoints interchange.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import engine_core as core
+from .engine import DenoiserEngine
+from .engine_core import with_precision
+from .onehot import OneHotEngine
+
+
+class CatEngine(DenoiserEngine):
+    supports_grad_sink = False  # (data parallel is not extended to this backbone)
+
+    onehot_rows = OneHotEngine.onehot_rows  # x_tU as the [B, 2I] float image (gdmcf_onehot_noise_f32)
+    _last_layer = OneHotEngine._last_layer  # output layer, plain or with the posterior mean in its epilogue
+
+    def buffers(self, B, device):
+        b = super().buffers(B, device)
+        if getattr(b, "dxin", None) is None:
+            f32 = dict(dtype=torch.float32, device=device)
+            b.xU = torch.zeros(B, 2 * self.I, **f32)
+            b.xt = torch.zeros(B, b.ldi, **f32)  # x_t: eps target, posterior, and the backward pass's first sum
+            b.dxin = torch.zeros(B, b.ldi, **f32)
+            b.cat_ws_bytes = int(self.lib.gdmcf_cat_grad_ws_bytes(B, self.I))
+            b.cat_ws = torch.empty(max(b.cat_ws_bytes, 256), dtype=torch.uint8, device=device)
+            self._grow_workspace(b, B, device, [(self.model.in_layers[0].weight.shape[0], self.I)])  # the dxin product
+        return b
+
+    # -- input step -----------------------------------------------------------------------------------------------------
+    def _cat_input(self, bufs, x, xU, ts, ca, cb, noise, drop_mask, training):
+        """gdmcf_cat_prep_input_f32 at the next Philox position: bufs.xin = [ drop(cat_layer(x_t, xU)) | emb(t) | 1 | 0-pad ],
+        bufs.xt = x_t.  Remembers the dropout's (mode, mask, p, position) for the backward pass; returns what the kernel
+        reads, to keep referenced."""
+        m = self.model
+        B = x.shape[0]
+        x = core._f32_rows(x)
+        p = float(m.drop.p)
+        noise_mode, noise, drop_mode, keep = core._prep_modes(B, ca, noise, drop_mask, p, training)
+        (nz, ldn), (kp, ldkp) = core._pl(noise), core._pl(keep)
+        cw, cb_ = m.cat_layer.weight, m.cat_layer.bias
+        _lib.require_gpu(cw, "DNNCat parameters")
+        if not (cw.is_contiguous() and cb_.is_contiguous() and cw.dtype == torch.float32):
+            raise RuntimeError("gdmcf_amd: DNNCat parameters must be contiguous float32")
+        self.offset += 1
+        _lib.check(self.lib.gdmcf_cat_prep_input_f32(
+            x.data_ptr(), x.stride(0), xU.data_ptr(), xU.stride(0), ts.data_ptr(), _lib.ptr(ca), _lib.ptr(cb), noise_mode, nz,
+            ldn, drop_mode, kp, ldkp, p, self.seed, self.offset, cw.data_ptr(), cb_.data_ptr(), m.emb_layer.weight.data_ptr(),
+            m.emb_layer.bias.data_ptr(), self.E, B, self.I, bufs.xin.data_ptr(), bufs.xin.stride(0), bufs.xt.data_ptr(),
+            bufs.xt.stride(0), bufs.temb.data_ptr(), _lib.stream_ptr()))
+        bufs.xin_ones = True
+        self._drop = (drop_mode, keep, p, self.offset)
+        return x, noise, keep, xU
+
+    def _train_input(self, bufs, spec, xt_out):
+        x0 = core._f32_rows(spec["x_start"])
+        _, s8 = self.onehot_rows(x0, spec["ts_U"], spec["sampled"], spec["discrete"], out=bufs.xU)
+        return self._cat_input(bufs, x0, bufs.xU, spec["ts"], spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"],
+                               self.model.training) + (s8,)
+
+    # -- backward: the plain chain, then the cat layer ---------------------------------------------------------------------
+    def _backward(self, sv, dz_last, rowscale):
+        """Gradients in model.parameters() order: emb_layer (w, b), cat_layer (w, b), in_layers..., out_layers..."""
+        if self.fused_opt is not None or self.grad_sink is not None:
+            raise NotImplementedError("gdmcf_amd.DNNCat: no optimiser inside the backward pass and no gradient sink (the "
+                                      "input gradient of the first layer reads its weight)")
+        out = super()._backward(sv, dz_last, rowscale)
+        bufs, layers, B = sv["bufs"], sv["layers"], sv["B"]
+        m, st = self.model, _lib.stream_ptr()
+        w1 = layers[0][0]
+        # dxin = dZ1 . W1[:, 0:I]: bufs.dzs[0] is still d(loss)/d(first pre-activation), W1 is not updated before step()
+        core.linear_bwd_input(self.lib, bufs, bufs.dzs[0], w1, None, None, 0, B, w1.shape[0], self.I, bufs.dxin, st)
+        gw, gb = self._grad_like(m.cat_layer.weight), self._grad_like(m.cat_layer.bias)
+        drop_mode, keep, p, offset = self._drop
+        (kp, ldkp) = core._pl(keep)
+        _lib.check(self.lib.gdmcf_cat_grad_f32(
+            bufs.dxin.data_ptr(), bufs.dxin.stride(0), bufs.xt.data_ptr(), bufs.xt.stride(0), bufs.xU.data_ptr(),
+            bufs.xU.stride(0), drop_mode, kp, ldkp, p, self.seed, offset, B, self.I, bufs.cat_ws.data_ptr(), bufs.cat_ws_bytes,
+            gw.data_ptr(), gb.data_ptr(), st))
+        return out[:2] + [gw, gb] + out[2:]
+
+    # -- plain forward (evaluation / reverse loop) --------------------------------------------------------------------------
+    @with_precision
+    def forward_plain(self, x, timesteps, x_U, training, drop_mask=None, posterior=None):
+        self.flush_weight_waiters()
+        B, dev = x.shape[0], x.device
+        layers = self._layers()
+        bufs = self.buffers(B, dev)
+        self._shadows_on(bufs, layers)
+        self.version += 1
+        self._saved = None
+        ts = timesteps.to(device=dev, dtype=torch.int64).contiguous()
+        xu = x_U.reshape(B, -1)
+        if xu.shape[1] != 2 * self.I:
+            raise RuntimeError("gdmcf_amd.DNNCat: x_U must hold two columns per item")
+        xu = core._f32_rows(xu)
+        keep = self._cat_input(bufs, x, xu, ts, None, None, None, drop_mask, training)
+        A = self._hidden_forward(bufs, layers, B)
+        w, bias, act = layers[-1]
+        res = self._last_layer(bufs, A, w, bias, act, B, w.shape[0], w.shape[1], keep[0], posterior)
+        del keep
+        return res
+
+
+class DNNCat(nn.Module):
+    """Drop-in for the reference DNNCat (models/DNN.py:180-265)."""
+
+    csr_rows = False  # training_losses densifies a CsrBatch for this backbone
+    fused_update_refusal = ("the input gradient of the first layer reads its weight, which a fused update would overwrite "
+                            "first; use the separate AdamW pass")
+
+    def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, cat_dim=2, gemm_dtype="f32"):
+        super().__init__()
+        if norm:
+            raise NotImplementedError("gdmcf_amd.DNNCat: norm=True needs a row norm between the mix and the dropout")
+        if gemm_dtype != "f32":
+            raise NotImplementedError("gdmcf_amd.DNNCat: GEMM inputs other than f32 (%s) are not built" % gemm_dtype)
+        if cat_dim != 2:
+            raise NotImplementedError("gdmcf_amd.DNNCat: the input kernel mixes x_t with one-hot PAIRS (cat_dim = 2)")
+        self.gemm_dtype = gemm_dtype
+        self.in_dims = list(in_dims)
+        self.out_dims = list(out_dims)
+        assert out_dims[0] == in_dims[-1], "In and out dimensions must equal to each other."
+        self.time_type = time_type
+        self.time_emb_dim = emb_size
+        self.norm = norm
+        self.emb_layer = nn.Linear(self.time_emb_dim, self.time_emb_dim)
+        self.cat_layer = nn.Linear(cat_dim + 1, 1)  # torch's default nn.Linear init, as in the reference
+        if self.time_type == "cat":
+            in_dims_temp = [self.in_dims[0] + self.time_emb_dim] + self.in_dims[1:]
+        else:
+            raise ValueError("Unimplemented timestep embedding type %s" % self.time_type)
+        out_dims_temp = self.out_dims
+        self.in_layers = nn.ModuleList([nn.Linear(a, b) for a, b in zip(in_dims_temp[:-1], in_dims_temp[1:])])
+        self.out_layers = nn.ModuleList([nn.Linear(a, b) for a, b in zip(out_dims_temp[:-1], out_dims_temp[1:])])
+        self.drop = nn.Dropout(dropout)  # holds p; the mask is applied inside the HIP input kernel
+        self.init_weights()
+        self._engine = None
+
+    def init_weights(self):
+        for layer in list(self.in_layers) + list(self.out_layers) + [self.emb_layer]:
+            fan_out, fan_in = layer.weight.size()
+            layer.weight.data.normal_(0.0, np.sqrt(2.0 / (fan_in + fan_out)))
+            layer.bias.data.normal_(0.0, 0.001)
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            self._engine = CatEngine(self)
+        return self._engine
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_engine"] = None
+        return state
+
+    def layer_list(self):
+        """[(weight, bias, act)] of the dense layers behind the cat layer; act 1 = tanh, 0 = none (reference :256-263)."""
+        layers = [(l.weight, l.bias, 1) for l in self.in_layers]
+        n_out = len(self.out_layers)
+        layers += [(l.weight, l.bias, 1 if i != n_out - 1 else 0) for i, l in enumerate(self.out_layers)]
+        return layers
+
+    def param_list(self):
+        return list(self.parameters())
+
+    def forward(self, x, timesteps, x_U, drop_mask=None, posterior=None):
+        """model(x_t, t, x_tU) of the reference's evaluation path; x_U is [B, I, 2] or [B, 2I].  Training goes through
+        GaussianDiffusionDiscrete.training_losses (fused forward + loss with its own backward); this plain forward carries
+        no autograd graph.  `posterior` (reverse loop, see OneHotEngine._last_layer): return (x_{t-1}, pred_xstart) with the
+        posterior mean fused into the output GEMM instead of the raw output."""
+        _lib.require_gpu(x, "DNNCat input")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and self.training:
+            raise RuntimeError("gdmcf_amd.DNNCat: the plain forward is not differentiable; train through "
+                               "GaussianDiffusionDiscrete.training_losses (or call under torch.no_grad())")
+        return self.engine.forward_plain(x, timesteps, x_U, self.training, drop_mask, posterior=posterior)

@@ -143,6 +143,12 @@ class DenoiserEngine(EngineBase):
             bufs.xin_ones = True  # (the builder leaves 1 in column I + E: the bias column of the first layer's weight gradient)
         return keepalive
 
+    def _train_input(self, bufs, spec, xt_out):
+        """The first layer's input of a training step on dense rows (a backbone with its own input step overrides this);
+        returns (x0, noise, ...) as the kernels read them, to keep referenced."""
+        return self._prep(bufs, spec["x_start"], spec["ts"], spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"],
+                          self.model.training, xt_out=xt_out)
+
     def _prep_csr(self, bufs, batch, ts, ca, cb, noise, drop_mask, training):
         """First-layer input straight from the device CSR rows of `batch` (data_utils.CsrBatch): no dense x0 anywhere; the
         rows' bitmaps go to bufs.x0bits for the loss epilogue."""
@@ -209,8 +215,7 @@ class DenoiserEngine(EngineBase):
         if csr is not None:
             keepalive = self._prep_csr(bufs, csr, ts, spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"], self.model.training)
         else:
-            keepalive = self._prep(bufs, x0, ts, spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"],
-                                   self.model.training, xt_out=xt_out)
+            keepalive = self._train_input(bufs, spec, xt_out)
         x0c = keepalive[0]
         alpha = None
         if eps_mode:

@@ -291,7 +291,7 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
     GCN backbones consume (`graph=` of DNNOneHotEmbeddingGCN), so with a `gdmcf_amd.DNN` model the result equals the
     continuous reverse loop of the parent class.
 
-    `CatOneHot=True` with a `gdmcf_amd.DNNOneHot` denoiser (`indexIn` False; SURVEY 8 f1, first slice): the rows are
+    `CatOneHot=True` with a `gdmcf_amd.DNNOneHot` or `gdmcf_amd.DNNCat` denoiser (`indexIn` False; SURVEY 8 f1, first slice): the rows are
     handed to the model a second time as one-hot pairs under the discrete transition noise of :770-831
     (`gdmcf_onehot_noise_f32`).  As in the reference, that noise uses its OWN timestep draw (:843) -- the model is
     conditioned on the second one (:865).  `indexIn = True` (set by main.py:241) selects the embedding backbone
@@ -337,14 +337,15 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         return torch.nn.functional.one_hot(sampled.long(), num_classes=2)
 
     def _onehot_model(self, model):
+        from .cat import DNNCat
         from .onehot import DNNOneHot
         from .onehot_embedding import DNNOneHotEmbedding
         if self.indexIn:  # main.py:239-242 sets it together with the embedding backbones
             if not isinstance(model, DNNOneHotEmbedding):
                 raise NotImplementedError("indexIn is built for gdmcf_amd.DNNOneHotEmbedding / DNNOneHotEmbeddingGCN only "
                                           "(the *_conti / *_time variants are not, SURVEY 8 f1)")
-        elif not isinstance(model, DNNOneHot) or isinstance(model, DNNOneHotEmbedding):
-            raise TypeError("gdmcf_amd.GaussianDiffusionDiscrete(CatOneHot=True) needs a gdmcf_amd.DNNOneHot denoiser "
+        elif not isinstance(model, (DNNOneHot, DNNCat)) or isinstance(model, DNNOneHotEmbedding):
+            raise TypeError("gdmcf_amd.GaussianDiffusionDiscrete(CatOneHot=True) needs a gdmcf_amd.DNNOneHot or DNNCat denoiser "
                             "(DNNOneHotEmbedding with indexIn = True)")
         return model
 
@@ -360,7 +361,8 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
             # rows left sparse: only what the CSR-fed kernels cover, otherwise densify here.  (rng == "torch"
             # draws the noise with torch.randn_like of the dense rows, unless the noise is given or there is none.)
             sparse_ok = (self.mean_type == ModelMeanType.START_X and not model.norm and x_start.csr.values is None
-                         and (self.rng == "philox" or noise is not None or self.noise_scale == 0.0))
+                         and (self.rng == "philox" or noise is not None or self.noise_scale == 0.0)
+                         and getattr(model, "csr_rows", True))  # (DNNCat: no CSR-fed input builder)
             if sparse_ok:
                 csr_batch = x_start
             else:

@@ -67,6 +67,9 @@ class FusedAdamW(torch.optim.Optimizer):
         32 floats (tools/ld_probe.py: the two Yelp products 0.291 -> 0.279 and 0.326 -> 0.285 ms).  Everything here takes
         leading dimensions, state_dict / load_state_dict / torch.save go through the view; what does need contiguous
         weights (this optimiser's separate pass, collectives) gets them back from unfuse() or another call of this method."""
+        why = getattr(model, "fused_update_refusal", None)
+        if why is not None and min_numel < (1 << 62):  # (unfuse() passes 1 << 62: nothing is taken over)
+            raise NotImplementedError(f"FusedAdamW.fuse_into_backward({type(model).__name__}): {why}")
         if align_rows is None:
             align_rows = os.environ.get("GDMCF_ALIGN_ROWS", "1") != "0"
         mine = {id(p) for g in self.param_groups for p in g["params"]}

@@ -573,6 +573,38 @@ int gdmcf_bpr_grad_f32(int mode, const int32_t* order, const int64_t* users, con
                        int n_users, int n_items, const float* coef, const float* src, int64_t ld_src, int d, float* out,
                        int64_t ld_out, float scale, float* zero_rows, int64_t ld_zero, void* stream);
 
+/* ---- DNNCat backbone: the cat layer in front of the plain DNN (models/DNN.py:180-265; csrc/cat.hip) ----------------------
+ * cat_w [3] / cat_b [1] are cat_layer's parameters IN DEVICE MEMORY (the optimiser moves them every step: no host read, no
+ * sync).  xU [B, ldu] is the one-hot image of gdmcf_onehot_noise_f32 (item i in columns 2i, 2i + 1).
+ *
+ * gdmcf_cat_prep_input_f32 replaces q_sample (gaussian_diffusion.py:399-407), `torch.cat([x.unsqueeze(-1), x_U], dim=2)`,
+ * `cat_layer(x).squeeze()`, `self.drop(x)` and `torch.cat([x, emb], dim=-1)` of DNNCat.forward (models/DNN.py:244-255; the
+ * timestep embedding of :245-246 through gdmcf_dnn_emb_cols_f32, launched from here) -- one pass over [B, I]:
+ *   x_t  = ca[ts[b]] x0 + cb[ts[b]] noise     as gdmcf_dnn_prep_input_f32 forms it, bit for bit (same noise_mode, Philox
+ *                                             counters and Box-Muller); ca == NULL: x_t = x0
+ *   z    = ((w0 x_t + w1 xU[b,2i]) + w2 xU[b,2i+1]) + c      float32, every operation rounded, no fused multiply-add
+ *   xin[b, 0:I] = dropout(z)                  drop_mode 0 none / 1 keep [B, ldkeep] uint8 / 2 Philox stream 1 with the plain
+ *                                             builder's counters; kept values times 1/(1-p)
+ *   xin[b, I:ldxin] = [ emb(t) | 1 | 0-pad ]  the layout of gdmcf_dnn_prep_input_f32;  temb_out [B, E] as there
+ *   xt_out[b, 0:I] = x_t                      all the backward pass keeps (the drawn keep-mask is recomputed there)
+ * E > 0; xin and xt_out 16-byte aligned with leading dimensions that are multiples of 4.                                  */
+int gdmcf_cat_prep_input_f32(const float* x, int64_t ldx, const float* xU, int64_t ldu, const int64_t* ts, const float* ca,
+                             const float* cb, int noise_mode, const float* noise, int64_t ldn, int drop_mode, const uint8_t* keep,
+                             int64_t ldkeep, float drop_p, uint64_t seed, uint64_t offset, const float* cat_w, const float* cat_b,
+                             const float* emb_w, const float* emb_b, int E, int B, int I, float* xin, int64_t ldxin, float* xt_out,
+                             int64_t ldxt, float* temb_out, void* stream);
+/* gdmcf_cat_grad_f32 replaces what autograd runs behind the dropout and cat_layer of models/DNN.py:248-253: with
+ * dxin [B, I] = dZ1 . W1[:, 0:I] (gdmcf_linear_bwd_input_f32 on the first I columns of the first layer's weight) and
+ * dz = dxin * keep / (1-p) -- drop_mode / keep / drop_p / seed / offset as given to gdmcf_cat_prep_input_f32 --
+ *   grad_w[0..2] = (sum dz x_t, sum dz xU[.,2i], sum dz xU[.,2i+1]),   grad_b[0] = sum dz        over all b, i.
+ * Two stages, no atomics (same inputs, same bits): float32 partials per workgroup of 4096 columns of a row (wave shuffles and
+ * one LDS exchange) in ws (gdmcf_cat_grad_ws_bytes(B, I) bytes, 16-byte aligned), then one workgroup adds the partials in
+ * index order in float64 and rounds once.  grad_w / grad_b are device pointers and are OVERWRITTEN.                        */
+size_t gdmcf_cat_grad_ws_bytes(int B, int I);
+int gdmcf_cat_grad_f32(const float* dxin, int64_t lddx, const float* xt, int64_t ldxt, const float* xU, int64_t ldu, int drop_mode,
+                       const uint8_t* keep, int64_t ldkeep, float drop_p, uint64_t seed, uint64_t offset, int B, int I, void* ws,
+                       size_t ws_bytes, float* grad_w, float* grad_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
