@@ -12,7 +12,7 @@
 // bits in every run whatever ids repeat.
 #include <math.h>
 
-#include "common.h"
+#include "draws.h"
 
 namespace {
 
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void bpr_sample_kernel(const int64_t* __restri
         if (flag) *flag = 1;
         return;
     }
-    const uint4 w = philox4x32_10(make_uint4((uint32_t)j, 0u, 7u, (uint32_t)offset), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+    const uint4 w = gd_philox_block((uint32_t)j, 0, GD_STREAM_BPR, offset, gd_philox_key(seed));
     const int32_t* __restrict__ row = indices + beg;
     pos[j] = row[bpr_mulhi(w.x, (uint32_t)deg)];
     // the r-th item (from 0) that is NOT in the sorted row: row[i] - i items are missing below row[i], so with i the first

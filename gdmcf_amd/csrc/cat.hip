@@ -10,35 +10,21 @@
 // Evaluation order of the mix (float32, every operation rounded, no fused multiply-add -- nn.Linear's left-to-right dot product
 // with the bias added last):
 //       t = w0 * x_t;   t = t + w1 * xU0;   t = t + w2 * xU1;   z = t + c
-// x_t itself is formed exactly as the plain builder forms it (kernels_misc.hip, xt4: two rounded products, one rounded sum; the
-// same Philox counters (col >> 2, b, 0, offset) and Box-Muller), the dropout draws are the plain builder's stream 1: one block
-// per PAIR of a thread's column groups, counter ((col of the even group) >> 2, b, 1, offset), 16 bits per element.
+// x_t and the dropout draws are the plain builder's (prep_input.hip) because both inline the same functions of draws.h:
+// gd_normal4 + gd_qsample for x_t, gd_drop_block + gd_drop_bits (one block per PAIR of a thread's column groups) for the keep-mask.
 //
 // The drawn keep-mask is never stored: the backward pass recomputes it from (seed, offset) -- gdmcf_cat_grad_f32 takes the same
 // drop_mode / keep / seed / offset as the builder.
 //
-// Mapping (both kernels): the plain builder's -- 256 threads, four columns per thread and group (one float4), CAT_G groups per
+// Mapping (both kernels): the plain builder's -- 256 threads, four columns per thread and group (one float4), CAT_G = PREP_G groups per
 // thread 1024 columns apart, a workgroup per 4096 columns of a row; a thread's four items are eight consecutive floats of xU.
 // No atomics: same inputs, same bits.
-#include <math.h>
-
-#include "common.h"
+#include "draws.h"
 
 namespace {
 
-constexpr int CAT_G = 4;
+constexpr int CAT_G = PREP_G;
 constexpr int CAT_SPAN = 256 * CAT_G * 4;  // columns of a row per workgroup
-
-typedef f32x4 f32x4_u4 __attribute__((aligned(4)));  // rows of a dense batch are only 4-byte aligned when I is odd
-
-// (as kernels_misc.hip: hardware transcendentals, the angle in revolutions)
-__device__ __forceinline__ void cat_box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = ((float)a + 1.0f) * 2.3283064365386963e-10f;  // (0,1]
-    const float u2 = (float)b * 2.3283064365386963e-10f;
-    const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));  // sqrt(-2 ln u1)
-    z0 = rad * __builtin_amdgcn_cosf(u2);
-    z1 = rad * __builtin_amdgcn_sinf(u2);
-}
 
 struct CatArgs {
     const float* x;  // x0 [B, ldx]
@@ -68,17 +54,6 @@ struct CatArgs {
     int64_t lddx;
 };
 
-// four consecutive values of a row from column col: one 16-byte load when all four exist, else element-wise (0 behind I)
-__device__ __forceinline__ void cat_load4(const float* __restrict__ row, int col, int I, bool full, float (&v)[4]) {
-    if (full) {
-        const f32x4 t = *reinterpret_cast<const f32x4_u4*>(row + col);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (col + j < I) ? row[col + j] : 0.f;
-    }
-}
-
 // the eight one-hot floats of items col .. col + 3
 __device__ __forceinline__ void cat_load_u(const float* __restrict__ urow, int col, int I, bool full, float (&u)[8]) {
     if (full) {
@@ -103,8 +78,8 @@ __device__ __forceinline__ void cat_keep4(const CatArgs& a, int b, int col, int 
 #pragma unroll
         for (int j = 0; j < 4; ++j) k[j] = (col + j < a.I && kr[col + j]) ? a.drop_scale : 0.f;
     } else if (a.drop_mode == 2) {
-        const int dsh = 16 * (u & 1);
-        const uint32_t du[4] = {(dr.x >> dsh) & 0xFFFFu, (dr.y >> dsh) & 0xFFFFu, (dr.z >> dsh) & 0xFFFFu, (dr.w >> dsh) & 0xFFFFu};
+        uint32_t du[4];
+        gd_drop_bits(dr, u & 1, du);
 #pragma unroll
         for (int j = 0; j < 4; ++j) k[j] = (du[j] < a.keep_thresh) ? a.drop_scale : 0.f;
     } else {
@@ -122,7 +97,7 @@ __global__ __launch_bounds__(256) void cat_prep_kernel(CatArgs a) {
         cb = a.cb[t];
     }
     const float w0 = a.cat_w[0], w1 = a.cat_w[1], w2 = a.cat_w[2], c = a.cat_b[0];
-    const uint2 key = make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    const uint2 key = gd_philox_key(a.seed);
     const int col_base = (blockIdx.x * (256 * CAT_G) + threadIdx.x) * 4;
     const float* __restrict__ xr = a.x + (int64_t)b * a.ldx;
     const float* __restrict__ ur = a.xU + (int64_t)b * a.ldu;
@@ -132,29 +107,20 @@ __global__ __launch_bounds__(256) void cat_prep_kernel(CatArgs a) {
 #pragma unroll
     for (int u = 0; u < CAT_G; ++u) {
         const int col = col_base + u * 1024;
-        if (a.drop_mode == 2 && (u & 1) == 0 && col < a.I)
-            dr = philox4x32_10(make_uint4((uint32_t)(col >> 2), (uint32_t)b, 1u, (uint32_t)a.offset), key);
+        if (a.drop_mode == 2 && (u & 1) == 0 && col < a.I) dr = gd_drop_block(col, b, a.offset, key);
         if (col >= a.I) continue;
         const bool full = col + 3 < a.I;
         float v[4], un[8], kp[4];
-        cat_load4(xr, col, a.I, full, v);
+        gd_load4(xr, col, a.I, full, v);
         cat_load_u(ur, col, a.I, full, un);
         if (a.ca) {
             float nz[4] = {0.f, 0.f, 0.f, 0.f};
-            if (a.noise_mode == 1) {
-                cat_load4(a.noise + (int64_t)b * a.ldn, col, a.I, full, nz);
-            } else if (a.noise_mode == 2) {
-                const uint4 r = philox4x32_10(make_uint4((uint32_t)(col >> 2), (uint32_t)b, 0u, (uint32_t)a.offset), key);
-                cat_box_muller(r.x, r.y, nz[0], nz[1]);
-                cat_box_muller(r.z, r.w, nz[2], nz[3]);
-            }
+            if (a.noise_mode == 1)
+                gd_load4(a.noise + (int64_t)b * a.ldn, col, a.I, full, nz);
+            else if (a.noise_mode == 2)
+                gd_normal4(col, b, GD_STREAM_NOISE, a.offset, key, nz);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#pragma clang fp contract(off)
-                const float p0 = ca * v[j];
-                const float p1 = cb * nz[j];
-                v[j] = p0 + p1;
-            }
+            for (int j = 0; j < 4; ++j) v[j] = gd_qsample(ca, v[j], cb, nz[j]);
         }
         cat_keep4(a, b, col, u, dr, kp);
         float z[4];
@@ -185,12 +151,10 @@ __global__ __launch_bounds__(256) void cat_prep_kernel(CatArgs a) {
     if (a.one_col >= 0 && blockIdx.x == 0 && threadIdx.x == 0) xin[a.one_col] = 1.f;
 }
 
-// ---------------------------------------------------------------------------------------------
 // gradients: first stage.  part[(b * gridDim.x + blockIdx.x) * 4 + k], k = (dz.x_t, dz.xU0, dz.xU1, dz)
-// ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cat_grad_kernel(CatArgs a, float* __restrict__ part) {
     const int b = blockIdx.y;
-    const uint2 key = make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    const uint2 key = gd_philox_key(a.seed);
     const int col_base = (blockIdx.x * (256 * CAT_G) + threadIdx.x) * 4;
     const float* __restrict__ dr_ = a.dxin + (int64_t)b * a.lddx;
     const float* __restrict__ xt = a.xt + (int64_t)b * a.ldxt;
@@ -200,13 +164,12 @@ __global__ __launch_bounds__(256) void cat_grad_kernel(CatArgs a, float* __restr
 #pragma unroll
     for (int u = 0; u < CAT_G; ++u) {
         const int col = col_base + u * 1024;
-        if (a.drop_mode == 2 && (u & 1) == 0 && col < a.I)
-            dr = philox4x32_10(make_uint4((uint32_t)(col >> 2), (uint32_t)b, 1u, (uint32_t)a.offset), key);
+        if (a.drop_mode == 2 && (u & 1) == 0 && col < a.I) dr = gd_drop_block(col, b, a.offset, key);
         if (col >= a.I) continue;
         const bool full = col + 3 < a.I;
         float d[4], v[4], un[8], kp[4];
-        cat_load4(dr_, col, a.I, full, d);
-        cat_load4(xt, col, a.I, full, v);
+        gd_load4(dr_, col, a.I, full, d);
+        gd_load4(xt, col, a.I, full, v);
         cat_load_u(ur, col, a.I, full, un);
         cat_keep4(a, b, col, u, dr, kp);
 #pragma unroll
@@ -262,8 +225,8 @@ __global__ __launch_bounds__(256) void cat_grad_reduce_kernel(const float* __res
 }
 
 int cat_fill_drop(CatArgs& a, int drop_mode, const uint8_t* keep, int64_t ldkeep, float drop_p, uint64_t seed, uint64_t offset) {
-    a.drop_mode = drop_mode; a.keep = keep; a.ldkeep = ldkeep; a.drop_scale = 1.0f / (1.0f - drop_p);
-    a.keep_thresh = (uint32_t)fmin(fmax(rint((1.0 - (double)drop_p) * 65536.0), 0.0), 65536.0);  // (as the plain builder)
+    a.drop_mode = drop_mode; a.keep = keep; a.ldkeep = ldkeep;
+    gd_drop_params(drop_p, &a.drop_scale, &a.keep_thresh);
     a.seed = seed; a.offset = offset;
     return 0;
 }

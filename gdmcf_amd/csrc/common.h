@@ -7,6 +7,7 @@
 #include "../../include/gdmcf_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef f32x4 f32x4_u4 __attribute__((aligned(4)));  // rows only 4-byte aligned (odd widths): gfx950 takes unaligned 16-byte accesses
 
 void gdmcf_set_error(const char* fmt, ...);
 
@@ -53,9 +54,8 @@ struct GdProfScope {
 static inline int gd_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool gd_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// ---- Philox4x32-10 (kernels_misc.hip, bpr.hip) ------------------------------------------------------------
-// Counter-based: any element can be regenerated in any kernel, so noise and dropout masks never have to be stored.  Counter
-// word z is the STREAM id: 0-6 are the draws of kernels_misc.hip, 7 is the BPR triple sampler (bpr.hip).
+// ---- Philox4x32-10 (draws.h: the streams and every draw built on it) --------------------------------------
+// Counter-based: any element can be regenerated in any kernel, so noise and dropout masks never have to be stored.
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
     constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
 #pragma unroll
@@ -79,7 +79,13 @@ struct GdShadow {
     int64_t rows, cols;
 };
 bool gd_shadow_lookup(const void* f32, GdShadow* out);
-int gd_cast_bf16(const float* src, int64_t ld, void* dst, int64_t ld16, int64_t rows, int64_t cols, hipStream_t s);
+int gd_cast_bf16(const float* src, int64_t ld, void* dst, int64_t ld16, int64_t rows, int64_t cols, hipStream_t s);  // reduce.hip
+
+// round-to-nearest-even float -> bfloat16 bits (v_cvt_pk_bf16_f32): what every kernel that keeps a shadow in sync stores
+__device__ __forceinline__ unsigned short gd_bf16_bits(float x) {
+    __bf16 h = (__bf16)x;
+    return __builtin_bit_cast(unsigned short, h);
+}
 
 // ---- GEMM core (gemm_f32.hip) -----------------------------------------------------------
 enum { GD_LAY_KC = 0, GD_LAY_MC = 1 };  // operand stored [rows][K] (K contiguous) / [K][rows]
@@ -98,7 +104,7 @@ struct GdAdamHyper {
     float inv_bc2_sqrt;  // 1 / sqrt(1 - beta2^step), from the double
     float pad_[3];       // (16-byte multiple: the struct is copied to the device in tables)
 };
-GdAdamHyper gd_adam_hyper(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale);
+GdAdamHyper gd_adam_hyper(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale);  // adamw.hip
 
 // One element of torch.optim.AdamW's single-tensor update (torch/optim/adamw.py; reference main.py:258, :351).
 // Every kernel that updates parameters inlines THIS function (the stand-alone pass, the epilogues of the LDS-tiled products, the
@@ -121,7 +127,7 @@ __device__ __forceinline__ void gd_adam_elem(float& p, float g, float& m, float&
     p = __builtin_fmaf(h.neg_step * m, __builtin_amdgcn_rcpf(denom), p);
 }
 
-// ---- graph step state (kernels_misc.hip: gdmcf_graph_state_*) ---------------------------------------------------------
+// ---- graph step state (adamw.hip: gdmcf_graph_state_*) ---------------------------------------------------------
 // When a training step is captured in a hipGraph its kernel ARGUMENTS are frozen; what changes from step to step (the
 // Philox offsets of the input builder and of the timestep sampler, the AdamW bias corrections) therefore lives in device
 // memory: a block of this layout, advanced by gdmcf_graph_state_tick at the start of every step (eager or replayed).

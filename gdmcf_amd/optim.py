@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 
-_BLOCK = 4096  # elements per workgroup; must match ADAM_BLOCK_ELEMS in kernels_misc.hip
+_BLOCK = 4096  # elements per workgroup; must match ADAM_BLOCK_ELEMS in csrc/adamw.hip
 _ROW_ALIGN = 32  # floats: fuse_into_backward seats the rows of a fused weight (and of its moments) on 128-byte lines
 
 

@@ -36,6 +36,24 @@ def test_library_is_built_from_the_current_sources():
     assert open(stamp).read() == b._digest(), "sources changed since libgdmcf_hip.so was built: run python -m gdmcf_amd.build"
 
 
+def test_build_lists_name_every_source_and_header():
+    """gdmcf_amd/build.py: SOURCES is what gets compiled and linked, HEADERS (with SOURCES) feeds the rebuild digest -- a .hip file
+    missing from the first is not in the library, a header missing from the second can be edited without a rebuild."""
+    from gdmcf_amd import build as b
+    on_disk = os.listdir(b.CSRC)
+    assert sorted(b.SOURCES) == sorted(f for f in on_disk if f.endswith(".hip")), "csrc/*.hip and build.SOURCES differ"
+    listed = {os.path.normpath(os.path.join(b.CSRC, h)) for h in b.HEADERS}
+    assert len(listed) == len(b.HEADERS)
+    for f in on_disk:
+        if f.endswith(".h"):
+            assert os.path.join(b.CSRC, f) in listed, f"csrc/{f} is not in build.HEADERS"
+    for f in b.SOURCES + b.HEADERS:
+        assert os.path.isfile(os.path.join(b.CSRC, f)), f"{f} is listed in build.py but does not exist"
+    for group in (b.ASM_LINT, b.STORE_LINT, b.NO_SPILL):
+        assert set(group) <= set(b.SOURCES)
+    assert "cat.hip" in b.NO_SPILL
+
+
 def test_schedule_build_matches_reference_tables():
     fx = H.load("schedules")
     kinds = {"linear": 0, "linear-var": 1, "cosine": 2, "binomial": 3}
