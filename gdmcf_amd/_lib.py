@@ -1,17 +1,105 @@
-"""ctypes binding of libgdmcf_hip.so (C ABI: include/gdmcf_hip.h).
+"""ctypes binding of libgdmcf_hip.so, derived from the C ABI's own text: include/gdmcf_hip.h is parsed once at import, and
+every signature, GdDwAdamw's fields and the GDMCF_* constants follow from it.  A new entry point is declared in the header and
+defined in a .hip file; nothing is restated here.  The header is plain C99 in one style (`<type> <name>` parameters, /* */
+comments), which is all the parser reads.  Type map, for parameters, return types and struct members (`const` is dropped):
+    int -> c_int    int64_t -> c_int64    uint64_t -> c_uint64    size_t -> c_size_t    float -> c_float    double -> c_double
+    char* -> c_char_p    any other pointer -> c_void_p    anything else -> ImportError naming the declaration
 
 The product path has NO CPU fallback: if the HIP library is missing, or a kernel is asked to run
 without a GPU, this module raises -- it never routes through PyTorch eager or the oracle.
 """
 import ctypes
 import os
+import re
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgdmcf_hip.so")
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "gdmcf_hip.h"))
 
-GDMCF_OK, E_SHAPE, E_ARG, E_UNSUPPORTED, E_HIP, E_WORKSPACE = 0, -1, -2, -3, -4, -5
-N_TABLES = 13
+P = c_void_p
+_CTYPES = {"int": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float, "double": c_double}
+
+
+def _uncomment(text):
+    return re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+
+
+def _code(text):
+    """A header's declarations: no comments, no preprocessor lines, no `extern "C" {` / `}` lines."""
+    return re.sub(r'^[ \t]*(#.*|extern\s+"C"\s*\{|\})[ \t]*$', "", _uncomment(text), flags=re.M)
+
+
+def _ctype(ctype, where):
+    words = re.sub(r"\bconst\b", " ", ctype).replace("*", " * ").split()
+    if "*" in words:
+        return c_char_p if words == ["char", "*"] else c_void_p
+    if " ".join(words) not in _CTYPES:
+        raise ImportError(f"gdmcf_hip.h: no ctypes type for '{' '.join(ctype.split())}' in the declaration of {where}")
+    return _CTYPES[" ".join(words)]
+
+
+def _declarator(decl, where):
+    """('<type>', '<name>') of a parameter or a struct member; the stars may sit on either side of the space."""
+    m = re.fullmatch(r"\s*(.*[\s*])(\w+)\s*", decl, flags=re.S)
+    if not m:
+        raise ImportError(f"gdmcf_hip.h: cannot read '{decl.strip()}' in the declaration of {where}")
+    return m.groups()
+
+
+def parse_functions(text):
+    """{name: (restype, [argtypes])} of every `<ret> gdmcf_<name>(<params>);` of a header text, in the header's order."""
+    code = _code(text)
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(gdmcf_\w+)\s*\(([^()]*)\)\s*;", code):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_ctype(ret, name), [_ctype(_declarator(p, name)[0], name) for p in params])
+    # a declaration the pattern skipped must not become a function that ctypes calls with its default int arguments
+    mentioned = re.findall(r"(gdmcf_\w+)\s*\(", code)
+    if len(mentioned) != len(out):
+        raise ImportError(f"gdmcf_hip.h: {len(mentioned)} gdmcf_*( but {len(out)} declarations read; unreadable: "
+                          f"{sorted(set(mentioned) - set(out)) or 'none, a name is repeated'}")
+    return out
+
+
+def parse_constants(text):
+    """{name: int} of every `#define GDMCF_<NAME> <integer or (-integer)>` and every `NAME = n` member of an anonymous enum."""
+    text = _uncomment(text)
+    out = {n: int(v) for n, v in re.findall(r"^\s*#\s*define\s+(GDMCF_\w+)\s+\(?\s*(-?\d+)\s*\)?\s*$", text, flags=re.M)}
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for member in filter(str.strip, body.split(",")):
+            m = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", member)
+            if not m:
+                raise ImportError(f"gdmcf_hip.h: enum member '{member.strip()}' is not `NAME = integer`")
+            out[m.group(1)] = int(m.group(2))
+    return out
+
+
+def parse_structs(text):
+    """{name: [(member, ctype), ...]} of every `typedef struct <name> { ... } <name>;`; a line may declare several members."""
+    out = {}
+    for name, body in re.findall(r"\btypedef\s+struct\s+(\w+)\s*\{([^}]*)\}\s*\1\s*;", _code(text)):
+        out[name] = []
+        for line in filter(str.strip, body.split(";")):
+            first, *more = line.split(",")
+            ctype, member = _declarator(first, "struct " + name)
+            if more and "*" in line:  # (`float *a, b;` declares one pointer and one float)
+                raise ImportError(f"gdmcf_hip.h: struct {name}: '{line.strip()}' must declare one pointer member per line")
+            out[name] += [(m.strip(), _ctype(ctype, "struct " + name)) for m in [member] + more]
+    return out
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        _HEADER = _f.read()
+except OSError as e:
+    raise ImportError(f"{HEADER_PATH} is missing: gdmcf_amd._lib derives its ctypes binding from the C header, which sits "
+                      "beside the package in the source tree.") from e
+_SIGNATURES = parse_functions(_HEADER)
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+CONSTANTS = parse_constants(_HEADER)
+GDMCF_OK, E_SHAPE, E_ARG, E_UNSUPPORTED, E_HIP, E_WORKSPACE, N_TABLES = (
+    CONSTANTS["GDMCF_" + n] for n in ("OK", "E_SHAPE", "E_ARG", "E_UNSUPPORTED", "E_HIP", "E_WORKSPACE", "N_TABLES"))
 TABLE_NAMES = (
     "betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_next", "sqrt_alphas_cumprod",
     "sqrt_one_minus_alphas_cumprod", "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod",
@@ -19,108 +107,12 @@ TABLE_NAMES = (
     "posterior_mean_coef1", "posterior_mean_coef2",
 )
 
-P = c_void_p
-_SIGNATURES = {
-    "gdmcf_version": (c_int, []),
-    "gdmcf_debug_last_gemm": (c_int, []),
-    "gdmcf_last_error": (c_char_p, []),
-    "gdmcf_device_info": (c_int, [P, P, c_char_p, c_int]),
-    "gdmcf_prof_enable": (c_int, [c_int]),
-    "gdmcf_prof_collect": (c_int, [c_int, P, P, P]),
-    "gdmcf_schedule_build": (c_int, [c_int, c_double, c_double, c_double, c_int, c_int, P]),
-    "gdmcf_densify_rows_f32": (c_int, [P, P, P, P, c_int, c_int, P, c_int64, P]),
-    "gdmcf_dnn_prep_input_f32": (c_int, [P, c_int64, P, P, P, c_int, P, c_int64, c_int, P, c_int64, c_float, c_uint64,
-                                         c_uint64, c_int, P, P, c_int, c_int, c_int, P, c_int64, P, c_int64, P, P, P]),
-    "gdmcf_dnn_emb_cols_f32": (c_int, [P, P, P, c_int, c_int, c_int, P, c_int64, P, P]),
-    "gdmcf_topn_metrics_f64": (c_int, [P, c_int64, c_int, P, P, P, c_int, P, P]),
-    "gdmcf_gemm_precision": (c_int, [c_int]),
-    "gdmcf_bf16_shadow_set": (c_int, [P, P, c_int64, c_int64, c_int64]),
-    "gdmcf_bf16_shadow_clear": (c_int, [P]),
-    "gdmcf_bf16_shadow_get": (P, [P]),
-    "gdmcf_bf16_shadow_info": (c_int, [P, P, P, P, P]),
-    "gdmcf_bf16_shadow_sync": (c_int, [P, c_int64, P]),
-    "gdmcf_linear_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "gdmcf_linear_fwd_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, P, c_int64, P, c_size_t, P]),
-    "gdmcf_linear_fwd_wt_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, P, c_int64, P, c_size_t, P]),
-    "gdmcf_loss_tiles": (c_int, [c_int]),
-    "gdmcf_linear_loss_fwd_f32": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, P, c_int, c_int, c_int, P, c_int64, P,
-                                          c_int64, P, P, P]),
-    "gdmcf_linear_posterior_fwd_f32": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, P, P, P, P, P, P, c_int64, c_int,
-                                               c_int, c_int, P, c_int64, P, c_int64, P]),
-    "gdmcf_linear_bwd_input_f32": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, c_int, c_int, c_int, c_int, P,
-                                           c_int64, P, c_size_t, P]),
-    "gdmcf_linear_bwd_weight_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, P, c_int64, P, c_int, P]),
-    "gdmcf_linear_bwd_weight_adamw_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, P, c_int64, P, P, P, c_float,
-                                                  c_float, c_float, c_float, c_float, c_int, c_float, P]),
-    "gdmcf_linear_bwd_weight_adamw_multi_f32": (c_int, [P, c_int, P]),
-    "gdmcf_rowscale_f32": (c_int, [P, c_int64, P, c_int, c_int, P, c_int64, P]),
-    "gdmcf_emb_bwd_f32": (c_int, [P, c_int64, P, c_int64, c_int, c_int, P, c_int, c_int, P, P, P, P]),
-    "gdmcf_row_loss_finish_f64": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),
-    "gdmcf_lt_history_update": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
-    "gdmcf_onehot_noise_f32": (c_int, [P, c_int64, P, c_int, c_int, c_float, P, c_int64, c_uint64, c_uint64, P, c_int64, P,
-                                     c_int64, P]),
-    "gdmcf_row_norms_f32": (c_int, [P, c_int64, c_int, c_int, P, P, P]),
-    "gdmcf_normalize_rows_bwd_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, P, c_int64, P]),
-    "gdmcf_tanh_bwd_f32": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, c_int, c_int, P, c_int64, P]),
-    "gdmcf_gather_rows_f32": (c_int, [P, c_int64, P, c_int, c_int, P, c_int64, P]),
-    "gdmcf_scatter_add_rows_f32": (c_int, [P, c_int64, P, c_int, c_int, P, c_int64, P]),
-    "gdmcf_normalize_rows_bwd_adamw_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, P, c_int64, P, P, c_float, c_float,
-                                                   c_float, c_float, c_float, c_int, c_float, P]),
-    "gdmcf_scatter_rows_adamw_f32": (c_int, [P, c_int64, P, c_int, c_int, c_int, P, c_int64, P, P, c_float, c_float, c_float,
-                                             c_float, c_float, c_int, c_float, P]),
-    "gdmcf_dp_pack_f64": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, P, P]),
-    "gdmcf_dp_unpack_f64": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
-    "gdmcf_randn_f32": (c_int, [P, c_int64, c_int, c_int, c_int, c_uint64, c_uint64, P]),
-    "gdmcf_eps_target_f32": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, c_int, c_int, c_int, P, c_int64, P, P, P]),
-    "gdmcf_sample_timesteps": (c_int, [P, P, c_int, c_int, c_int, c_double, c_uint64, c_uint64, P, P, P, P]),
-    "gdmcf_adamw_f32": (c_int, [P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_float, P]),
-    "gdmcf_adamw_bf16s_f32": (c_int, [P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_float, P]),
-    "gdmcf_topk_masked_f32": (c_int, [P, c_int64, c_int, c_int, P, P, c_int, P, P, P]),
-    "gdmcf_spmm_csr_f32": (c_int, [P, P, P, P, c_int, c_int, P, P, c_int, P, P, c_int, P, c_int64, c_int, P, c_int64, P, P, c_int,
-                                   c_int64, c_float, c_double, P]),
-    "gdmcf_spmm_bundled_f32": (c_int, [P, c_int, P, P, P, P, c_int, P, P, P, P, c_int, P, P, c_int, P, P, c_int64, c_int, c_int, P, c_int64, c_int, P,
-                                       c_int64, P, P, c_int, c_int64, c_float, c_double, P]),
-    "gdmcf_spmm_stream_f32": (c_int, [P, c_int, P, c_int64, P, c_int, P, P, c_int, c_int, c_int, P, c_int64, c_int, P, c_int64, P, P,
-                                      c_int, c_int64, c_float, c_double, P]),
-    "gdmcf_graph_guided_step_u8": (c_int, [P, c_int64, P, c_int, c_int, c_float, P, c_int64, P, P, c_int, c_uint64, c_uint64, P,
-                                           c_int64, P, P]),
-    "gdmcf_debug_spmm_stamps": (c_int, [c_int, P]),
-    "gdmcf_graph_state_bytes": (c_int, []),
-    "gdmcf_adam_hyper_bytes": (c_int, []),
-    "gdmcf_graph_state_init": (c_int, [P, c_uint64, c_uint64, c_int64, c_int64, c_int64, P]),
-    "gdmcf_adam_hyper_fill": (c_int, [P, c_int, c_float, c_float, c_float, c_float, c_float, c_int64, c_float]),
-    "gdmcf_graph_state_bind": (c_int, [P]),
-    "gdmcf_graph_state_tick": (c_int, [P, P]),
-    "gdmcf_row_loss_finish_mean_f64": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, P]),
-    "gdmcf_dnn_prep_input_csr_f32": (c_int, [P, P, P, P, P, P, c_int, P, c_int64, c_int, P, c_int64, c_float, c_uint64, c_uint64,
-                                             P, P, c_int, c_int, c_int, P, c_int64, P, P, c_int64, P]),
-    "gdmcf_linear_loss_fwd_bits_f32": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, P, c_int, c_int, c_int, P, c_int64, P,
-                                               c_int64, P, P, P]),
-    "gdmcf_scale_f32": (c_int, [P, c_int64, c_float, P, P]),
-    "gdmcf_onehot_prep_input_csr_f32": (c_int, [P, P, P, P, c_float, P, c_int64, c_uint64, c_uint64, P, c_int64, P, c_int, P,
-                                                c_int64, c_float, c_uint64, P, P, c_int, c_int, c_int, P, c_int64, P, P,
-                                                c_int64, P]),
-    "gdmcf_score_topk_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "gdmcf_score_topk_f32": (c_int, [P, c_int64, P, c_int, P, c_int64, c_int, c_int, P, P, c_int, P, P, P, c_size_t, P]),
-    "gdmcf_bpr_sample_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_uint64, c_uint64, P, P, P, P]),
-    "gdmcf_bpr_loss_f32": (c_int, [P, c_int64, P, c_int64, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P]),
-    "gdmcf_bpr_grad_f32": (c_int, [c_int, P, P, P, P, c_int, c_int, c_int, P, P, c_int64, c_int, P, c_int64, c_float, P, c_int64, P]),
-    "gdmcf_cat_prep_input_f32": (c_int, [P, c_int64, P, c_int64, P, P, P, c_int, P, c_int64, c_int, P, c_int64, c_float, c_uint64,
-                                         c_uint64, P, P, P, P, c_int, c_int, c_int, P, c_int64, P, c_int64, P, P]),
-    "gdmcf_cat_grad_ws_bytes": (c_size_t, [c_int, c_int]),
-    "gdmcf_cat_grad_f32": (c_int, [P, c_int64, P, c_int64, P, c_int64, c_int, P, c_int64, c_float, c_uint64, c_uint64, c_int, c_int,
-                                   P, c_size_t, P, P, P]),
-}
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-
 
 class GdDwAdamw(ctypes.Structure):
     """One entry of gdmcf_linear_bwd_weight_adamw_multi_f32's list (include/gdmcf_hip.h): the arguments of one
     gdmcf_linear_bwd_weight_adamw_f32 call."""
-    _fields_ = [("dZ", c_void_p), ("lddz", c_int64), ("A", c_void_p), ("lda", c_int64), ("rowscale", c_void_p),
-                ("a_scale_col", c_int), ("M", c_int), ("N", c_int), ("K", c_int), ("W", c_void_p), ("ldw", c_int64),
-                ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("db", c_void_p), ("lr", c_float), ("beta1", c_float),
-                ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float), ("step", c_int), ("grad_scale", c_float)]
+    _fields_ = parse_structs(_HEADER)["GdDwAdamw"]
+
 
 _lib = None
 

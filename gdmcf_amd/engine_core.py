@@ -22,7 +22,7 @@ class _Bufs:
     pass
 
 
-_GEMM_MODES = {"f32": 0, "bf16": 1, "f32x3": 2}  # include/gdmcf_hip.h GDMCF_GEMM_F32 / _BF16 / _F32X3
+_GEMM_MODES = {k: _lib.CONSTANTS["GDMCF_GEMM_" + k.upper()] for k in ("f32", "bf16", "f32x3")}  # include/gdmcf_hip.h's enum
 
 
 def with_precision(fn):

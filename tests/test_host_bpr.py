@@ -1,8 +1,6 @@
-"""CPU (-m "not gpu"): the fused BPR step's C entry points are declared and exported, its host API refuses CPU tensors, and
-the sampler's "r-th item missing from a sorted row" search (csrc/bpr.hip: bpr_sample_kernel) is right on paper."""
-import os
-import re
-
+"""CPU (-m "not gpu"): the fused BPR step's C entry points check their arguments (their declaration, export and binding:
+tests/test_host_abi.py), its host API refuses CPU tensors, and the sampler's "r-th item missing from a sorted row" search
+(csrc/bpr.hip: bpr_sample_kernel) is right on paper."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -11,20 +9,6 @@ import torch
 import gdmcf_amd
 from gdmcf_amd import _lib
 from gdmcf_amd.lightgcn import BPRTrainer, bpr_loss_grad, bpr_reg_grad_, sample_bpr_items
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("gdmcf_bpr_sample_f32", "gdmcf_bpr_loss_f32", "gdmcf_bpr_grad_f32")
-
-
-def test_bpr_symbols_are_declared_and_exported():
-    hdr = open(os.path.join(ROOT, "include", "gdmcf_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    lib = _lib.load()
-    for name in SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, hdr), f"{name} is not declared in include/gdmcf_hip.h"
-        assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
-    from gdmcf_amd import build as b
-    assert "bpr.hip" in b.SOURCES
 
 
 def test_bpr_entry_points_check_their_arguments():

@@ -1,8 +1,6 @@
 """CPU: the DNNCat backbone's host side -- parameter layout against the reference's recorded state_dict, what it refuses,
-which diffusion modes accept it, and the C entry points of csrc/cat.hip in the header, the binding and the build list."""
-import os
-import re
-
+which diffusion modes accept it, and the argument checks of csrc/cat.hip's C entry points (their declaration, export and
+binding: tests/test_host_abi.py; cat.hip in the build lists: test_build_lists_name_every_source_and_header)."""
 import pytest
 import torch
 
@@ -10,9 +8,7 @@ import gdmcf_amd
 from gdmcf_amd import ModelMeanType, _lib
 from tests import helpers as H
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRAIN_CASES = ["tiny_x0", "ragged_eps_wd", "deep_x0", "wide_x0"]
-SYMBOLS = ("gdmcf_cat_prep_input_f32", "gdmcf_cat_grad_ws_bytes", "gdmcf_cat_grad_f32")
 
 
 def _model(I=64, dims=(16,), **kw):
@@ -69,18 +65,6 @@ def test_onehot_model_accepts_dnncat_without_indexin_only():
     with pytest.raises(TypeError):
         d._onehot_model(gdmcf_amd.DNN([64, 16], [16, 64], 10))
     assert not isinstance(m, gdmcf_amd.DNN)  # (the continuous diffusion and the graphed step still want the plain DNN)
-
-
-def test_cat_symbols_are_declared_bound_and_built():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gdmcf_hip.h")).read(), flags=re.S)
-    lib = _lib.load()
-    for name in SYMBOLS:
-        m = re.search(r"\b(?:int|size_t)\s+%s\s*\(([^)]*)\)" % name, hdr)
-        assert m, f"{name} is not declared in include/gdmcf_hip.h"
-        assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
-        assert len(_lib._SIGNATURES[name][1]) == len([a for a in m.group(1).split(",") if a.strip()]), name
-    import gdmcf_amd.build as b
-    assert "cat.hip" in b.SOURCES and "cat.hip" in b.NO_SPILL
 
 
 def test_cat_entry_points_check_their_arguments():
