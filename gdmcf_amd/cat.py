@@ -11,10 +11,18 @@ Downstream of the mix this is `DenoiserEngine`'s layer chain.  Two things differ
     (`gdmcf_linear_bwd_input_f32` on the first I columns of W1, its leading dimension) and `gdmcf_cat_grad_f32`, which reduces
     it to cat_layer's four gradients.  The keep-mask is recomputed there from the builder's Philox position, not stored.
 
+Rows that stay sparse (opt-in: `DNNCat(..., csr_rows=True)`): a `data_utils.CsrBatch` (x0 target, all values 1, Philox or given
+noise) then feeds `gdmcf_cat_prep_input_csr_f32` -- densify, class draws and the builder in one launch, the rows and the classes
+left as two bitmaps -- the loss takes its target from the row bitmap and `gdmcf_cat_grad_bits_f32` the one-hot pair from both;
+no dense batch and no [B, 2I] image exist (the image's buffer is made by the first DENSE training step only).  The Philox
+positions are the dense route's and both kernels' outputs are the dense ones' bit for bit, so a run on `csr.batch(ids)` is the
+run on `csr.rows(ids)`.  The default stays
+`csr_rows=False` (`training_losses` densifies a CsrBatch, as it does for every configuration the sparse kernels do not cover:
+eps target, values other than 1, torch-drawn noise).
+
 Not built (each raises NotImplementedError): `norm=True`, GEMM inputs other than f32, AdamW fused into the backward pass
-(dxin reads W1: the first layer's update must not run before it), the graphed step, CSR-fed rows (densified by
-`training_losses`), data parallel.  Constructor, parameter names and initialisation draw order are the reference's, so
-checkpoints interchange.
+(dxin reads W1: the first layer's update must not run before it), the graphed step, data parallel; the reverse loop takes
+dense rows only.  Constructor, parameter names and initialisation draw order are the reference's, so checkpoints interchange.
 """
 import numpy as np
 import torch
@@ -32,12 +40,14 @@ class CatEngine(DenoiserEngine):
 
     onehot_rows = OneHotEngine.onehot_rows  # x_tU as the [B, 2I] float image (gdmcf_onehot_noise_f32)
     _last_layer = OneHotEngine._last_layer  # output layer, plain or with the posterior mean in its epilogue
+    _xU = OneHotEngine._xU  # bufs.xU, the [B, 2I] image of the dense route, made on its first step
 
     def buffers(self, B, device):
         b = super().buffers(B, device)
         if getattr(b, "dxin", None) is None:
             f32 = dict(dtype=torch.float32, device=device)
-            b.xU = torch.zeros(B, 2 * self.I, **f32)
+            b.xU = None  # never made by a run on CSR rows (_xU)
+            b.x0bits = b.clsbits = None  # the sparse route's rows and classes as bitmaps (_train_input_csr)
             b.xt = torch.zeros(B, b.ldi, **f32)  # x_t: eps target, posterior, and the backward pass's first sum
             b.dxin = torch.zeros(B, b.ldi, **f32)
             b.cat_ws_bytes = int(self.lib.gdmcf_cat_grad_ws_bytes(B, self.I))
@@ -56,10 +66,7 @@ class CatEngine(DenoiserEngine):
         p = float(m.drop.p)
         noise_mode, noise, drop_mode, keep = core._prep_modes(B, ca, noise, drop_mask, p, training)
         (nz, ldn), (kp, ldkp) = core._pl(noise), core._pl(keep)
-        cw, cb_ = m.cat_layer.weight, m.cat_layer.bias
-        _lib.require_gpu(cw, "DNNCat parameters")
-        if not (cw.is_contiguous() and cb_.is_contiguous() and cw.dtype == torch.float32):
-            raise RuntimeError("gdmcf_amd: DNNCat parameters must be contiguous float32")
+        cw, cb_ = self._cat_params()
         self.offset += 1
         _lib.check(self.lib.gdmcf_cat_prep_input_f32(
             x.data_ptr(), x.stride(0), xU.data_ptr(), xU.stride(0), ts.data_ptr(), _lib.ptr(ca), _lib.ptr(cb), noise_mode, nz,
@@ -67,14 +74,48 @@ class CatEngine(DenoiserEngine):
             m.emb_layer.bias.data_ptr(), self.E, B, self.I, bufs.xin.data_ptr(), bufs.xin.stride(0), bufs.xt.data_ptr(),
             bufs.xt.stride(0), bufs.temb.data_ptr(), _lib.stream_ptr()))
         bufs.xin_ones = True
-        self._drop = (drop_mode, keep, p, self.offset)
+        self._drop = (drop_mode, keep, p, self.offset, False)
         return x, noise, keep, xU
+
+    def _cat_params(self):
+        cw, cb_ = self.model.cat_layer.weight, self.model.cat_layer.bias
+        _lib.require_gpu(cw, "DNNCat parameters")
+        if not (cw.is_contiguous() and cb_.is_contiguous() and cw.dtype == torch.float32):
+            raise RuntimeError("gdmcf_amd: DNNCat parameters must be contiguous float32")
+        return cw, cb_
 
     def _train_input(self, bufs, spec, xt_out):
         x0 = core._f32_rows(spec["x_start"])
-        _, s8 = self.onehot_rows(x0, spec["ts_U"], spec["sampled"], spec["discrete"], out=bufs.xU)
-        return self._cat_input(bufs, x0, bufs.xU, spec["ts"], spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"],
+        xU = self._xU(bufs, x0.shape[0], x0.device)
+        _, s8 = self.onehot_rows(x0, spec["ts_U"], spec["sampled"], spec["discrete"], out=xU)
+        return self._cat_input(bufs, x0, xU, spec["ts"], spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"],
                                self.model.training) + (s8,)
+
+    def _train_input_csr(self, bufs, spec):
+        """gdmcf_cat_prep_input_csr_f32 on spec["csr"] (data_utils.CsrBatch): bufs.xin and bufs.xt as _train_input leaves them,
+        the rows in bufs.x0bits (the loss target), the classes in bufs.clsbits; no dense row, no one-hot image.  The Philox
+        position advances as on the dense route (class draws, then the builder), so both routes draw the same numbers from the
+        same seed."""
+        batch, m = spec["csr"], self.model
+        B, I = batch.shape
+        if bufs.x0bits is None:
+            bufs.x0bits = torch.zeros(B, (I + 31) // 32, dtype=torch.int32, device=batch.device)
+            bufs.clsbits = torch.zeros_like(bufs.x0bits)
+        s8, ts_U, sampled = None, spec["ts_U"], spec["sampled"]
+        if sampled is not None:
+            s8 = (sampled if sampled.dtype == torch.uint8 else (sampled != 0).to(torch.uint8)).contiguous()
+        elif ts_U is not None:
+            ts_U = ts_U.to(device=batch.device, dtype=torch.int64).contiguous()
+        self._cat_params()
+        p = float(m.drop.p)
+        self.offset += 2
+        _, noise, keep, drop_mode = core.cat_prep_input_csr(
+            self.lib, batch, ts_U, spec["discrete"], s8, self.seed, self.offset - 1, spec["ts"], spec["ca"], spec["cb"],
+            spec["noise"], spec["drop_mask"], p, m.training, self.offset, m.cat_layer, m.emb_layer, self.E, bufs.xin, bufs.xt,
+            bufs.temb, bufs.x0bits, bufs.clsbits, _lib.stream_ptr())
+        bufs.xin_ones = True
+        self._drop = (drop_mode, keep, p, self.offset, True)
+        return None, noise, keep, batch, s8, ts_U
 
     # -- backward: the plain chain, then the cat layer ---------------------------------------------------------------------
     def _backward(self, sv, dz_last, rowscale):
@@ -89,7 +130,11 @@ class CatEngine(DenoiserEngine):
         # dxin = dZ1 . W1[:, 0:I]: bufs.dzs[0] is still d(loss)/d(first pre-activation), W1 is not updated before step()
         core.linear_bwd_input(self.lib, bufs, bufs.dzs[0], w1, None, None, 0, B, w1.shape[0], self.I, bufs.dxin, st)
         gw, gb = self._grad_like(m.cat_layer.weight), self._grad_like(m.cat_layer.bias)
-        drop_mode, keep, p, offset = self._drop
+        drop_mode, keep, p, offset, sparse = self._drop
+        if sparse:  # the one-hot pair from the bitmaps the CSR-fed builder wrote
+            core.cat_grad_bits(self.lib, bufs.dxin, bufs.xt, bufs.x0bits, bufs.clsbits, drop_mode, keep, p, self.seed, offset, B,
+                               self.I, bufs.cat_ws, bufs.cat_ws_bytes, gw, gb, st)
+            return out[:2] + [gw, gb] + out[2:]
         (kp, ldkp) = core._pl(keep)
         _lib.check(self.lib.gdmcf_cat_grad_f32(
             bufs.dxin.data_ptr(), bufs.dxin.stride(0), bufs.xt.data_ptr(), bufs.xt.stride(0), bufs.xU.data_ptr(),
@@ -123,11 +168,14 @@ class CatEngine(DenoiserEngine):
 class DNNCat(nn.Module):
     """Drop-in for the reference DNNCat (models/DNN.py:180-265)."""
 
-    csr_rows = False  # training_losses densifies a CsrBatch for this backbone
+    csr_rows = False  # training_losses densifies a CsrBatch for this backbone unless the instance was built with csr_rows=True
     fused_update_refusal = ("the input gradient of the first layer reads its weight, which a fused update would overwrite "
                             "first; use the separate AdamW pass")
 
-    def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, cat_dim=2, gemm_dtype="f32"):
+    def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, cat_dim=2, gemm_dtype="f32",
+                 csr_rows=False):
+        """csr_rows=True: a data_utils.CsrBatch handed to training_losses stays sparse (module docstring); the default
+        densifies it."""
         super().__init__()
         if norm:
             raise NotImplementedError("gdmcf_amd.DNNCat: norm=True needs a row norm between the mix and the dropout")
@@ -136,6 +184,8 @@ class DNNCat(nn.Module):
         if cat_dim != 2:
             raise NotImplementedError("gdmcf_amd.DNNCat: the input kernel mixes x_t with one-hot PAIRS (cat_dim = 2)")
         self.gemm_dtype = gemm_dtype
+        if csr_rows:
+            self.csr_rows = True  # (on the instance only: the class attribute is the default)
         self.in_dims = list(in_dims)
         self.out_dims = list(out_dims)
         assert out_dims[0] == in_dims[-1], "In and out dimensions must equal to each other."

@@ -162,6 +162,12 @@ class DenoiserEngine(EngineBase):
         bufs.xin_ones = True
         return keepalive
 
+    def _train_input_csr(self, bufs, spec):
+        """The first layer's input of a training step on rows that stay sparse (spec["csr"]; a backbone with its own input step
+        overrides this); returns (None or x0, noise, ...) to keep referenced -- the x0 target is bufs.x0bits."""
+        return self._prep_csr(bufs, spec["csr"], spec["ts"], spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"],
+                              self.model.training)
+
     def _transposed(self, w):
         """W^T of a large weight, [in, out] row-major on 128-byte rows, cached per weight VERSION: the reverse-diffusion loop of an
         evaluation runs many batches over frozen weights, and with the weight in this orientation the hidden layer's product runs
@@ -213,7 +219,7 @@ class DenoiserEngine(EngineBase):
                 bufs.xt = torch.zeros(B, bufs.ldi, dtype=torch.float32, device=dev)
             xt_out = bufs.xt
         if csr is not None:
-            keepalive = self._prep_csr(bufs, csr, ts, spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"], self.model.training)
+            keepalive = self._train_input_csr(bufs, spec)
         else:
             keepalive = self._train_input(bufs, spec, xt_out)
         x0c = keepalive[0]

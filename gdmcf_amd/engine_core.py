@@ -118,6 +118,37 @@ def onehot_prep_input_csr(lib, batch, ts_U, discrete, sampled, seed, offset_nois
     return batch, sampled, keep
 
 
+def cat_prep_input_csr(lib, batch, ts_U, discrete, sampled, seed, offset_noise, ts, ca, cb, noise, drop_mask, drop_p, training,
+                       offset_prep, cat, emb, E, xin, xt, temb, x0bits, clsbits, st):
+    """gdmcf_cat_prep_input_csr_f32: the DNNCat backbone's first-layer input [ drop(cat_layer(x_t, one-hot pair)) | emb(t) | 1 |
+    0-pad ] and x_t straight from the device CSR rows of `batch` -- what gdmcf_onehot_noise_f32 (at `offset_noise`) +
+    gdmcf_cat_prep_input_f32 (at `offset_prep`) leave on the dense rows, without those rows and without the [B, 2I] image.
+    `sampled`: the given classes (uint8 [B, I]) or None (drawn from ts_U); `cat`: the cat layer.  The rows go to `x0bits`, the
+    classes to `clsbits` (bitmaps).  Returns (batch, noise, keep, drop_mode): the first three to keep referenced, the last for
+    the backward pass, which recomputes a drawn keep-mask."""
+    B, I = batch.shape
+    noise_mode, noise, drop_mode, keep = _prep_modes(B, ca, noise, drop_mask, drop_p, training)
+    (sp, lds), (nz, ldn), (kp, ldkp) = _pl(sampled), _pl(noise), _pl(keep)
+    c = batch.csr
+    _lib.check(lib.gdmcf_cat_prep_input_csr_f32(
+        c.indptr.data_ptr(), c.indices.data_ptr(), batch.row_ids.data_ptr(), _lib.ptr(ts_U), float(discrete), sp, lds,
+        offset_noise, ts.data_ptr(), _lib.ptr(ca), _lib.ptr(cb), noise_mode, nz, ldn, drop_mode, kp, ldkp, drop_p, seed,
+        offset_prep, cat.weight.data_ptr(), cat.bias.data_ptr(), emb.weight.data_ptr(), emb.bias.data_ptr(), E, B, I,
+        xin.data_ptr(), xin.stride(0), xt.data_ptr(), xt.stride(0), temb.data_ptr(), x0bits.data_ptr(), x0bits.stride(0),
+        clsbits.data_ptr(), clsbits.stride(0), st))
+    return batch, noise, keep, drop_mode
+
+
+def cat_grad_bits(lib, dxin, xt, x0bits, clsbits, drop_mode, keep, drop_p, seed, offset, B, I, ws, ws_bytes, gw, gb, st):
+    """gdmcf_cat_grad_bits_f32: the cat layer's four gradients with the one-hot pair taken from the two bitmaps the CSR-fed
+    builder wrote (same arithmetic as gdmcf_cat_grad_f32 on the [B, 2I] image)."""
+    (kp, ldkp) = _pl(keep)
+    _lib.check(lib.gdmcf_cat_grad_bits_f32(
+        dxin.data_ptr(), dxin.stride(0), xt.data_ptr(), xt.stride(0), x0bits.data_ptr(), x0bits.stride(0), clsbits.data_ptr(),
+        clsbits.stride(0), drop_mode, kp, ldkp, drop_p, seed, offset, B, I, ws.data_ptr(), ws_bytes, gw.data_ptr(), gb.data_ptr(),
+        st))
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # dense layers.  W is [N, K] row-major (rows at least K apart), `bufs` lends the split-K workspace.
 # ------------------------------------------------------------------------------------------------------------------

@@ -362,7 +362,7 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
             # draws the noise with torch.randn_like of the dense rows, unless the noise is given or there is none.)
             sparse_ok = (self.mean_type == ModelMeanType.START_X and not model.norm and x_start.csr.values is None
                          and (self.rng == "philox" or noise is not None or self.noise_scale == 0.0)
-                         and getattr(model, "csr_rows", True))  # (DNNCat: no CSR-fed input builder)
+                         and getattr(model, "csr_rows", True))  # (DNNCat: CSR-fed only when built with csr_rows=True)
             if sparse_ok:
                 csr_batch = x_start
             else:

@@ -604,6 +604,29 @@ size_t gdmcf_cat_grad_ws_bytes(int B, int I);
 int gdmcf_cat_grad_f32(const float* dxin, int64_t lddx, const float* xt, int64_t ldxt, const float* xU, int64_t ldu, int drop_mode,
                        const uint8_t* keep, int64_t ldkeep, float drop_p, uint64_t seed, uint64_t offset, int B, int I, void* ws,
                        size_t ws_bytes, float* grad_w, float* grad_b, void* stream);
+/* The cat layer fed from device CSR rows: row b of the batch is row rows[b] of a {0,1} CSR matrix (indptr int64, indices int32).
+ * gdmcf_cat_prep_input_csr_f32 is ONE launch for gdmcf_densify_rows_f32, gdmcf_onehot_noise_f32(offset = offset_noise) and
+ * gdmcf_cat_prep_input_f32(offset = offset_prep): for equal inputs, seed and offsets it leaves the same bits over the whole
+ * [B, ldxin] extent of xin, in xt_out[:, 0:I] and in temb_out; neither the dense rows nor the [B, 2I] image exist.  The classes
+ * are `sampled` (uint8 [B, lds], non-zero = class 1; ts_U may be NULL) or drawn from ts_U [B] with gdmcf_onehot_noise_f32's
+ * counters.  It also writes two bitmaps (both required; word c >> 5, bit c & 31 = column c, bits behind I are 0, words behind
+ * ceil(I/32) are not written): x0bits_out, the rows -- the target gdmcf_linear_loss_fwd_bits_f32 reads -- and clsbits_out, the
+ * classes.  Both offsets are by-value: the entry refuses to run while a graph step state is bound.                              */
+int gdmcf_cat_prep_input_csr_f32(const int64_t* indptr, const int32_t* indices, const int64_t* rows, const int64_t* ts_U,
+                                 float discrete, const uint8_t* sampled, int64_t lds, uint64_t offset_noise, const int64_t* ts,
+                                 const float* ca, const float* cb, int noise_mode, const float* noise, int64_t ldn, int drop_mode,
+                                 const uint8_t* keep, int64_t ldkeep, float drop_p, uint64_t seed, uint64_t offset_prep,
+                                 const float* cat_w, const float* cat_b, const float* emb_w, const float* emb_b, int E, int B, int I,
+                                 float* xin, int64_t ldxin, float* xt_out, int64_t ldxt, float* temb_out, uint32_t* x0bits_out,
+                                 int64_t ldx0bits, uint32_t* clsbits_out, int64_t ldclsbits, void* stream);
+/* gdmcf_cat_grad_f32 with the one-hot pair taken from the two bitmaps of gdmcf_cat_prep_input_csr_f32 instead of xU:
+ * xU[b,2i] = !x0 && !class, xU[b,2i+1] = x0 && class.  Same mapping, partials (gdmcf_cat_grad_ws_bytes) and reduction.
+ * The four results equal gdmcf_cat_grad_f32's on the corresponding image bit for bit (the fused multiply-adds of the sum
+ * dz * x_t are written out as the dense kernel is compiled, csrc/cat.hip: cat_grad_fused).                                     */
+int gdmcf_cat_grad_bits_f32(const float* dxin, int64_t lddx, const float* xt, int64_t ldxt, const uint32_t* x0bits, int64_t ldx0bits,
+                            const uint32_t* clsbits, int64_t ldclsbits, int drop_mode, const uint8_t* keep, int64_t ldkeep,
+                            float drop_p, uint64_t seed, uint64_t offset, int B, int I, void* ws, size_t ws_bytes, float* grad_w,
+                            float* grad_b, void* stream);
 
 #ifdef __cplusplus
 }

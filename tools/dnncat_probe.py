@@ -2,16 +2,21 @@
 leg for this backbone; this probe is its measurement).
 
     python tools/dnncat_probe.py [--steps 20] [--warmup 3] [--rounds 5] [--legs hip,eager] [--out profiles/dnncat_probe_yelp.json]
+    python tools/dnncat_probe.py --legs hip,hip_csr --rounds 5 --out profiles/dnncat_csr_probe_yelp.json
 
 Yelp shape (34 395 items, hid 1000, batch 400), T = 5, f32, x0 target, separate AdamW pass.  After the same untimed clock
 pre-heat as bench.py (clock_preheat) the legs alternate for `rounds` rounds, each `warmup` untimed steps then `steps` timed ones:
   hip:   gdmcf_amd.DNNCat under GaussianDiffusionDiscrete(CatOneHot=True): zero_grad -> training_losses -> mean -> backward ->
          FusedAdamW.step (gdmcf_onehot_noise_f32, gdmcf_cat_prep_input_f32, the dense layers, the dxin product, gdmcf_cat_grad_f32);
+  hip_csr: the same model built with csr_rows=True (its own instance, optimiser and diffusion), the same row ids handed over as
+         dcsr.batch(ids): gdmcf_cat_prep_input_csr_f32, the bitmap loss epilogue, gdmcf_cat_grad_bits_f32 -- no dense batch, no
+         [B, 2I] image (`hip` is fed rows densified outside the timed region, so the difference does not include the densify pass);
   eager: the reference's formulas as torch operations on the same GPU -- q_sample, the [B, I, 3] cat, Linear(3, 1), dropout, the
          MLP, the SNR-weighted row mse, autograd, torch.optim.AdamW.  Its one-hot image comes from the same HIP kernel (the
          reference's per-item multinomial is not what is being compared).
 Prints one JSON document: ms per step is the median over the rounds, *_legs_ms every round, *_spread_ms = max - min of the
-rounds (the noise a difference has to exceed).  --legs hip runs that leg alone, for a per-kernel profile of it."""
+rounds (the noise a difference has to exceed); one_hot_image_allocated says per HIP leg whether its engine holds the [B, 2I]
+buffer.  --legs hip (or hip_csr) runs that leg alone, for a per-kernel profile of it."""
 import argparse
 import json
 import os
@@ -68,8 +73,10 @@ def main(argv=None):
     B, hid, T, n_pool, emb = 400, 1000, 5, 4, 10
     indptr, indices, I = data.synth_csr("yelp", n_rows=n_pool * B, seed=0)
     dcsr = DeviceCSR(sp.csr_matrix((np.ones(len(indices), np.float32), indices, indptr), shape=(n_pool * B, I)), dev)
-    batches = [dcsr.rows(torch.arange(i * B, (i + 1) * B, device=dev)) for i in range(n_pool)]
+    id_pool = [torch.arange(i * B, (i + 1) * B, device=dev) for i in range(n_pool)]
     legs_on = args.legs.split(",")
+    batches = [dcsr.rows(ids) for ids in id_pool] if set(legs_on) & {"hip", "eager"} else None
+    csr_batches = [dcsr.batch(ids) for ids in id_pool]
     preheat = clock_preheat(lib, dev, args.preheat_seconds)
 
     torch.manual_seed(0)
@@ -77,6 +84,15 @@ def main(argv=None):
     diffusion = gdmcf_amd.GaussianDiffusionDiscrete(gdmcf_amd.ModelMeanType.START_X, "linear-var", 0.01, 0.001, 0.01, T, dev,
                                                     CatOneHot=True)
     opt = gdmcf_amd.FusedAdamW(model.parameters(), lr=1e-5, weight_decay=0.0)
+    model_csr = None
+    if "hip_csr" in legs_on:
+        rng_state = torch.get_rng_state()
+        torch.manual_seed(0)
+        model_csr = gdmcf_amd.DNNCat([I, hid], [hid, I], emb, csr_rows=True).to(dev).train()
+        torch.set_rng_state(rng_state)
+        diffusion_csr = gdmcf_amd.GaussianDiffusionDiscrete(gdmcf_amd.ModelMeanType.START_X, "linear-var", 0.01, 0.001, 0.01, T,
+                                                            dev, CatOneHot=True)
+        opt_csr = gdmcf_amd.FusedAdamW(model_csr.parameters(), lr=1e-5, weight_decay=0.0)
     eager = EagerDNNCat(I, hid, emb).to(dev).train()
     eopt = torch.optim.AdamW(eager.parameters(), lr=1e-5, weight_decay=0.0)
     ca, cb = diffusion._t32["sqrt_ab"], diffusion._t32["sqrt_1mab"]
@@ -87,6 +103,13 @@ def main(argv=None):
         loss = diffusion.training_losses(model, x, True)["loss"].mean()
         loss.backward()
         opt.step()
+        return loss
+
+    def hip_csr_step(x):
+        opt_csr.zero_grad()
+        loss = diffusion_csr.training_losses(model_csr, x, True)["loss"].mean()
+        loss.backward()
+        opt_csr.step()
         return loss
 
     def eager_step(x):
@@ -101,18 +124,18 @@ def main(argv=None):
         eopt.step()
         return loss
 
-    steps_of = {"hip": hip_step, "eager": eager_step}
+    steps_of = {"hip": hip_step, "hip_csr": hip_csr_step, "eager": eager_step}
     legs = {k: [] for k in legs_on}
     last = {}
     for _ in range(args.rounds):
         for leg in legs_on:
-            fn = steps_of[leg]
+            fn, pool = steps_of[leg], (csr_batches if leg == "hip_csr" else batches)
             for i in range(args.warmup):
-                fn(batches[i % n_pool])
+                fn(pool[i % n_pool])
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(args.steps):
-                last[leg] = fn(batches[i % n_pool])
+                last[leg] = fn(pool[i % n_pool])
             torch.cuda.synchronize()
             legs[leg].append(1e3 * (time.perf_counter() - t0) / args.steps)
     res = {}
@@ -123,8 +146,15 @@ def main(argv=None):
         res[f"{leg}_final_loss"] = float(last[leg])
     if "hip" in res and "eager" in legs:
         res["eager_over_hip"] = round(res["eager_ms_per_step"] / res["hip_ms_per_step"], 3)
-    out = dict(what="ms per training step of the DNNCat backbone, HIP path vs the same module in eager PyTorch, Yelp shape, f32, "
-                    "batch 400, T = 5, x0 target, separate AdamW pass; median over rounds of alternating legs",
+    if "hip" in legs and "hip_csr" in legs:
+        res["hip_minus_hip_csr_ms"] = round(res["hip_ms_per_step"] - res["hip_csr_ms_per_step"], 4)
+        res["larger_spread_ms"] = max(res["hip_spread_ms"], res["hip_csr_spread_ms"])
+        res["difference_exceeds_spread"] = bool(res["hip_minus_hip_csr_ms"] > res["larger_spread_ms"])
+    res["one_hot_image_allocated"] = {leg: any(getattr(b, "xU", None) is not None for b in m.engine._bufs.values())
+                                      for leg, m in (("hip", model), ("hip_csr", model_csr)) if leg in legs}
+    out = dict(what="ms per training step of the DNNCat backbone, Yelp shape, f32, batch 400, T = 5, x0 target, separate AdamW "
+                    "pass; legs: hip = dense rows, hip_csr = the same rows as a CsrBatch (csr_rows=True), eager = the same "
+                    "module in eager PyTorch; median over rounds of alternating legs",
                config=dict(n_items=I, hidden=hid, batch=B, T=T, steps=args.steps, warmup=args.warmup, rounds=args.rounds,
                            device=torch.cuda.get_device_name(dev)),
                clock_preheat=preheat, **res)
