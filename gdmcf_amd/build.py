@@ -12,12 +12,12 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["capi.hip", "dp_exchange.hip", "gemm_f32.hip", "gemm_bf16.hip", "gemm_split.hip", "gemm_small.hip", "gemm_dr.hip", "prep_input.hip", "noise.hip", "loss_tail.hip", "adamw.hip", "rows.hip", "reduce.hip", "linear.hip", "topk_spmm.hip", "spmm_bundle.hip", "score_topk.hip", "bpr.hip", "cat.hip"]
-HEADERS = ["common.h", "draws.h", "gemm_epilogue.h", os.path.join("..", "..", "include", "gdmcf_hip.h")]
+SOURCES = ["capi.hip", "dp_exchange.hip", "gemm_f32.hip", "gemm_bf16.hip", "gemm_split.hip", "gemm_small.hip", "gemm_dr.hip", "gemm_dr_tn.hip", "gemm_dr_fat.hip", "gemm_dr_kn.hip", "prep_input.hip", "noise.hip", "loss_tail.hip", "adamw.hip", "rows.hip", "reduce.hip", "linear.hip", "topk_spmm.hip", "spmm_bundle.hip", "score_topk.hip", "bpr.hip", "cat.hip"]
+HEADERS = ["common.h", "draws.h", "gemm_dr.h", "gemm_epilogue.h", os.path.join("..", "..", "include", "gdmcf_hip.h")]
 LIB = os.path.join(CSRC, "libgdmcf_hip.so")
-ASM_LINT = ("gemm_dr.hip", "gemm_split.hip")  # disassembled and run through lint_vmcnt + lint_store_data at every build
-STORE_LINT = ("gemm_f32.hip", "gemm_bf16.hip", "score_topk.hip")  # disassembled for lint_store_data only
-NO_SPILL = ("gemm_f32.hip", "gemm_bf16.hip", "gemm_split.hip", "gemm_dr.hip", "score_topk.hip", "cat.hip")  # kernels with uncounted asm loads (and score_topk.hip, whose
+ASM_LINT = ("gemm_dr_tn.hip", "gemm_split.hip")  # disassembled and run through lint_vmcnt + lint_store_data at every build
+STORE_LINT = ("gemm_f32.hip", "gemm_bf16.hip", "gemm_dr_fat.hip", "gemm_dr_kn.hip", "score_topk.hip")  # disassembled for lint_store_data only
+NO_SPILL = ("gemm_f32.hip", "gemm_bf16.hip", "gemm_split.hip", "gemm_dr_tn.hip", "score_topk.hip", "cat.hip")  # kernels with uncounted asm loads (and score_topk.hip, whose
 # register budget is the user fragments; cat.hip, whose two passes are meant to be bound by HBM alone): a spill is a build error
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -38,7 +38,7 @@ def _digest():
     return h.hexdigest()
 
 
-# ---- ISA lint for the register-streaming kernels (gemm_dr.hip: dr_tn_kernel) -----------------------------------------------
+# ---- ISA lint for the register-streaming kernels (gemm_dr_tn.hip: dr_tn_kernel) --------------------------------------------
 # Their operand ring lives in registers that asm buffer loads write long after the asm statement: hipcc believes the value is
 # there at once.  That is only safe while NO compiler-generated instruction reads or writes such a register other than the
 # MFMAs that consume it as an A / B operand -- a v_mov (PHI copy, e.g. after loop unswitching), a temporary placed in a slot
@@ -123,7 +123,8 @@ def lint_vmcnt(asm_text, only=None):
     v_mov / v_accvgpr / scratch copy hipcc inserted (PHI copies after loop unswitching, spills), an accumulator rotated over a
     slot that has not landed.  Path-insensitive: kernels whose waits are selected by the same predicate as their loads
     (gemm_f32.hip, gemm_bf16.hip: `if (more) load(); ... if (more) wait(N) else wait(0)`) raise false alarms and are not run
-    through it; gemm_dr.hip (all kernels) and gemm_split.hip verify cleanly and are checked at every build."""
+    through it; gemm_dr_tn.hip (both kernels) and gemm_split.hip verify cleanly and are checked at every build.  (gemm_dr_fat.hip and
+    gemm_dr_kn.hip have no inline-asm loads: every wait in them is hipcc's own.)"""
     bad, nk = [], 0
     for m in re.finditer(r"^(_Z\S+):[^\n]*\n(.*?)\n\s*s_endpgm", asm_text, flags=re.S | re.M):
         name, body = m.group(1), m.group(2)
@@ -293,26 +294,13 @@ def build(force=False, verbose=True):
                 if "Function Name:" in line:
                     name = line.split("Function Name:")[1].split()[0]
                 elif "VGPRs Spill:" in line and int(line.split("VGPRs Spill:")[1].split()[0]) > 0:
-                    # (dr_fat_kernel and dr_kn_kernel have no inline-asm loads: every wait in them is hipcc's own, a spilled register
-                    # -- lane constants saved across their 512-register loops -- is reloaded like any other value)
-                    if "dr_fat_kernel" not in (name or "") and "dr_kn_kernel" not in (name or ""):
-                        bad.append(name)
+                    bad.append(name)
             if bad:
                 raise RuntimeError(f"{src}: register spills in {len(bad)} kernel(s) with uncounted asm loads, e.g. {bad[0]}")
             err = err if ("warning:" in err or "error:" in err) else ""  # the remarks (and their source excerpts) are not news
         if verbose and err.strip():
             print(err, file=sys.stderr)
-        if src in STORE_LINT:  # (their waits are path-dependent, see lint_vmcnt: only the store-data hazard is checked here)
-            asm = os.path.join(CSRC, src.replace(".hip", ".lint.s"))
-            r2 = subprocess.run([hipcc] + FLAGS + ["-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", asm],
-                                capture_output=True, text=True)
-            if r2.returncode != 0:
-                raise RuntimeError(f"hipcc -S failed for {src}:\n{r2.stderr}")
-            bad = lint_store_data(open(asm).read())
-            os.remove(asm)
-            if bad:
-                raise RuntimeError(f"{src}: store data registers rewritten too early (lint_store_data):\n  " + "\n  ".join(bad[:12]))
-        if src in ASM_LINT:
+        if src in ASM_LINT or src in STORE_LINT:
             asm = os.path.join(CSRC, src.replace(".hip", ".lint.s"))
             r2 = subprocess.run([hipcc] + FLAGS + ["-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", asm],
                                 capture_output=True, text=True)
@@ -320,12 +308,13 @@ def build(force=False, verbose=True):
                 raise RuntimeError(f"hipcc -S failed for {src}:\n{r2.stderr}")
             text = open(asm).read()
             os.remove(asm)
-            bad = lint_vmcnt(text) + lint_store_data(text)
-            if src == "gemm_dr.hip":
+            bad = lint_store_data(text)
+            if src in ASM_LINT:  # (STORE_LINT only: waits that are path-dependent or hipcc's own, see lint_vmcnt)
+                bad += lint_vmcnt(text)
+            if src == "gemm_dr_tn.hip":
                 bad += lint_ring_registers(text)
             if bad:
-                raise RuntimeError(f"{src}: in-flight operand registers touched (see lint_vmcnt / lint_ring_registers):\n  "
-                                   + "\n  ".join(bad[:12]))
+                raise RuntimeError(f"{src}: ISA lint failed (lint_store_data / lint_vmcnt / lint_ring_registers):\n  " + "\n  ".join(bad[:12]))
         return obj
 
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:

@@ -193,7 +193,7 @@ struct GdGemm {
                // 2: operands split into three bfloat16 terms, six bf16 MFMAs per product block (gemm_split.hip)
 };
 
-// Split count the register-streaming input-gradient kernel (csrc/gemm_dr.hip: dr_kn_kernel) would use for C[M, N] = A[M, K] B[K, N],
+// Split count the register-streaming input-gradient kernel (csrc/gemm_dr_kn.hip: dr_kn_kernel) would use for C[M, N] = A[M, K] B[K, N],
 // or 0 when it does not take the product: gdmcf_linear_ws_bytes sizes the slab workspace with it.
 int gd_dr_kn_splits(int M, int N, int K);
 extern thread_local int t_gd_last_gemm;  // gdmcf_debug_last_gemm (include/gdmcf_hip.h)
@@ -204,7 +204,7 @@ int gd_gemm_launch(int layA, int layB, int epi, int shape_class, GdGemm& g, hipS
 int gd_gemm_bf16_launch(int layA, int layB, int epi, int shape_class, GdGemm& g, hipStream_t s);  // g.bf16 != 0
 int gd_gemm_split_launch(int layA, int layB, int epi, int shape_class, GdGemm& g, hipStream_t s);  // g.bf16 == 2 (gemm_split.hip)
 int gd_gemm_small_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s);  // degenerate shapes (gemm_small.hip)
-// direct-to-register f32 products (gemm_dr.hip): GD_DR_NOT_TAKEN = not a product / shape it handles, fall back to the LDS-tiled kernels
+// direct-to-register f32 products (gemm_dr.h, gemm_dr*.hip): GD_DR_NOT_TAKEN = not a product / shape it handles, fall back to the LDS-tiled kernels
 enum { GD_DR_NOT_TAKEN = 1 };
 int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s);
 // n (<= 4) fused-AdamW weight-gradient products (as gd_gemm_dr_launch takes them, GD_EPI_ADAMW) in ONE launch; GD_DR_NOT_TAKEN and

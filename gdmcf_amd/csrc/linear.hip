@@ -362,7 +362,7 @@ int gdmcf_linear_bwd_weight_adamw_f32(const float* dZ, int64_t lddz, const float
 int gdmcf_linear_bwd_weight_adamw_multi_f32(const GdDwAdamw* list, int n, void* stream) {
     GD_CHECK_ARG(n >= 0 && (n == 0 || list), "linear_bwd_weight_adamw_multi: bad list");
     hipStream_t s = (hipStream_t)stream;
-    constexpr int MAXN = 4;  // products per launch (gemm_dr.hip: DR_MULTI_MAX)
+    constexpr int MAXN = 4;  // products per launch (gemm_dr_tn.hip: DR_MULTI_MAX)
     for (int i0 = 0; i0 < n; i0 += MAXN) {
         const int k = n - i0 < MAXN ? n - i0 : MAXN;
         GdGemm g[MAXN];

@@ -202,7 +202,7 @@ def test_two_ranks_of_fifty_rows_match_the_oracle_on_the_global_batch(tmp_path):
                                    (130, 4100, 515)])
 def test_weight_gradient_product_every_element_against_float64(B, N, K):
     """gdmcf_linear_bwd_weight_f32 (dW = dZ^T A, db = sum_m rs_m dZ_m; reference main.py:350) through the C ABI at the shapes
-    the register-streaming kernel serves (csrc/gemm_dr.hip: operands travel in registers that hand-counted waits guard), EVERY
+    the register-streaming kernel serves (csrc/gemm_dr_tn.hip: operands travel in registers that hand-counted waits guard), EVERY
     element against a float64 product, three launches each: a compiler-inserted copy of such a register -- seen during
     development -- shows up as a handful of elements off by O(1) among tens of millions, which sampled checks miss.
     Also: bit-identical from launch to launch (dynamic tile queue, fixed arithmetic)."""
@@ -341,7 +341,7 @@ print("LDS-OK")
 @pytest.mark.parametrize("B,N,K,bits", [(400, 34395, 1000, 0), (400, 34395, 1000, 1), (400, 94949, 1000, 1), (240, 40000, 520, 0),
                                         (400, 200000, 2000, 1)])
 def test_output_layer_loss_product_on_the_fat_tile_kernel(B, N, K, bits):
-    """csrc/gemm_dr.hip dr_fat_kernel (round 4, the DEFAULT for batch-sized M: one 80 x 16 NB tile per wave, one wave per SIMD, one
+    """csrc/gemm_dr_fat.hip dr_fat_kernel (round 4, the DEFAULT for batch-sized M: one 80 x 16 NB tile per wave, one wave per SIMD, one
     pass) through the C ABI of the fused loss layer (reference models/DNN.py:83-86 + gaussian_diffusion.py:335): EVERY element
     of alpha * (h W^T + b) - target and the row sums of its square against float64 -- float and bitmap targets, the Yelp,
     Amazon-Book and stress widths (tile widths 11, 10, ... blocks; one and several rounds of tiles) and a ragged shape with a

@@ -1,6 +1,6 @@
 """GPU (-m gpu): launches of the library that overlap in time must not share hidden state ("latent bugs").
 
-* The register-streaming weight-gradient kernel (csrc/gemm_dr.hip: dr_tn_kernel, reference main.py:350) pulls its tiles from
+* The register-streaming weight-gradient kernel (csrc/gemm_dr_tn.hip: dr_tn_kernel, reference main.py:350) pulls its tiles from
   ticket counters in device memory.  The counters used to belong to the CALL SITE: two launches of the same entry point that
   overlap -- the two weight gradients of a step on two streams (GDMCF_GEMM_SIDE=1), two host threads -- drew from the same
   queues and each computed a subset of its tiles.  They now belong to the launch (dr_ticket_slot); here the two Yelp-shape

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Probe build of the library with one source recompiled under extra macros (the other objects are the product's):
 #   bash tools/build_variant.sh <tag> <source.hip> [-DMACRO=..]...   ->  tools/bin/libgdmcf_<tag>.so
+# (the GD_ADAMW_DBG / _ST / _LD and GD_NO_SNOP probes of dr_tn_adamw_kernel: <source.hip> = gemm_dr_tn.hip)
 # tools/fused_probe.py and friends load it with GDMCF_PROBE_LIB=tools/bin/libgdmcf_<tag>.so (probe scripts only; the product
 # always loads gdmcf_amd/csrc/libgdmcf_hip.so).
 set -e

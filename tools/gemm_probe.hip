@@ -1,7 +1,7 @@
 // Ablation / tuning harness for csrc/gemm_f32.hip (not part of the library).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DGD_PROBE_...] tools/gemm_probe.hip -o tools/gemm_probe_<variant>
 // Runs the five Yelp-shape products of the training step and prints ms / TFLOP/s per product.  GD_LDS=1 switches every
-// route of gemm_dr.hip off (DrRoutes): all products on the LDS-tiled kernels.
+// route of the gemm_dr*.hip kernels off (DrRoutes, gemm_dr.h): all products on the LDS-tiled kernels.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +19,9 @@ int gd_gemm_bf16_launch(int, int, int, int, GdGemm&, hipStream_t) { return GDMCF
 int gd_gemm_small_launch(int, int, int, GdGemm&, hipStream_t) { return GDMCF_E_UNSUPPORTED; }
 int gd_gemm_split_launch(int, int, int, int, GdGemm&, hipStream_t) { return GDMCF_E_UNSUPPORTED; }
 #include "../gdmcf_amd/csrc/gemm_dr.hip"
+#include "../gdmcf_amd/csrc/gemm_dr_tn.hip"
+#include "../gdmcf_amd/csrc/gemm_dr_fat.hip"
+#include "../gdmcf_amd/csrc/gemm_dr_kn.hip"
 void gd_prof_begin(int, double, hipStream_t) {}
 void gd_prof_end(hipStream_t) {}
 void gdmcf_set_error(const char* fmt, ...) {
