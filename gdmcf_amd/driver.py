@@ -6,7 +6,8 @@ on top of the HIP path.  Host glue only: batches in, metrics out.
 * `evaluate`         = main.py:267-310: p_sample -> history mask -> top-N -> computeTopNAccuracy.
   The reference moves a dense [B, I] row block to the device per batch and masks with
   `prediction[his_data.nonzero()] = -inf`; here the history stays CSR and the mask is applied inside the
-  top-k kernel.
+  top-k kernel.  `sparse=True` hands p_sample the rows as a CsrBatch as well: with sampling_steps == 0 the first layers of the
+  reverse loop then gather the rows' weight rows instead of multiplying a dense batch (GaussianDiffusion._sparse_reverse_ok).
 """
 import numpy as np
 import torch
@@ -47,18 +48,19 @@ def train_one_epoch(diffusion, model, optimizer, train_csr, batch_size, device, 
 
 @torch.no_grad()
 def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps, sampling_noise, batch_size,
-             device):
+             device, sparse=False):
     """Precision / Recall / NDCG / MRR @topN exactly as reference main.py:267-310.
 
     data_csr: rows fed to p_sample (the reference feeds the training rows); data_te: ground-truth CSR;
-    mask_his: CSR of interactions to exclude from the ranking."""
+    mask_his: CSR of interactions to exclude from the ranking.  sparse=True: p_sample receives each batch as a
+    data_utils.CsrBatch (never densified where the reverse loop takes sparse rows; densified inside p_sample otherwise)."""
     model.eval()
     n = mask_his.shape[0]
     predict_items = []
     dcsr = data_csr if isinstance(data_csr, DeviceCSR) else DeviceCSR(data_csr, device)
     for lo in range(0, n, batch_size):
         rows = np.arange(lo, min(lo + batch_size, n))
-        batch = dcsr.rows(torch.from_numpy(rows))
+        batch = dcsr.batch(torch.from_numpy(rows)) if sparse else dcsr.rows(torch.from_numpy(rows))
         kw = dict(index=torch.from_numpy(rows)) if getattr(diffusion, "indexIn", False) else {}
         prediction = diffusion.p_sample(model, batch, sampling_steps, sampling_noise, **kw)
         indptr, cols = evaluate_utils.csr_rows_to_device(mask_his, rows, device)

@@ -47,7 +47,6 @@ class DenoiserEngine(EngineBase):
         self._gemm_side = os.environ.get("GDMCF_GEMM_SIDE", "0") == "1"
         self._side2 = None
         self._side2_used = False
-        self._wt = {}  # id(weight) -> (weight, version, transposed copy): the reverse loop's hidden layers (see _transposed)
         self._wt_on = os.environ.get("GDMCF_FWD_WT", "1") == "1"
 
     def _grad_like(self, p):
@@ -168,29 +167,20 @@ class DenoiserEngine(EngineBase):
         return self._prep_csr(bufs, spec["csr"], spec["ts"], spec["ca"], spec["cb"], spec["noise"], spec["drop_mask"],
                               self.model.training)
 
-    def _transposed(self, w):
-        """W^T of a large weight, [in, out] row-major on 128-byte rows, cached per weight VERSION: the reverse-diffusion loop of an
-        evaluation runs many batches over frozen weights, and with the weight in this orientation the hidden layer's product runs
-        on the register-streaming kernel (gdmcf_linear_fwd_wt_f32): 0.224 -> 0.205 ms per step at the Yelp shape.  The transpose
-        itself (one pass over the weight) is paid once per version."""
-        rec = self._wt.get(id(w))
-        if rec is None or rec[0] is not w or rec[1] != w._version or rec[2].device != w.device:
-            n, k = w.shape
-            buf = torch.zeros(k, (n + 31) // 32 * 32, dtype=torch.float32, device=w.device)
-            buf[:, :n].copy_(w.detach().t())
-            rec = self._wt[id(w)] = (w, w._version, buf)
-        return rec[2]
-
-    def _hidden_forward(self, bufs, layers, B, xin=None, frozen=False):
+    def _hidden_forward(self, bufs, layers, B, xin=None, frozen=False, csr=None):
         """All layers but the last; returns the activation feeding the last layer.  frozen: the caller runs many forward passes over
-        unchanged weights (reverse loop): large layers go through their cached transposes."""
+        unchanged weights (reverse loop): large layers go through their cached transposes.  csr: the first-layer input holds the
+        binary, undropped rows of this data_utils.CsrBatch (first reverse step from x_0): the first layer is a gather of nnz rows of
+        its cached transpose instead of a product."""
         lib, st = self.lib, _lib.stream_ptr()
         A = bufs.xin if xin is None else xin
         for li, (w, bias, act) in enumerate(layers[:-1]):
             N, K = w.shape
             out = bufs.acts[li]
             self._use_weight(w)
-            if frozen and self._wt_on and self.gemm_dtype == "f32" and K >= 4096 and w.numel() >= (1 << 20):
+            if li == 0 and csr is not None:
+                self._gather_first_layer(bufs, csr, w, bias, act, A, B, out, st)
+            elif frozen and self._wt_on and self.gemm_dtype == "f32" and K >= 4096 and w.numel() >= (1 << 20):
                 wt = self._transposed(w)
                 _lib.check(lib.gdmcf_linear_fwd_wt_f32(A.data_ptr(), A.stride(0), wt.data_ptr(), wt.stride(0), bias.data_ptr(), act, B, N, K,
                                                        out.data_ptr(), out.stride(0), bufs.ws.data_ptr(), bufs.ws_bytes, st))
@@ -382,7 +372,11 @@ class DenoiserEngine(EngineBase):
                       capture=None, draw_noise=None):
         """tabs32: dict of float32 device tables [T] (sqrt_ab, sqrt_1mab, c1, c2, r1, r2, sigma).  draw_noise(like) -> [B, I]
         float32 N(0,1): the reverse loop's th.randn_like(x_t) (reference :210-217); default: gdmcf_randn_f32 on the engine's
-        Philox seed (stream 7, one offset per draw)."""
+        Philox seed (stream 7, one offset per draw).
+        x_start may be a data_utils.CsrBatch where GaussianDiffusion._sparse_reverse_ok holds (steps == 0, binary rows, no
+        F.normalize, no dropout, float32 products): x_T = x_0 is written into the first-layer input by the CSR-fed builder (the
+        posterior epilogue needs the dense x_t), and the first step's first hidden layer is a gather of the rows' few dozen
+        weight rows (gdmcf_gather_fwd_f32) instead of the [B, I + E] x [I + E, N] product.  Steps T-2 .. 0 run as on dense rows."""
         m, lib = self.model, self.lib
         if draw_noise is None:
             def draw_noise(like):
@@ -390,6 +384,11 @@ class DenoiserEngine(EngineBase):
                 return _lib.philox_randn(like.shape, like.device, self.seed, self.offset, 7)
         self.flush_weight_waiters()
         B, dev, I = x_start.shape[0], x_start.device, self.I
+        from .data_utils import CsrBatch
+        csr = x_start if isinstance(x_start, CsrBatch) else None
+        if csr is not None and (steps != 0 or m.norm or self.gemm_dtype != "f32" or csr.csr.values is not None):
+            raise RuntimeError("gdmcf_amd: the reverse loop takes CSR rows only for steps == 0, binary rows, norm=False and "
+                               "float32 products (GaussianDiffusion.p_sample densifies the rest)")
         layers = self._layers()
         bufs = self.buffers(B, dev)
         self._shadows_on(bufs, layers)
@@ -441,7 +440,10 @@ class DenoiserEngine(EngineBase):
             # straight into the other buffer's first I columns, a tiny kernel adds that step's embedding columns
             # (no per-step input builder: 2 x 55 MB less traffic per step at Yelp shape).
             cur, nxt = bufs.xin, bufs.xin2
-            keep.append(self._prep(bufs, x_start, t_vec, ca, cb, noise0, None, False, xin=cur))  # x_T
+            if csr is not None:
+                keep.append(self._prep_csr(bufs, csr, t_vec, None, None, None, None, False))  # x_T = x_0, into bufs.xin
+            else:
+                keep.append(self._prep(bufs, x_start, t_vec, ca, cb, noise0, None, False, xin=cur))  # x_T
             bufs.xin_ones = False  # (gdmcf_dnn_emb_cols_f32 below rewrites the padding columns with zeros)
             for n, i in enumerate(range(T - 1, -1, -1)):
                 ts = step_ts[i]
@@ -449,7 +451,7 @@ class DenoiserEngine(EngineBase):
                                                       m.emb_layer.bias.data_ptr(), self.E, B, I, cur.data_ptr(),
                                                       cur.stride(0), bufs.temb.data_ptr(), st))
                 keep.append(ts)
-                A = self._hidden_forward(bufs, layers, B, xin=cur, frozen=True)
+                A = self._hidden_forward(bufs, layers, B, xin=cur, frozen=True, csr=csr if n == 0 else None)
                 out = torch.empty(B, I, dtype=torch.float32, device=dev) if i == 0 else None
                 posterior(i, n, A, cur, out if out is not None else nxt)
                 cur, nxt = nxt, cur

@@ -159,6 +159,22 @@ def linear_fwd(lib, bufs, A, W, bias, act, B, N, K, out, st):
                                         bufs.ws_bytes, st))
 
 
+def gather_fwd(lib, pre, base, batch, table, I, a, tblE, E, bias, act, B, N, out, st):
+    """gdmcf_gather_fwd_f32: out = act(pre + base + the rows of `table` [I, .] named by the CSR rows of `batch`
+    (data_utils.CsrBatch, or None: no gather) + a @ tblE + bias) -- a first layer on a sparse binary input as a sum of rows of the
+    transposed weight.  `a` [B, E]: the embedding columns of the builder's xin, read in place; `tblE` [E, .]: their rows of the
+    transposed weight.  Every operand but `out` may be None."""
+    (p, ldp), (tb, ldt), (ap, lda), (te, ldte), (o, ldo) = _pl(pre), _pl(table), _pl(a), _pl(tblE), _pl(out)
+    c = batch.csr if batch is not None else None
+    if c is None:
+        tb, ldt = None, 0
+    if E == 0:
+        ap, lda, te, ldte = None, 0, None, 0
+    _lib.check(lib.gdmcf_gather_fwd_f32(
+        p, ldp, _lib.ptr(base), c.indptr.data_ptr() if c is not None else None, c.indices.data_ptr() if c is not None else None,
+        batch.row_ids.data_ptr() if c is not None else None, tb, ldt, I, ap, lda, te, ldte, E, _lib.ptr(bias), act, B, N, o, ldo, st))
+
+
 def linear_bwd_input(lib, bufs, dz, W, rs, A_prev, act_prev, B, N, K, d_prev, st):
     """d_prev = ((rs .) dz @ W) * act_prev'(A_prev)"""
     (z, ldz), (w, ldw), (a, lda), (d, ldd) = _pl(dz), _pl(W), _pl(A_prev), _pl(d_prev)
@@ -288,6 +304,7 @@ class EngineBase:
         self.offset = 0
         self._bufs = {}
         self._saved = None
+        self._wt = {}  # id(weight) -> (weight, version, transposed copy): see _transposed
         # data parallel: called as grad_sink(param, grad) the moment a gradient's kernels are enqueued, so the
         # all-reduce of the big weight gradients overlaps the rest of the backward (gdmcf_amd/parallel.py).
         # When set, the engine assigns .grad itself and hands autograd None for that parameter.
@@ -315,6 +332,29 @@ class EngineBase:
             # (rows of a weight may lie further apart than its columns: FusedAdamW.fuse_into_backward seats them on 128-byte lines)
             if not (w.stride(1) == 1 and w.stride(0) >= w.shape[1] and b.is_contiguous() and w.dtype == torch.float32):
                 raise RuntimeError(f"gdmcf_amd: {what} must be float32 with unit column stride")
+
+    def _transposed(self, w):
+        """W^T of a large weight, [in, out] row-major on 128-byte rows, cached per weight VERSION: the reverse-diffusion loop of an
+        evaluation runs many batches over frozen weights, and with the weight in this orientation the hidden layer's product runs
+        on the register-streaming kernel (gdmcf_linear_fwd_wt_f32): 0.224 -> 0.205 ms per step at the Yelp shape.  The transpose
+        itself (one pass over the weight) is paid once per version.  The same copy is the table of gdmcf_gather_fwd_f32 (the first
+        reverse step from CSR rows: its rows are the items', then the E embedding columns')."""
+        rec = self._wt.get(id(w))
+        if rec is None or rec[0] is not w or rec[1] != w._version or rec[2].device != w.device:
+            n, k = w.shape
+            buf = torch.zeros(k, (n + 31) // 32 * 32, dtype=torch.float32, device=w.device)
+            buf[:, :n].copy_(w.detach().t())
+            rec = self._wt[id(w)] = (w, w._version, buf)
+        return rec[2]
+
+    def _gather_first_layer(self, bufs, batch, w, bias, act, xin, B, out, st):
+        """act([x_0 | emb] @ w^T + bias) for the binary, undropped CSR rows of `batch` as a sum of rows of the cached w^T
+        (gdmcf_gather_fwd_f32) instead of the [B, I + E] x [I + E, N] product; `xin` holds this step's embedding columns."""
+        N, I, E = w.shape[0], self.I, self.E
+        wt = self._transposed(w)
+        emb_cols = (xin.data_ptr() + 4 * I, xin.stride(0))
+        gather_fwd(self.lib, None, None, batch, wt, I, emb_cols, (wt.data_ptr() + 4 * I * wt.stride(0), wt.stride(0)), E, bias, act,
+                   B, N, out, st)
 
     def _shared_buffers(self, b, B, device, n_loss, n_first, weights):
         """The buffers every backbone has: embedding columns, loss layer, loss tail, embedding backward, GEMM workspace.

@@ -263,12 +263,28 @@ class GaussianDiffusion(nn.Module):
         return {"loss": loss}
 
     # -- sampling --------------------------------------------------------------------------------
+    def _sparse_reverse_ok(self, model, x_start, steps):
+        """Whether a reverse loop may keep the data_utils.CsrBatch `x_start` sparse: x_T must be x_0 itself (steps == 0), binary
+        (all values 1, no F.normalize) and undropped, so that the first layers' products are sums of weight rows
+        (gdmcf_gather_fwd_f32); float32 products only; the backbones whose engines take the rows (exact types: DNNCat and the
+        GCN backbone densify).  Anything else: p_sample calls x_start.dense() and runs the dense route, to the bit."""
+        from .onehot import DNNOneHot
+        from .onehot_embedding import DNNOneHotEmbedding
+        return (steps == 0 and self.noise_scale != 0.0 and not model.norm and x_start.csr.values is None
+                and getattr(model, "gemm_dtype", "f32") == "f32" and (not model.training or model.drop.p == 0)
+                and type(model) in (DNN, DNNOneHot, DNNOneHotEmbedding))
+
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,
                  capture=None):
+        """x_start: dense [B, n_items] rows, or a data_utils.CsrBatch -- kept sparse where _sparse_reverse_ok holds (the first
+        reverse step's first hidden layer is then a gather of the rows' weight rows), densified here otherwise."""
         assert steps <= self.steps, "Too much steps in inference."
         _lib.require_gpu(x_start, "x_start")
         if not isinstance(model, DNN):
             raise TypeError("gdmcf_amd.GaussianDiffusion.p_sample needs a gdmcf_amd.DNN denoiser")
+        from .data_utils import CsrBatch
+        if isinstance(x_start, CsrBatch) and not self._sparse_reverse_ok(model, x_start, steps):
+            x_start = x_start.dense()
         if self.noise_scale == 0.0:
             x_t = x_start
             with torch.no_grad():
@@ -392,21 +408,39 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         assert steps <= self.steps, "Too much steps in inference."
         _lib.require_gpu(x_start, "x_start")
         model = self._onehot_model(model)
+        from .data_utils import CsrBatch
+        csr_batch = None
+        if isinstance(x_start, CsrBatch):
+            if self._sparse_reverse_ok(model, x_start, steps):
+                csr_batch = x_start
+            else:
+                x_start = x_start.dense()
         B, dev = x_start.shape[0], x_start.device
         with torch.no_grad():
-            x0 = x_start.float().contiguous()
-            if steps == 0:
+            if csr_batch is not None:
+                # rows left sparse (steps == 0): neither the [B, 2I] image nor the second branch's input is built -- a handle
+                # carries that branch's step-independent pre-activation, gathered once; the first step's x_t is the rows themselves
+                x0 = None
+                x_tU, keep = model.engine.onehot_rows_sparse(csr_batch), None
+                x_t = csr_batch
+            elif steps == 0:
+                x0 = x_start.float().contiguous()
                 # the noiseless one-hot image: every true bit survives (sampled == the rows themselves)
                 x_tU, keep = model.engine.onehot_rows(x0, None, (x0 != 0).to(torch.uint8), self.discrete)
                 x_t = x0
             else:
+                x0 = x_start.float().contiguous()
                 t = torch.full((B,), steps - 1, dtype=torch.int64, device=dev)
                 x_tU, keep = model.engine.onehot_rows(x0, t, sampled0, self.discrete)
                 x_t = self.q_sample(x0, t, noise0) if self.noise_scale != 0.0 else x0
             graph = degp = None
             if self.indexIn and self.noise_scale != 0.0:
-                graph = torch.zeros(B, x0.shape[1], dtype=torch.uint8, device=dev)
-                deg = x0.sum(dim=1)
+                graph = torch.zeros(B, x_start.shape[1], dtype=torch.uint8, device=dev)
+                if csr_batch is not None:  # binary rows: the row sums are the row lengths, exact in float32 either way
+                    ip = csr_batch.csr.indptr
+                    deg = (ip[csr_batch.row_ids + 1] - ip[csr_batch.row_ids]).to(torch.float32)
+                else:
+                    deg = x0.sum(dim=1)
                 degp = (deg / deg.max()).float().contiguous()  # :710-711 (a batch without any interaction gives nan, as there)
             eps_mode = self.mean_type == ModelMeanType.EPSILON
             if self.mean_type not in (ModelMeanType.START_X, ModelMeanType.EPSILON):
@@ -441,7 +475,10 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
                 if sampling_noise and i != 0:
                     z = step_noise[n] if step_noise is not None else self._draw_noise(x_t, stream_id=7)
                     po.update(sigma=tabs["sigma"][i], z=z.float().contiguous())
-                x_in = x_t if (x_t.dtype == torch.float32 and x_t.is_contiguous()) else x_t.float().contiguous()
+                if isinstance(x_t, CsrBatch):  # (first step of the sparse route: the engine's CSR-fed builder densifies into xin1)
+                    x_in = x_t
+                else:
+                    x_in = x_t if (x_t.dtype == torch.float32 and x_t.is_contiguous()) else x_t.float().contiguous()
                 noisy = sampling_noise and i != 0
                 if fused_posterior:
                     if capture is not None and noisy:

@@ -12,8 +12,13 @@ by column range.
 Training rows may arrive as a `data_utils.CsrBatch` (x0 target, no F.normalize): branch 1 is then fed by
 `gdmcf_dnn_prep_input_csr_f32`, branch 2 by `gdmcf_onehot_prep_input_csr_f32` (discrete noise, dropout and embedding columns in
 one launch), the loss target is the rows' bitmaps; no dense row and no [B, 2I] image exist, and the Philox positions are
-those of the dense route, so the two routes are the same run bit for bit.  The reverse loop and `GraphedTrainStep` do not
-take sparse rows.
+those of the dense route, so the two routes are the same run bit for bit.  `GraphedTrainStep` does not take sparse rows.
+
+The reverse loop takes a `CsrBatch` too where x_T is x_0 (`p_sample` with steps == 0, eval mode, binary rows, no F.normalize,
+float32 products; `DNNOneHot` and `DNNOneHotEmbedding`): the one-hot image is then the noiseless one for the whole loop, so the
+second branch's first product is `S0 + sum of D[i] over the row's items` plus the step's embedding terms.  That sum is gathered
+once per batch (`onehot_rows_sparse` -> `SparseXU`), and per step the layer is one `gdmcf_gather_fwd_f32` launch on it; the
+[B, 2I] image and xin2 do not exist, and branch 1's first product at the first step is a gather of the rows' weight rows.
 
 `gemm_dtype="bf16"` rounds the GEMM operands to bf16 on chip (from the f32 tensors: no bf16 shadows here).  Data parallel: the engine hands every gradient to `DataParallelStep`'s sink as soon as its
 kernels are enqueued (overlapped all-reduce, or the sharded optimiser with its all-gathers waited for at the end of the
@@ -26,6 +31,27 @@ import torch.nn as nn
 from . import _lib
 from . import engine_core as core
 from .engine_core import EngineBase, _Bufs, _ceil64, with_precision
+
+
+class SparseXU:
+    """Stands in for the [B, 2I] one-hot image x_U during a reverse loop from CSR rows (OneHotEngine.onehot_rows_sparse): the rows
+    (`batch`: data_utils.CsrBatch) and `P2` [B, h], the second branch's first-layer pre-activation without its embedding and bias
+    terms -- S0 + sum over the row's items of D[i] -- which is the same at every step of the loop."""
+
+    def __init__(self, batch, P2):
+        self.batch, self.P2 = batch, P2
+        self.shape, self.device, self.is_cuda = (batch.shape[0], batch.shape[1], 2), batch.device, batch.is_cuda
+
+
+class _OneHotBufs(_Bufs):
+    """xin2 [B, ld2], the second branch's first-layer input, is made on first use: a reverse loop from CSR rows never reads it
+    (110 MB at the Yelp shape)."""
+
+    def __getattr__(self, name):  # (only reached while the attribute does not exist yet)
+        if name != "xin2":
+            raise AttributeError(name)
+        self.xin2 = torch.zeros(self.xin1.shape[0], self.ld2, dtype=torch.float32, device=self.xin1.device)
+        return self.xin2
 
 
 class OneHotEngine(EngineBase):
@@ -47,10 +73,9 @@ class OneHotEngine(EngineBase):
         I, E = self.I, self.E
         br1, br2, out = self._chains()
         f32 = dict(dtype=torch.float32, device=device)
-        b = _Bufs()
+        b = _OneHotBufs()
         b.ld1, b.ld2 = _ceil64(I + E), _ceil64(2 * I + E)
         b.xin1 = torch.zeros(B, b.ld1, **f32)
-        b.xin2 = torch.zeros(B, b.ld2, **f32)
         b.xU = None  # the [B, 2I] one-hot image of the dense route: made on its first step (_xU), never by a run on CSR rows
         b.x0bits = None
         b.h1, b.h2 = br1[-1][0].shape[0], br2[-1][0].shape[0]
@@ -96,6 +121,40 @@ class OneHotEngine(EngineBase):
             _lib.stream_ptr()))
         return out, (x0, s8, ts_U)
 
+    def _branch2_tables(self, w):
+        """(D, S0, tblE) of the second branch's first weight w [N, 2I + E], cached per weight version like _transposed: with
+        the noiseless one-hot image of a binary row (column 2i + 1 set for the row's items, column 2i for every other item)
+        image @ w^T = S0 + sum over the row's items of D[i], D[i] = w^T[2i + 1] - w^T[2i] ([I, N32], each entry rounded once),
+        S0 = sum_i w^T[2i] ([N], summed in float64 and rounded once); tblE [E, N32]: the rows of w^T behind the image."""
+        rec = self._wt.get(("br2", id(w)))
+        if rec is None or rec[0] is not w or rec[1] != w._version or rec[2][0].device != w.device:
+            I, E = self.I, self.E
+            n = w.shape[0]
+            n32 = (n + 31) // 32 * 32
+            wd = w.detach()
+            even, odd = wd[:, 0:2 * I:2], wd[:, 1:2 * I:2]
+            D = torch.zeros(I, n32, dtype=torch.float32, device=w.device)
+            torch.sub(odd.t(), even.t(), out=D[:, :n])
+            S0 = even.sum(dim=1, dtype=torch.float64).to(torch.float32).contiguous()
+            tblE = torch.zeros(max(E, 1), n32, dtype=torch.float32, device=w.device)
+            tblE[:E, :n].copy_(wd[:, 2 * I:2 * I + E].t())
+            rec = self._wt[("br2", id(w))] = (w, w._version, (D, S0, tblE))
+        return rec[2]
+
+    def onehot_rows_sparse(self, batch):
+        """What stands in for onehot_rows(x0, None, x0 != 0, .) -- the noiseless image of a reverse loop with steps == 0 -- when
+        the rows are a data_utils.CsrBatch of binary rows: no [B, 2I] image and no xin2; one gather launch
+        (gdmcf_gather_fwd_f32, base = S0) leaves the second branch's step-independent pre-activation in the handle."""
+        B, dev = batch.shape[0], batch.device
+        _, br2, _ = self._chains()
+        w = br2[0][0]
+        N = w.shape[0]
+        D, S0, _ = self._branch2_tables(w)
+        P2 = torch.empty(B, _ceil64(N), dtype=torch.float32, device=dev)
+        core.gather_fwd(self.lib, None, S0, batch, D, self.I, None, None, 0, None, 0, B, N, P2, _lib.stream_ptr())
+        self.sparse_gathers = getattr(self, "sparse_gathers", 0) + 1  # (branch-2 gathers launched: one per loop, not per step)
+        return SparseXU(batch, P2)
+
     def _chain_forward(self, bufs, chain, acts, A, B, last_out):
         """A chain of layers from A: layer li writes acts[li], the one after the last of `acts` writes `last_out`."""
         lib, st = self.lib, _lib.stream_ptr()
@@ -105,11 +164,30 @@ class OneHotEngine(EngineBase):
             core.linear_fwd(lib, bufs, A, w, bias, act, B, N, K, out, st)
             A = out
 
-    def _hidden(self, bufs, br1, br2, out, B):
-        """Both branches into hcat, then all out layers but the last; returns the activation feeding the last layer."""
-        ld = bufs.hcat.stride(0)
-        self._chain_forward(bufs, br1, bufs.acts1, bufs.xin1, B, bufs.hcat)
-        self._chain_forward(bufs, br2, bufs.acts2, bufs.xin2, B, (bufs.hcat.data_ptr() + 4 * bufs.h1, ld))
+    def _hidden(self, bufs, br1, br2, out, B, sparse=(None, None)):
+        """Both branches into hcat, then all out layers but the last; returns the activation feeding the last layer.
+        sparse = (CsrBatch or None, SparseXU or None), reverse loop from CSR rows: with the first, xin1 holds those binary rows
+        undropped and branch 1's first layer is a gather of their weight rows; with the second, branch 2's first layer is the
+        handle's P2 plus this step's embedding terms and bias (xin2 is not read).  Both through gdmcf_gather_fwd_f32."""
+        ld, st = bufs.hcat.stride(0), _lib.stream_ptr()
+        x_csr, xU = sparse
+        hcat2 = (bufs.hcat.data_ptr() + 4 * bufs.h1, ld)
+        if x_csr is not None:
+            w, bias, act = br1[0]
+            o = bufs.acts1[0] if len(br1) > 1 else bufs.hcat
+            self._gather_first_layer(bufs, x_csr, w, bias, act, bufs.xin1, B, o, st)
+            self._chain_forward(bufs, br1[1:], bufs.acts1[1:], o, B, bufs.hcat)
+        else:
+            self._chain_forward(bufs, br1, bufs.acts1, bufs.xin1, B, bufs.hcat)
+        if xU is not None:
+            w, bias, act = br2[0]
+            o = bufs.acts2[0] if len(br2) > 1 else hcat2
+            _, _, tblE = self._branch2_tables(w)
+            core.gather_fwd(self.lib, xU.P2, None, None, None, self.I, (bufs.xin1.data_ptr() + 4 * self.I, bufs.xin1.stride(0)),
+                            tblE, self.E, bias, act, B, w.shape[0], o, st)
+            self._chain_forward(bufs, br2[1:], bufs.acts2[1:], o, B, hcat2)
+        else:
+            self._chain_forward(bufs, br2, bufs.acts2, bufs.xin2, B, hcat2)
         self._chain_forward(bufs, out[:-1], bufs.acts_out, bufs.hcat, B, None)
         return bufs.acts_out[len(out) - 2] if len(out) > 1 else bufs.hcat
 
@@ -282,19 +360,43 @@ class OneHotEngine(EngineBase):
     # -- plain forward (evaluation / reverse loop) ----------------------------------------------------------------------
     def _plain_inputs(self, x, timesteps, x_U, training, drop_mask, drop_mask_U):
         """What every forward_plain starts with: buffers, a new version, both branch inputs built from (x, t) and the
-        one-hot image x_U.  Returns (bufs, x, keepalive)."""
+        one-hot image x_U.  Returns (bufs, x, keepalive, sparse).
+        Reverse loop from CSR rows (GaussianDiffusionDiscrete.p_sample): x_U is a SparseXU handle -- no xin2 is built, branch 2
+        reads the handle -- and at the first step x is the CsrBatch itself: xin1 comes from the CSR-fed builder, and the dense
+        x_t the posterior epilogue needs is xin1's first I columns.  `sparse` = (that CsrBatch or None, the handle or None) is
+        what _hidden takes."""
+        from .data_utils import CsrBatch
         B, dev = x.shape[0], x.device
         bufs = self.buffers(B, dev)
         self.version += 1
         self._saved = None
         ts = timesteps.to(device=dev, dtype=torch.int64).contiguous()
-        x, xu = core._f32_rows(x), x_U.reshape(B, -1)
+        x_csr = x if isinstance(x, CsrBatch) else None
+        xU = x_U if isinstance(x_U, SparseXU) else None
+        if (x_csr is not None or xU is not None) and (
+                (training and self.model.drop.p > 0) or drop_mask is not None or drop_mask_U is not None or self.model.norm
+                or self.gemm_dtype != "f32" or (x_csr is not None and (xU is None or x_csr.csr.values is not None))):
+            raise RuntimeError(f"gdmcf_amd.{type(self.model).__name__}: CSR rows enter the plain forward only undropped, binary, "
+                               "with norm=False and float32 products (GaussianDiffusionDiscrete.p_sample densifies the rest)")
+        if x_csr is not None:
+            if bufs.x0bits is None:
+                bufs.x0bits = torch.zeros(B, (self.I + 31) // 32, dtype=torch.int32, device=dev)
+            self.offset += 1
+            m = self.model
+            keep1 = core.prep_input_csr(self.lib, x_csr, ts, None, None, None, None, float(m.drop.p), False, self.seed, self.offset,
+                                        m.emb_layer, self.E, bufs.xin1, bufs.temb, bufs.x0bits, _lib.stream_ptr())
+            x = bufs.xin1[:, : self.I]
+        else:
+            x = core._f32_rows(x)
+            keep1 = self._prep_input(bufs, x, self.I, bufs.xin1, ts, None, None, None, drop_mask, training)
+        if xU is not None:
+            return bufs, x, (ts, keep1, xU), (x_csr, xU)
+        xu = x_U.reshape(B, -1)
         if xu.shape[1] != 2 * self.I:
             raise RuntimeError(f"gdmcf_amd.{type(self.model).__name__}: x_U must hold two columns per item")
         xu = core._f32_rows(xu)
-        keep = (self._prep_input(bufs, x, self.I, bufs.xin1, ts, None, None, None, drop_mask, training),
-                self._prep_input(bufs, xu, 2 * self.I, bufs.xin2, ts, None, None, None, drop_mask_U, training))
-        return bufs, x, (ts, keep)
+        keep = (keep1, self._prep_input(bufs, xu, 2 * self.I, bufs.xin2, ts, None, None, None, drop_mask_U, training))
+        return bufs, x, (ts, keep), (None, None)
 
     def _last_layer(self, bufs, A, W, bias, act, B, N, K, x_t, posterior):
         """The layer that produces the model output: plain (`out`), or -- reverse loop -- with the posterior mean of
@@ -317,9 +419,9 @@ class OneHotEngine(EngineBase):
     @with_precision
     def forward_plain(self, x, timesteps, x_U, training, drop_mask=None, drop_mask_U=None, posterior=None):
         br1, br2, out = self._chains()
-        bufs, x, keep = self._plain_inputs(x, timesteps, x_U, training, drop_mask, drop_mask_U)
+        bufs, x, keep, sparse = self._plain_inputs(x, timesteps, x_U, training, drop_mask, drop_mask_U)
         B = x.shape[0]
-        A = self._hidden(bufs, br1, br2, out, B)
+        A = self._hidden(bufs, br1, br2, out, B, sparse)
         w, bias, act = out[-1]
         res = self._last_layer(bufs, A, w, bias, act, B, w.shape[0], w.shape[1], x, posterior)
         del keep

@@ -56,10 +56,11 @@ class OneHotEmbeddingEngine(OneHotEngine):
         self._grow_workspace(b, B, device, [(self.I, b.D)])
         return b
 
-    def _scores_operands(self, bufs, br1, br2, B, index):
-        """ucat = [h, h_U, embedding_user(index)], then the row-normalised operands uhat, Vhat of the cosine scores."""
+    def _scores_operands(self, bufs, br1, br2, B, index, sparse=(None, None)):
+        """ucat = [h, h_U, embedding_user(index)], then the row-normalised operands uhat, Vhat of the cosine scores.
+        `sparse`: OneHotEngine._hidden's (reverse loop from CSR rows)."""
         lib, st, m = self.lib, _lib.stream_ptr(), self.model
-        self._hidden(bufs, br1, br2, [None], B)
+        self._hidden(bufs, br1, br2, [None], B, sparse)
         Wu, V = m.embedding_user.weight, m.embedding_item.weight
         ld = bufs.ucat.stride(0)
         _lib.check(lib.gdmcf_gather_rows_f32(Wu.data_ptr(), Wu.stride(0), index.data_ptr(), B, bufs.eu,
@@ -179,8 +180,8 @@ class OneHotEmbeddingEngine(OneHotEngine):
         br1, br2, _ = self._chains()
         B = x.shape[0]
         index = self._index_on(index, x.device, B)
-        bufs, x, keep = self._plain_inputs(x, timesteps, x_U, training, drop_mask, drop_mask_U)
-        self._scores_operands(bufs, br1, br2, B, index)
+        bufs, x, keep, sparse = self._plain_inputs(x, timesteps, x_U, training, drop_mask, drop_mask_U)
+        self._scores_operands(bufs, br1, br2, B, index, sparse)
         res = self._last_layer(bufs, bufs.uhat, bufs.Vhat, None, 0, B, self.I, bufs.D, x, posterior)
         del keep
         return res

@@ -232,6 +232,23 @@ int gdmcf_linear_fwd_f32(const float* A, int64_t lda, const float* W, int64_t ld
 int gdmcf_linear_fwd_wt_f32(const float* A, int64_t lda, const float* Wt, int64_t ldwt,
                             const float* bias, int act, int M, int N, int K, float* C, int64_t ldc,
                             void* ws, size_t ws_bytes, void* stream);
+/* A first hidden layer on a sparse {0,1} input row, as a sum of table rows: replaces the first nn.Linear (+tanh) of
+ * DNN.forward (models/DNN.py:79-81) and of both branches of DNNOneHot.forward (:446-455) where the layer's input is known to
+ * be binary and undropped -- the first reverse step of an evaluation with sampling_steps == 0 (x_T is x_0 itself), and the
+ * one-hot backbones' second branch at every reverse step (its image is the noiseless one-hot of x_0 for the whole loop):
+ *   out[b, n] = act( pre[b, n] + base[n] + sum_{j in CSR row rows[b]} table[j, n] + sum_{e < E} a[b, e] * tblE[e, n] + bias[n] )
+ * Every operand is optional (NULL), but one of pre / the CSR rows / a must be given.  pre [B, ldpre]; base, bias [N]; the CSR
+ * rows are rows[b] of (indptr int64, indices int32) as in gdmcf_dnn_prep_input_csr_f32, indptr == NULL: no gather; table
+ * [I, ldt] and tblE [E, ldte] are row-major with N-contiguous rows (W^T, the orientation gdmcf_linear_fwd_wt_f32 takes), 16-byte
+ * aligned, ldt and ldte multiples of 4 and >= N; a [B, lda] is read in place from the embedding columns of the builder's xin
+ * (a != NULL goes together with E > 0); act: 0 none, 1 tanh.  An index outside [0, I) adds nothing.
+ * Order of the sum, per element, all in float32: s = pre (or 0); s += base; s += table[j] for the row's indices in the order
+ * they are stored; s = fma(a[b, e], tblE[e], s) for e = 0 .. E-1; s += bias; then act.  One launch, no atomics, no workspace:
+ * the same bits on every run.  An empty row gives act(pre + base + embedding terms + bias).                                  */
+int gdmcf_gather_fwd_f32(const float* pre, int64_t ldpre, const float* base, const int64_t* indptr, const int32_t* indices,
+                         const int64_t* rows, const float* table, int64_t ldt, int I, const float* a, int64_t lda,
+                         const float* tblE, int64_t ldte, int E, const float* bias, int act, int B, int N, float* out, int64_t ldo,
+                         void* stream);
 /* Last layer fused with the per-row diffusion loss (gaussian_diffusion.py:335 mean_flat):
  *   out = A @ W^T + bias ;  diff[m,n] = alpha[m]*out[m,n] - target[m,n]   (alpha NULL -> 1)
  *   rowsum[m] = sum_n diff[m,n]^2  (deterministic two-stage reduction)
