@@ -8,9 +8,9 @@ from .evaluate_utils import computeTopNAccuracy, computeTopNAccuracy_device, mas
 from .lightgcn import BPRTrainer, LightGCN  # noqa: F401
 from .onehot import DNNOneHot  # noqa: F401
 from .cat import DNNCat  # noqa: F401
-from .onehot_embedding import DNNOneHotEmbedding  # noqa: F401
+from .onehot_embedding import DNNOneHotEmbedding, nt_xent_loss_grad  # noqa: F401
 from .onehot_gcn import DNNOneHotEmbeddingGCN  # noqa: F401
 from . import checkpoint, data_utils, driver, parallel  # noqa: F401
 
 __all__ = ["DNN", "timestep_embedding", "GaussianDiffusion", "GaussianDiffusionDiscrete", "ModelMeanType", "FusedAdamW", "computeTopNAccuracy",
-           "computeTopNAccuracy_device", "masked_topk", "score_topk", "print_results", "LightGCN", "BPRTrainer", "DNNOneHot", "DNNCat", "DNNOneHotEmbedding", "DNNOneHotEmbeddingGCN"]
+           "computeTopNAccuracy_device", "masked_topk", "score_topk", "print_results", "LightGCN", "BPRTrainer", "DNNOneHot", "DNNCat", "DNNOneHotEmbedding", "DNNOneHotEmbeddingGCN", "nt_xent_loss_grad"]

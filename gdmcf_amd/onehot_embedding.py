@@ -10,8 +10,12 @@ row-normalised operands u/|u| and V/|v| (`gdmcf_row_norms_f32` + `gdmcf_rowscale
 input / weight gradient GEMMs followed by the backward of the normalisation (`gdmcf_normalize_rows_bwd_f32`); the user
 rows move with `gdmcf_gather_rows_f32` / `gdmcf_scatter_add_rows_f32`; tanh' of the hidden activations takes the NT-Xent
 gradient as an addend (`gdmcf_tanh_bwd_f32`).  The NT-Xent term itself is a softmax over a [B, B] matrix of the two
-[B, hid] activations -- 0.01 % of the step's arithmetic -- and is evaluated with the reference's own torch expressions on
-the device (forward and gradient).
+[B, hid] activations -- 0.01 % of the step's arithmetic, but some three dozen eager launches and one stream
+synchronisation (`masked_select`) when it is evaluated with the reference's own torch expressions under autograd, which
+is what `ntxent="torch"` (the default) does.  `ntxent="fused"` takes the term and its gradient from
+`gdmcf_ntxent_fwd_f32` / `gdmcf_ntxent_bwd_f32` (csrc/ntxent.hip; four launches, no synchronisation, no autograd); they
+read the two column ranges of `ucat` and write the gradient into the persistent `closs_grad`.  `nt_xent_loss_grad` is the
+stand-alone face of the two entries.
 """
 import torch
 import torch.nn as nn
@@ -31,7 +35,40 @@ def nt_xent_loss(z1, z2, temperature=0.1, eps=1e-5):
     return -torch.log((torch.diag(sim) + eps) / negatives.sum(dim=1)).mean()
 
 
+NTXENT_MAX_B = 4096  # gdmcf_ntxent_*: 2 <= B <= 4096, 1 <= d <= 4096
+
+
+@torch.no_grad()
+def nt_xent_loss_grad(z1, z2, temperature=0.1, eps=1e-5, scale=None):
+    """(loss, dz1, dz2) of `nt_xent_loss(z1, z2, temperature, eps)` without autograd: gdmcf_ntxent_fwd_f32 and
+    gdmcf_ntxent_bwd_f32 (four launches, no host synchronisation, same bits in every run).  z1, z2: [B, d] float32 on the
+    GPU with unit column stride and any row stride (column ranges of a wider buffer are fine), 2 <= B <= 4096,
+    1 <= d <= 4096.  loss: a one-element float32 device tensor; dz1, dz2 [B, d]: scale * d loss / d z, with `scale` a
+    one-element float32 device tensor (None: 1)."""
+    for t, what in ((z1, "z1"), (z2, "z2")):
+        _lib.require_gpu(t, "nt_xent_loss_grad " + what)
+        if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
+            raise ValueError(f"nt_xent_loss_grad: {what} must be a 2-D float32 tensor with unit column stride")
+    if z1.shape != z2.shape:
+        raise ValueError("nt_xent_loss_grad: z1 and z2 must have the same shape")
+    if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1):
+        raise ValueError("nt_xent_loss_grad: scale must be a one-element float32 device tensor (or None)")
+    lib, st = _lib.load(), _lib.stream_ptr()
+    B, d = z1.shape
+    f32 = dict(dtype=torch.float32, device=z1.device)
+    nbytes = lib.gdmcf_ntxent_ws_bytes(B)
+    ws = torch.empty(max(nbytes // 4, 1), **f32)
+    loss, dz1, dz2 = torch.empty(1, **f32), torch.empty(B, d, **f32), torch.empty(B, d, **f32)
+    _lib.check(lib.gdmcf_ntxent_fwd_f32(z1.data_ptr(), z1.stride(0), z2.data_ptr(), z2.stride(0), B, d, float(temperature),
+                                        float(eps), ws.data_ptr(), nbytes, loss.data_ptr(), st))
+    _lib.check(lib.gdmcf_ntxent_bwd_f32(z1.data_ptr(), z1.stride(0), z2.data_ptr(), z2.stride(0), B, d, ws.data_ptr(), nbytes,
+                                        _lib.ptr(scale), dz1.data_ptr(), dz1.stride(0), dz2.data_ptr(), dz2.stride(0), st))
+    return loss, dz1, dz2
+
+
 class OneHotEmbeddingEngine(OneHotEngine):
+    last_ntxent_route = None  # "fused" / "torch": how the last training step evaluated the NT-Xent term
+
     def buffers(self, B, device):
         b = super().buffers(B, device)
         if hasattr(b, "ucat"):
@@ -55,6 +92,21 @@ class OneHotEmbeddingEngine(OneHotEngine):
         b.Vhat = torch.zeros(self.I, ldD, **f32)
         self._grow_workspace(b, B, device, [(self.I, b.D)])
         return b
+
+    def _ntxent_fused(self, B):
+        """B = 1 (the reference's expression then divides by an empty sum) and B > 4096 stay on the torch route."""
+        return self.model.ntxent == "fused" and 2 <= B <= NTXENT_MAX_B
+
+    def _ntxent_buffers(self, bufs, B):
+        """The fused route's workspace and its persistent gradient buffer, made on the route's first step."""
+        if getattr(bufs, "closs_grad", None) is None:
+            if bufs.h1 != bufs.h2:
+                raise RuntimeError("gdmcf_amd.DNNOneHotEmbedding: the NT-Xent term needs two hidden activations of one width")
+            f32 = dict(dtype=torch.float32, device=bufs.ucat.device)
+            bufs.ntxent_bytes = self.lib.gdmcf_ntxent_ws_bytes(B)
+            bufs.ntxent_ws = torch.empty(bufs.ntxent_bytes // 4, **f32)
+            bufs.closs_grad = torch.zeros(B, bufs.ucat.stride(0), **f32)  # [dz1 | dz2] in columns [0, h1), [h1, h12): tanh_bwd's addend
+        return bufs.closs_grad
 
     def _scores_operands(self, bufs, br1, br2, B, index, sparse=(None, None)):
         """ucat = [h, h_U, embedding_user(index)], then the row-normalised operands uhat, Vhat of the cosine scores.
@@ -102,14 +154,30 @@ class OneHotEmbeddingEngine(OneHotEngine):
         x0, target, alpha, rowdiv, keep = self._train_inputs(spec, bufs)
         self._scores_operands(bufs, br1, br2, B, index)
         loss = self._loss_layer(spec, bufs, B, bufs.uhat, bufs.Vhat, None, self.I, bufs.D, target, alpha, rowdiv)
-        # NT-Xent term between the two hidden activations (reference torch expressions, [B, B] work)
-        with torch.enable_grad():
-            h = bufs.ucat[:, : bufs.h1].detach().clone().requires_grad_(True)
-            hU = bufs.ucat[:, bufs.h1: bufs.h12].detach().clone().requires_grad_(True)
-            closs = nt_xent_loss(h, hU)
-            dh, dhU = torch.autograd.grad(closs, (h, hU))
-        self.last_closs = closs.detach()
-        self._saved = dict(B=B, bufs=bufs, chains=(br1, br2, out), index=index, closs_grad=torch.cat([dh, dhU], dim=1).contiguous(),
+        # NT-Xent term between the two hidden activations and its gradient ([B, B] work)
+        if self._ntxent_fused(B):
+            # csrc/ntxent.hip: reads the two column ranges of ucat, writes closs_grad; no clone, no autograd, no synchronisation
+            self.last_ntxent_route = "fused"
+            lib, st = self.lib, _lib.stream_ptr()
+            ld, cg = bufs.ucat.stride(0), self._ntxent_buffers(bufs, B)
+            z1, z2 = bufs.ucat.data_ptr(), bufs.ucat.data_ptr() + 4 * bufs.h1
+            closs = torch.empty((), dtype=torch.float32, device=dev)
+            _lib.check(lib.gdmcf_ntxent_fwd_f32(z1, ld, z2, ld, B, bufs.h1, 0.1, 1e-5, bufs.ntxent_ws.data_ptr(), bufs.ntxent_bytes,
+                                                closs.data_ptr(), st))
+            _lib.check(lib.gdmcf_ntxent_bwd_f32(z1, ld, z2, ld, B, bufs.h1, bufs.ntxent_ws.data_ptr(), bufs.ntxent_bytes, None,
+                                                cg.data_ptr(), cg.stride(0), cg.data_ptr() + 4 * bufs.h1, cg.stride(0), st))
+            self.last_closs = closs
+        else:
+            # the reference's torch expressions under autograd (masked_select synchronises the stream)
+            self.last_ntxent_route = "torch"
+            with torch.enable_grad():
+                h = bufs.ucat[:, : bufs.h1].detach().clone().requires_grad_(True)
+                hU = bufs.ucat[:, bufs.h1: bufs.h12].detach().clone().requires_grad_(True)
+                closs = nt_xent_loss(h, hU)
+                dh, dhU = torch.autograd.grad(closs, (h, hU))
+            self.last_closs = closs.detach()
+            cg = torch.cat([dh, dhU], dim=1).contiguous()
+        self._saved = dict(B=B, bufs=bufs, chains=(br1, br2, out), index=index, closs_grad=cg,
                            keepalive=(x0, keep, target, alpha, rowdiv, spec["pt"]))
         return loss + self.last_closs * 0.1  # reference :952-953 (after the history update and the division by pt)
 
@@ -192,9 +260,13 @@ class DNNOneHotEmbedding(DNNOneHot):
     `item_num=n_item, user_num=n_user` and sets `diffusion.indexIn = True`."""
 
     def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, item_num=2810, user_num=5949,
-                 gemm_dtype="f32"):
+                 gemm_dtype="f32", ntxent="torch"):
+        if ntxent not in ("torch", "fused"):
+            raise ValueError("ntxent must be 'torch' (the reference's expressions under autograd) or 'fused' (csrc/ntxent.hip), "
+                             "not %r" % (ntxent,))
         self._defer_init = True
         super().__init__(in_dims, out_dims, emb_size, time_type=time_type, norm=norm, dropout=dropout, gemm_dtype=gemm_dtype)
+        self.ntxent = ntxent  # how a training step evaluates the NT-Xent term and its gradient
         eu = self.in_layers[-1].out_features
         self.embedding_item = nn.Embedding(item_num, eu + eu + self.in_layers2[-1].out_features)
         self.embedding_user = nn.Embedding(user_num, eu)

@@ -140,7 +140,7 @@ class DNNOneHotEmbeddingGCN(DNNOneHotEmbedding):
     2; parse_args_util.py:24 defaults to 2) may also be given as `gcn_layers=`."""
 
     def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, item_num=2810, user_num=5949,
-                 args=None, gcn_layers=None, gemm_dtype="f32"):
+                 args=None, gcn_layers=None, gemm_dtype="f32", ntxent="torch"):
         self.args = args
         if gcn_layers is None:
             gcn_layers = int(getattr(args, "gcnLayerNum", 2))
@@ -150,7 +150,7 @@ class DNNOneHotEmbeddingGCN(DNNOneHotEmbedding):
             raise ValueError("gcnLayerNum must be 0, 1 or 2")
         self._gcn_layers_pending = gcn_layers
         super().__init__(in_dims, out_dims, emb_size, time_type=time_type, norm=norm, dropout=dropout, item_num=item_num,
-                         user_num=user_num, gemm_dtype=gemm_dtype)
+                         user_num=user_num, gemm_dtype=gemm_dtype, ntxent=ntxent)
         self.gcn_layers = gcn_layers
         d = self.embedding_item.weight.shape[1]
         if gcn_layers > 0:

@@ -645,6 +645,30 @@ int gdmcf_cat_grad_bits_f32(const float* dxin, int64_t lddx, const float* xt, in
                             float drop_p, uint64_t seed, uint64_t offset, int B, int I, void* ws, size_t ws_bytes, float* grad_w,
                             float* grad_b, void* stream);
 
+/* ---- NT-Xent term of the embedding backbones and its gradient (models/DNN.py:479-508, applied at :627-629; csrc/ntxent.hip) ----
+ * z1 [B, ld1], z2 [B, ld2]: the two hidden activations, d columns each (what follows a row's d elements is never read).
+ * float32 throughout, 2 <= B <= 4096 and 1 <= d <= 4096 (GDMCF_E_UNSUPPORTED otherwise).  No float atomics, every sum in one
+ * fixed order: same inputs, same bits.  No host synchronisation, copy or allocation.
+ *
+ * gdmcf_ntxent_fwd_f32 replaces `torch.mm(z1, z2.t()) / temperature`, the softmax, `torch.eye(..).bool()`, `masked_select(~mask)`
+ * (whose output size makes torch synchronise the stream), `.view(n, -1).sum(dim=1)`, `torch.diag`, the log and the mean of
+ * nt_xent_loss (DNN.py:484-508), in three launches:
+ *   S = z1 z2^T / temperature (v_mfma_f32_16x16x4_f32);  P = softmax of every row (row maximum subtracted, expf, divided by the
+ *   row sum);  neg_i = sum_{j != i} P_ij, summed over the off-diagonal entries themselves (never 1 - P_ii);
+ *   *loss_out = mean_i -log((P_ii + eps) / neg_i)                                                     (a device float)
+ * and leaves P and three numbers per row in ws (gdmcf_ntxent_ws_bytes(B) bytes, 16-byte aligned) for the gradient.
+ *
+ * gdmcf_ntxent_bwd_f32 replaces what autograd runs behind `closs` (the masked_scatter of masked_select's backward, the softmax
+ * backward, two torch.mm), in one launch, from the ws the forward entry left for the same z1, z2, B, d:
+ *   dS_ij = P_ij (g_ij - c_i) / temperature,  g_ii = -1 / (B (P_ii + eps)),  g_ij = 1 / (B neg_i),  c_i = sum_k g_ik P_ik
+ *   dz1 = scale[0] dS z2,  dz2 = scale[0] dS^T z1      (scale: a device float, NULL = 1; dz1, dz2 are OVERWRITTEN and must not
+ *                                                       alias z1, z2 or ws)                                               */
+size_t gdmcf_ntxent_ws_bytes(int B);
+int gdmcf_ntxent_fwd_f32(const float* z1, int64_t ld1, const float* z2, int64_t ld2, int B, int d, float temperature, float eps,
+                         void* ws, size_t ws_bytes, float* loss_out, void* stream);
+int gdmcf_ntxent_bwd_f32(const float* z1, int64_t ld1, const float* z2, int64_t ld2, int B, int d, const void* ws, size_t ws_bytes,
+                         const float* scale, float* dz1, int64_t lddz1, float* dz2, int64_t lddz2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
