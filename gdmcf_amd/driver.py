@@ -48,12 +48,14 @@ def train_one_epoch(diffusion, model, optimizer, train_csr, batch_size, device, 
 
 @torch.no_grad()
 def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps, sampling_noise, batch_size,
-             device, sparse=False):
+             device, sparse=False, latent=False):
     """Precision / Recall / NDCG / MRR @topN exactly as reference main.py:267-310.
 
     data_csr: rows fed to p_sample (the reference feeds the training rows); data_te: ground-truth CSR;
     mask_his: CSR of interactions to exclude from the ranking.  sparse=True: p_sample receives each batch as a
-    data_utils.CsrBatch (never densified where the reverse loop takes sparse rows; densified inside p_sample otherwise)."""
+    data_utils.CsrBatch (never densified where the reverse loop takes sparse rows; densified inside p_sample otherwise).
+    latent=True: p_sample(latent=True) -- the reverse loop in the first hidden layer's space where
+    GaussianDiffusion._latent_reverse_ok holds; composes with sparse=True."""
     model.eval()
     n = mask_his.shape[0]
     predict_items = []
@@ -62,6 +64,8 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
         rows = np.arange(lo, min(lo + batch_size, n))
         batch = dcsr.batch(torch.from_numpy(rows)) if sparse else dcsr.rows(torch.from_numpy(rows))
         kw = dict(index=torch.from_numpy(rows)) if getattr(diffusion, "indexIn", False) else {}
+        if latent:
+            kw["latent"] = True
         prediction = diffusion.p_sample(model, batch, sampling_steps, sampling_noise, **kw)
         indptr, cols = evaluate_utils.csr_rows_to_device(mask_his, rows, device)
         predict_items.append(masked_topk(prediction, topN[-1], indptr, cols))

@@ -369,8 +369,10 @@ class DenoiserEngine(EngineBase):
     # ------------------------------------------------------------------------------------------
     @with_precision
     def p_sample_loop(self, x_start, steps, T, tabs32, eps_mode, sampling_noise, noise0=None, step_noise=None,
-                      capture=None, draw_noise=None):
-        """tabs32: dict of float32 device tables [T] (sqrt_ab, sqrt_1mab, c1, c2, r1, r2, sigma).  draw_noise(like) -> [B, I]
+                      capture=None, draw_noise=None, latent=False):
+        """latent: carry the loop in the first hidden layer's space (_latent_loop; the caller has checked
+        GaussianDiffusion._latent_reverse_ok).
+        tabs32: dict of float32 device tables [T] (sqrt_ab, sqrt_1mab, c1, c2, r1, r2, sigma).  draw_noise(like) -> [B, I]
         float32 N(0,1): the reverse loop's th.randn_like(x_t) (reference :210-217); default: gdmcf_randn_f32 on the engine's
         Philox seed (stream 7, one offset per draw).
         x_start may be a data_utils.CsrBatch where GaussianDiffusion._sparse_reverse_ok holds (steps == 0, binary rows, no
@@ -394,6 +396,11 @@ class DenoiserEngine(EngineBase):
         self._shadows_on(bufs, layers)
         st = _lib.stream_ptr()
         self.version += 1
+        if latent:
+            if eps_mode or sampling_noise or capture is not None or m.norm or self.gemm_dtype != "f32":
+                raise RuntimeError("gdmcf_amd: the latent reverse loop takes the x0 target without sampling noise, capture or "
+                                   "F.normalize, in float32 products (GaussianDiffusion._latent_reverse_ok)")
+            return self._latent_loop(bufs, layers, x_start, csr, steps, T, tabs32, noise0)
         if bufs.xin2 is None:
             bufs.xin2 = torch.zeros_like(bufs.xin)
         if self.gemm_dtype == "bf16" and getattr(bufs, "sh_xin2", None) is None:
@@ -472,3 +479,58 @@ class DenoiserEngine(EngineBase):
         self._saved = None
         del keep
         return out
+
+    def _latent_loop(self, bufs, layers, x_start, csr, steps, T, tabs32, noise0):
+        """The reverse loop in the first hidden layer's space.  With the x0 target and no sampling noise the loop is linear in x_t
+        between two hidden activations, x_{t-1} = c1[t] (W_out a_t + b_out) + c2[t] x_t, so p_t = W1x x_t obeys
+            p_{t-1} = c1[t] (M a_t + v) + c2[t] p_t,    M = W1x W_out,  v = W1x b_out,    h_{t-1} = tanh(p_{t-1} + e_{t-1})
+        (one gdmcf_latent_step_f32 per step; M, v and the table e are _latent_operands).  Two item-wide products remain whatever T
+        is: the first layer on x_T into p (no time columns, no activation; a gather on CSR rows) and the output product of the last
+        step, x_0 = c1[0] (W_out a_0 + b_out) -- posterior_mean_coef2[0] is exactly 0.  x_T is built as in the item-space loop: same
+        builder, same Philox offsets."""
+        lib, st, I = self.lib, _lib.stream_ptr(), self.I
+        B, dev = x_start.shape[0], x_start.device
+        (w1, b1, act1), (w, bias, _) = layers[0], layers[-1]
+        h1, K = w1.shape[0], w.shape[1]
+        for wl, _, _ in layers:
+            self._use_weight(wl)
+        emb = self.model.emb_layer
+        ops = self._latent_operands(w1, b1, w, K, bias, T, (w1, b1, w, bias, emb.weight, emb.bias))
+        key = (id(tabs32), T, B)
+        if getattr(bufs, "lat_tabs_key", None) != key:
+            bufs.lat_tabs = {k: tabs32[k][:T, None].expand(T, B).contiguous() for k in ("c1", "c2")}
+            bufs.lat_tabs_key = key
+        c1, c2 = bufs.lat_tabs["c1"], bufs.lat_tabs["c2"]
+        if getattr(bufs, "lat_p", None) is None:
+            bufs.lat_p = torch.zeros(B, _ceil64(h1), dtype=torch.float32, device=dev)
+            bufs.lat_h = torch.zeros(B, _ceil64(h1), dtype=torch.float32, device=dev)
+        p = bufs.lat_p
+        t_vec = torch.full((B,), max(steps - 1, 0), dtype=torch.int64, device=dev)
+        if csr is not None:
+            keep = self._prep_csr(bufs, csr, t_vec, None, None, None, None, False)  # x_T = x_0 (the output product's x_t operand)
+            wt = self._transposed(w1)
+            core.gather_fwd(lib, None, None, csr, wt, I, None, None, 0, None, 0, B, h1, p, st)
+        else:
+            ca, cb = (tabs32["sqrt_ab"], tabs32["sqrt_1mab"]) if steps > 0 else (None, None)
+            keep = self._prep(bufs, x_start, t_vec, ca, cb, noise0, None, False, xin=bufs.xin)  # x_T
+            core.linear_fwd(lib, bufs, (bufs.xin.data_ptr(), bufs.xin.stride(0)), w1, None, 0, B, h1, I, p, st)
+        bufs.xin_ones = False
+        # the first activation alternates between two buffers: with one hidden layer it is the step kernel's operand A as well
+        hcur, hnxt = bufs.acts[0], bufs.lat_h
+        core.gather_fwd(lib, p, None, None, None, I, None, None, 0, ops.e[T - 1], act1, B, h1, hcur, st)
+        for i in range(T - 1, -1, -1):
+            A = hcur
+            for li in range(1, len(layers) - 1):
+                wl, bl, al = layers[li]
+                out = bufs.acts[li]
+                core.linear_fwd(lib, bufs, A, wl, bl, al, B, wl.shape[0], wl.shape[1], out, st)
+                A = out
+            if i == 0:
+                x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
+                core.posterior_fwd(lib, A, w, bias, bufs.xin, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
+                break
+            core.latent_step(lib, A, ops.M, ops.v, p, c1[i], c2[i], ops.e[i - 1], act1, B, h1, K, p, hnxt, st)
+            hcur, hnxt = hnxt, hcur
+        self._saved = None
+        del keep
+        return x0

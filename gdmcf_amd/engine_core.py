@@ -175,6 +175,14 @@ def gather_fwd(lib, pre, base, batch, table, I, a, tblE, E, bias, act, B, N, out
         batch.row_ids.data_ptr() if c is not None else None, tb, ldt, I, ap, lda, te, ldte, E, _lib.ptr(bias), act, B, N, o, ldo, st))
 
 
+def latent_step(lib, A, M, v, p_cur, c1, c2, e, act, B, N, K, p_next, h_next, st):
+    """gdmcf_latent_step_f32: p_next = c1 . (A @ M^T + v) + c2 . p_cur, h_next = act(p_next + e) -- one reverse step carried in
+    the first hidden layer's space.  M [N, K]; v, e [N] or None; h_next None: not written; p_next may be p_cur."""
+    (a, lda), (m, ldm), (pc, ldpc), (pn, ldpn), (h, ldh) = _pl(A), _pl(M), _pl(p_cur), _pl(p_next), _pl(h_next)
+    _lib.check(lib.gdmcf_latent_step_f32(a, lda, m, ldm, _lib.ptr(v), pc, ldpc, c1.data_ptr(), c2.data_ptr(), _lib.ptr(e), act,
+                                         B, N, K, pn, ldpn, h, ldh, None, 0, st))
+
+
 def linear_bwd_input(lib, bufs, dz, W, rs, A_prev, act_prev, B, N, K, d_prev, st):
     """d_prev = ((rs .) dz @ W) * act_prev'(A_prev)"""
     (z, ldz), (w, ldw), (a, lda), (d, ldd) = _pl(dz), _pl(W), _pl(A_prev), _pl(d_prev)
@@ -305,6 +313,7 @@ class EngineBase:
         self._bufs = {}
         self._saved = None
         self._wt = {}  # id(weight) -> (weight, version, transposed copy): see _transposed
+        self._latent = None  # (key, operands) of the latent reverse loop: see _latent_operands
         # data parallel: called as grad_sink(param, grad) the moment a gradient's kernels are enqueued, so the
         # all-reduce of the big weight gradients overlaps the rest of the backward (gdmcf_amd/parallel.py).
         # When set, the engine assigns .grad itself and hands autograd None for that parameter.
@@ -346,6 +355,58 @@ class EngineBase:
             buf[:, :n].copy_(w.detach().t())
             rec = self._wt[id(w)] = (w, w._version, buf)
         return rec[2]
+
+    def _emb_table(self, w, bias, I_cols, T, st):
+        """[T, .] table of a first layer's time columns and bias for every timestep, W_e emb(t) + b with W_e = w[:, I_cols:I_cols + E]:
+        gdmcf_dnn_emb_cols_f32 into a scratch input, then gdmcf_gather_fwd_f32 on W_e^T.  Returns (table, scratch to keep)."""
+        m, lib, E, h, dev = self.model, self.lib, self.E, w.shape[0], w.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        e = torch.zeros(T, _ceil64(h), **f32)
+        if E == 0:
+            e[:, :h].copy_(bias.detach()[None, :].expand(T, h))
+            return e, None
+        ew, eb = m.emb_layer.weight, m.emb_layer.bias
+        # the embedding columns of all T timesteps behind four dummy item columns of a scratch input (16-byte aligned rows)
+        xs = torch.zeros(T, _ceil64(4 + E), **f32)
+        ts = torch.arange(T, dtype=torch.int64, device=dev)
+        temb = torch.zeros(T, E, **f32)
+        _lib.check(lib.gdmcf_dnn_emb_cols_f32(ts.data_ptr(), ew.data_ptr(), eb.data_ptr(), E, T, 4, xs.data_ptr(), xs.stride(0),
+                                              temb.data_ptr(), st))
+        we_t = torch.zeros(E, (h + 3) // 4 * 4, **f32)
+        we_t[:, :h].copy_(w.detach()[:, I_cols:I_cols + E].t())
+        gather_fwd(lib, None, None, None, None, I_cols, (xs.data_ptr() + 16, xs.stride(0)), we_t, E, bias, 0, T, h, e, st)
+        return e, (xs, ts, temb, we_t)
+
+    def _latent_operands(self, w1, bias1, second, K, b_out, T, entering, tables=()):
+        """Operands of the reverse loop carried in the first hidden layer's space (gdmcf_latent_step_f32), cached per weight
+        VERSION like _transposed -- keyed on (data_ptr, _version, device) of every tensor that enters (`entering`: the
+        parameters behind all of the arguments):
+          M [h, K] = W1x . second     W1x = w1[:, :I] (read in place, its own leading dimension); second [I, K] = the output layer's
+                                      weight (or an embedding backbone's normalised item vectors): gdmcf_linear_bwd_input_f32
+          v [h]    = W1x . b_out      (None without b_out): gdmcf_linear_fwd_f32 on the one row b_out
+          e [T, h] = W1e emb(t) + b1  the first layer's time columns and bias for every timestep (_emb_table)
+          tabs                        the same table for every (weight, bias, item columns) of `tables`
+        Returns a _Bufs with M, v, e, tabs.  One item-wide product per weight version; an evaluation pass pays it once."""
+        lib, st = self.lib, _lib.stream_ptr()
+        key = tuple((t.data_ptr(), t._version, str(t.device)) for t in entering) + (int(T), int(K), b_out is None)
+        if self._latent is not None and self._latent[0] == key:
+            return self._latent[1]
+        h, I, dev = w1.shape[0], self.I, w1.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        o, ws = _Bufs(), _Bufs()
+        ws.ws_bytes = int(max(lib.gdmcf_linear_ws_bytes(h, I, K), lib.gdmcf_linear_ws_bytes(1, h, I)))
+        ws.ws = torch.empty(max(ws.ws_bytes, 256), dtype=torch.uint8, device=dev)
+        w1x = (w1.data_ptr(), w1.stride(0))
+        o.M = torch.zeros(h, _ceil64(K), **f32)
+        linear_bwd_input(lib, ws, w1x, second, None, None, 0, h, I, K, o.M, st)
+        o.v = None
+        if b_out is not None:
+            o.v = torch.zeros(h, **f32)
+            linear_fwd(lib, ws, (b_out.data_ptr(), I), w1x, None, 0, 1, h, I, (o.v.data_ptr(), h), st)
+        o.e, o.keep = self._emb_table(w1, bias1, I, T, st)
+        o.tabs = [self._emb_table(w, b, cols, T, st) for w, b, cols in tables]
+        self._latent = (key, o)
+        return o
 
     def _gather_first_layer(self, bufs, batch, w, bias, act, xin, B, out, st):
         """act([x_0 | emb] @ w^T + bias) for the binary, undropped CSR rows of `batch` as a sum of rows of the cached w^T

@@ -50,6 +50,7 @@ class GaussianDiffusion(nn.Module):
         self.Lt_count = torch.zeros(steps, dtype=torch.int64, device=self.device)
         self.update_history = True  # data-parallel wrappers switch this off and replay the gathered batch
         self.rng = "philox"  # "philox": in-kernel noise/dropout;  "torch": torch.randn / torch.bernoulli
+        self.last_reverse_route = None  # "latent" / "item": the route the last p_sample took (_latent_reverse_ok)
         if noise_scale != 0.0:
             if noise_schedule not in _SCHEDULE_KIND:
                 raise NotImplementedError(f"unknown beta schedule: {noise_schedule}!")
@@ -274,10 +275,42 @@ class GaussianDiffusion(nn.Module):
                 and getattr(model, "gemm_dtype", "f32") == "f32" and (not model.training or model.drop.p == 0)
                 and type(model) in (DNN, DNNOneHot, DNNOneHotEmbedding))
 
+    @staticmethod
+    def _latent_backbones():
+        """Exact types whose engines carry the reverse loop in the first hidden layer's space (p_sample(latent=True))."""
+        from .onehot import DNNOneHot
+        from .onehot_embedding import DNNOneHotEmbedding
+        from .onehot_gcn import DNNOneHotEmbeddingGCN
+        return (DNN, DNNOneHot, DNNOneHotEmbedding, DNNOneHotEmbeddingGCN)
+
+    def _latent_tables_ok(self):
+        """posterior_mean_coef2[0] == 0 (alphas_cumprod_prev[0] is 1 for every schedule: the last step needs no x_1) and finite
+        posterior_mean_coef1, as float32; read back once per table set."""
+        c1, c2 = self._t32.get("c1"), self._t32.get("c2")
+        if c1 is None or c2 is None:
+            return False
+        rec = getattr(self, "_latent_tabs_rec", None)
+        if rec is None or rec[0] is not c1 or rec[1] is not c2:
+            ok = bool(c2[0].item() == 0.0) and bool(torch.isfinite(c1).all().item())
+            rec = self._latent_tabs_rec = (c1, c2, ok)
+        return rec[2]
+
+    def _latent_reverse_ok(self, model, sampling_noise=False, capture=None):
+        """Whether p_sample(latent=True) may carry the reverse loop in the first hidden layer's space: between two
+        hidden activations the loop must be linear in x_t -- x0 target, no sampling noise, no F.normalize, no dropout -- nothing may
+        ask for the per-step x_t (capture), the products are float32, the last step needs no x_1 (c2[0] == 0), and the backbone's
+        engine has the loop (exact types).  Anything else takes the item-space route, to the bit."""
+        return (self.mean_type == ModelMeanType.START_X and self.noise_scale != 0.0 and not sampling_noise and capture is None
+                and not model.norm and (not model.training or model.drop.p == 0)
+                and getattr(model, "gemm_dtype", "f32") == "f32" and type(model) in self._latent_backbones()
+                and self._latent_tables_ok())
+
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,
-                 capture=None):
+                 capture=None, latent=False):
         """x_start: dense [B, n_items] rows, or a data_utils.CsrBatch -- kept sparse where _sparse_reverse_ok holds (the first
-        reverse step's first hidden layer is then a gather of the rows' weight rows), densified here otherwise."""
+        reverse step's first hidden layer is then a gather of the rows' weight rows), densified here otherwise.
+        latent=True: where _latent_reverse_ok holds, the loop runs in the first hidden layer's space (two item-wide products per
+        call instead of two per step; same [B, n_items] result up to float32 rounding); `last_reverse_route` says which route ran."""
         assert steps <= self.steps, "Too much steps in inference."
         _lib.require_gpu(x_start, "x_start")
         if not isinstance(model, DNN):
@@ -285,6 +318,8 @@ class GaussianDiffusion(nn.Module):
         from .data_utils import CsrBatch
         if isinstance(x_start, CsrBatch) and not self._sparse_reverse_ok(model, x_start, steps):
             x_start = x_start.dense()
+        latent = bool(latent) and self._latent_reverse_ok(model, sampling_noise, capture)
+        self.last_reverse_route = "latent" if latent else "item"
         if self.noise_scale == 0.0:
             x_t = x_start
             with torch.no_grad():
@@ -296,7 +331,8 @@ class GaussianDiffusion(nn.Module):
             return model.engine.p_sample_loop(x_start, steps, self.steps, self._t32,
                                               self.mean_type == ModelMeanType.EPSILON, bool(sampling_noise),
                                               noise0=noise0, step_noise=step_noise, capture=capture,
-                                              draw_noise=lambda like: self._draw_noise(like, stream_id=7))
+                                              draw_noise=lambda like: self._draw_noise(like, stream_id=7),
+                                              **(dict(latent=True) if latent else {}))
 
 
 class GaussianDiffusionDiscrete(GaussianDiffusion):
@@ -395,8 +431,11 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         return self._fused_loss(model, spec, batch_size, device)
 
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,
-                 capture=None, sampled0=None, graph_sampled=None, graph_pick=None):
-        """Reverse loop of the one-hot variant (reference :668-768).  With `indexIn` (the embedding backbones) every reverse
+                 capture=None, sampled0=None, graph_sampled=None, graph_pick=None, latent=False):
+        """latent: as GaussianDiffusion.p_sample -- where _latent_reverse_ok holds the loop runs in the engine
+        (OneHotEngine.latent_loop); with `indexIn` the per-step graph update runs exactly as on the item-space route (same draws,
+        same `last_graph`).
+        Reverse loop of the one-hot variant (reference :668-768).  With `indexIn` (the embedding backbones) every reverse
         step also advances the degree-guided graph of :706-729 on the device (gdmcf_graph_guided_step_u8: classes drawn
         from the accumulated graph's transition rows, one bit per user drawn from its relative degree, AND-ed when
         args.user_guided, OR-ed into the graph) and hands it to the model as `graph=` -- a uint8 [B, I] tensor of edge
@@ -404,10 +443,12 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         inject the draws (parity runs); `self.last_graph` keeps the final graph, `capture["graph"]` every step's."""
         if not self.CatOneHot:
             return super().p_sample(model, x_start, steps, sampling_noise, index, noise0=noise0, step_noise=step_noise,
-                                    capture=capture)
+                                    capture=capture, latent=latent)
         assert steps <= self.steps, "Too much steps in inference."
         _lib.require_gpu(x_start, "x_start")
         model = self._onehot_model(model)
+        latent = bool(latent) and self._latent_reverse_ok(model, sampling_noise, capture)
+        self.last_reverse_route = "latent" if latent else "item"
         from .data_utils import CsrBatch
         csr_batch = None
         if isinstance(x_start, CsrBatch):
@@ -450,6 +491,17 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
                 if self.noise_scale != 0.0 else None
             # models of this package fuse the posterior into their output GEMM (`posterior=` of their forward); anything
             # else with the reference's call signature takes the element-wise path below
+            if latent:
+                def before_step(n, i):
+                    if graph is not None:
+                        self._graph_step(graph, torch.full((B,), i, dtype=torch.int64, device=dev), degp,
+                                         None if graph_sampled is None else graph_sampled[n],
+                                         None if graph_pick is None else graph_pick[n])
+                x_0 = model.engine.latent_loop(x_t, x_tU, self.steps, tabs["c1"], tabs["c2"],
+                                               index=index if self.indexIn else None, before_step=before_step)
+                del keep
+                self.last_graph = graph
+                return x_0
             import inspect
             try:
                 fused_posterior = "posterior" in inspect.signature(getattr(model, "forward", model)).parameters

@@ -157,8 +157,15 @@ class GraphedTrainStep:
             finally:
                 self.lib.gdmcf_graph_state_bind(None)
         self.graph.replay()
+        self._bump_versions()
         self._dev_step += 1
         return self.loss.clone()
+
+    def _bump_versions(self):
+        """A replay rewrites every parameter without Python seeing it: move their version counters, which is what the engine's
+        per-version caches (EngineBase._transposed, _latent_operands) and the bf16 weight shadows compare."""
+        for p in self.model.parameters():
+            torch.autograd.graph.increment_version(p)
 
     # -- hand the counters back to the host-side objects ---------------------------------------------------------------------
     def close(self):
@@ -174,6 +181,7 @@ class GraphedTrainStep:
             if "step" in st:
                 st["step"] = step
         self.eng.static_grads = False
+        self._bump_versions()
         self.graph, self._state = None, None
 
     def __enter__(self):

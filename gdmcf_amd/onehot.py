@@ -428,6 +428,111 @@ class OneHotEngine(EngineBase):
         return res
 
 
+    # -- reverse loop in the first hidden layer's space (GaussianDiffusionDiscrete.p_sample(latent=True)) ---------------------
+    def _latent_second(self, bufs, out):
+        """(second [I, K], K, b_out or None, the parameters behind them): the product that turns the last activation into the
+        prediction."""
+        w, bias, _ = out[-1]
+        return w, w.shape[1], bias, (w, bias)
+
+    def _latent_A(self, bufs, out, B, index):
+        """The activation that feeds the last product, from bufs.hcat = [h | h_U]."""
+        self._chain_forward(bufs, out[:-1], bufs.acts_out, bufs.hcat, B, None)
+        return bufs.acts_out[len(out) - 2] if len(out) > 1 else bufs.hcat
+
+    def _set_hcat(self, bufs, t):
+        bufs.hcat = t
+
+    @with_precision
+    def latent_loop(self, x_T, x_U, T, c1, c2, index=None, before_step=None):
+        """The whole reverse loop with x_t carried as p_t = W1x x_t, the first layer of branch 1 without its time columns
+        (DenoiserEngine._latent_loop has the algebra): per step one gdmcf_latent_step_f32 with A = the activation behind
+        [h | h_U] that feeds the last product and M = W1x . W_out (an embedding backbone: W1x . V^), plus the small layers.
+        Branch 2 sees the same image at every step: its first layer's pre-activation without time columns and bias is taken
+        ONCE per call -- from the SparseXU handle, or one product on the dense image -- and re-enters every step through
+        gdmcf_gather_fwd_f32 with that step's row of the time table as the bias.  Item-wide work per call: branch 1's first layer
+        on x_T (a gather on CSR rows), branch 2's once, and the last product, x_0 = c1[0] (W_out a_0 + b_out).
+        x_T: dense [B, I] rows or a data_utils.CsrBatch of binary rows; x_U: the [B, 2I] image or a SparseXU; c1, c2: [T, B]
+        tables; before_step(n, i): called ahead of step n (timestep i), e.g. the degree-guided graph update."""
+        from .data_utils import CsrBatch
+        lib, st, I = self.lib, _lib.stream_ptr(), self.I
+        B, dev = x_T.shape[0], x_T.device
+        br1, br2, out = self._chains()
+        bufs = self.buffers(B, dev)
+        self.version += 1
+        self._saved = None
+        if self.model.norm or self.gemm_dtype != "f32":
+            raise RuntimeError("gdmcf_amd: the latent reverse loop takes norm=False and float32 products "
+                               "(GaussianDiffusion._latent_reverse_ok)")
+        if index is not None:
+            index = self._index_on(index, dev, B)
+        (w1, b1, act1), (w2, b2, act2) = br1[0], br2[0]
+        hf1, hf2 = w1.shape[0], w2.shape[0]
+        second, K, b_out, behind = self._latent_second(bufs, out)
+        m = self.model
+        ops = self._latent_operands(w1, b1, second, K, b_out, T, (w1, b1, w2, b2, m.emb_layer.weight, m.emb_layer.bias) + behind,
+                                    tables=[(w2, b2, 2 * I)])
+        e2 = ops.tabs[0][0]
+        if getattr(bufs, "lat_p", None) is None:
+            f32 = dict(dtype=torch.float32, device=dev)
+            bufs.lat_p = torch.zeros(B, _ceil64(hf1), **f32)
+            bufs.lat_hcat = torch.zeros_like(bufs.hcat)
+            bufs.lat_P2 = torch.zeros(B, _ceil64(hf2), **f32)
+        p = bufs.lat_p
+        # p_T and the x_t operand of the last product (c2[0] == 0: it only has to be finite)
+        if isinstance(x_T, CsrBatch):
+            if bufs.x0bits is None:
+                bufs.x0bits = torch.zeros(B, (I + 31) // 32, dtype=torch.int32, device=dev)
+            self.offset += 1
+            ts = torch.full((B,), T - 1, dtype=torch.int64, device=dev)
+            keep = core.prep_input_csr(lib, x_T, ts, None, None, None, None, float(m.drop.p), False, self.seed, self.offset,
+                                       m.emb_layer, self.E, bufs.xin1, bufs.temb, bufs.x0bits, st)
+            xdense = bufs.xin1
+            core.gather_fwd(lib, None, None, x_T, self._transposed(w1), I, None, None, 0, None, 0, B, hf1, p, st)
+        else:
+            keep = xdense = core._f32_rows(x_T)
+            core.linear_fwd(lib, bufs, xdense, (w1.data_ptr(), w1.stride(0)), None, 0, B, hf1, I, p, st)
+        # branch 2's step-independent pre-activation
+        if isinstance(x_U, SparseXU):
+            P2 = x_U.P2
+        else:
+            xu = core._f32_rows(x_U.reshape(B, -1))
+            if xu.shape[1] != 2 * I:
+                raise RuntimeError(f"gdmcf_amd.{type(m).__name__}: x_U must hold two columns per item")
+            P2 = bufs.lat_P2
+            core.linear_fwd(lib, bufs, xu, (w2.data_ptr(), w2.stride(0)), None, 0, B, hf2, 2 * I, P2, st)
+            keep = (keep, xu)
+        # [h | h_U] alternates between two buffers: with one layer in branch 1 and one out layer, the step kernel writes the next
+        # step's h into the buffer it is not reading A from
+        pair = (bufs.hcat, bufs.lat_hcat)
+        ld = bufs.hcat.stride(0)
+        first = (lambda t: t) if len(br1) == 1 else (lambda t: bufs.acts1[0])  # where the first activation of branch 1 lives
+        x0 = None
+        try:
+            core.gather_fwd(lib, p, None, None, None, I, None, None, 0, ops.e[T - 1], act1, B, hf1, first(pair[0]), st)
+            for n, i in enumerate(range(T - 1, -1, -1)):
+                if before_step is not None:
+                    before_step(n, i)
+                cur, nxt = pair[n % 2], pair[(n + 1) % 2]
+                self._set_hcat(bufs, cur)
+                hcat2 = (cur.data_ptr() + 4 * bufs.h1, ld)
+                if len(br1) > 1:
+                    self._chain_forward(bufs, br1[1:], bufs.acts1[1:], bufs.acts1[0], B, cur)
+                o2 = bufs.acts2[0] if len(br2) > 1 else hcat2
+                core.gather_fwd(lib, P2, None, None, None, I, None, None, 0, e2[i], act2, B, hf2, o2, st)
+                self._chain_forward(bufs, br2[1:], bufs.acts2[1:], o2, B, hcat2)
+                A = self._latent_A(bufs, out, B, index)
+                if i == 0:
+                    x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
+                    core.posterior_fwd(lib, A, second, b_out, xdense, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
+                else:
+                    core.latent_step(lib, A, ops.M, ops.v, p, c1[i], c2[i], ops.e[i - 1], act1, B, hf1, K, p, first(nxt), st)
+        finally:
+            self._set_hcat(bufs, pair[0])
+        del keep
+        return x0
+
+
 class DNNOneHot(nn.Module):
     """Drop-in for the reference DNNOneHot (models/DNN.py:360-477).  As there, `out_dims[0]` of the CALLER's list grows
     by the width of the second branch (the reference aliases and mutates it, :384-385)."""

@@ -111,22 +111,43 @@ class OneHotEmbeddingEngine(OneHotEngine):
     def _scores_operands(self, bufs, br1, br2, B, index, sparse=(None, None)):
         """ucat = [h, h_U, embedding_user(index)], then the row-normalised operands uhat, Vhat of the cosine scores.
         `sparse`: OneHotEngine._hidden's (reverse loop from CSR rows)."""
-        lib, st, m = self.lib, _lib.stream_ptr(), self.model
         self._hidden(bufs, br1, br2, [None], B, sparse)
-        Wu, V = m.embedding_user.weight, m.embedding_item.weight
+        self._user_operand(bufs, B, index)
+        self._vhat(bufs)
+
+    def _user_operand(self, bufs, B, index):
+        """ucat's user columns = embedding_user(index), then uhat = u / |u| of the scored user vector."""
+        lib, st, Wu = self.lib, _lib.stream_ptr(), self.model.embedding_user.weight
         ld = bufs.ucat.stride(0)
         _lib.check(lib.gdmcf_gather_rows_f32(Wu.data_ptr(), Wu.stride(0), index.data_ptr(), B, bufs.eu,
                                              bufs.ucat.data_ptr() + 4 * bufs.h12, ld, st))
         u = self._user_vector(bufs, B)  # what is scored against the items: ucat itself, or a subclass's function of it
         _lib.check(lib.gdmcf_row_norms_f32(u.data_ptr(), u.stride(0), B, bufs.D, None, bufs.rn_u.data_ptr(), st))
         core.rowscale(lib, u, bufs.rn_u, B, bufs.D, bufs.uhat, st)
-        # V / |v| only changes with the item table (every optimiser step while training; never during evaluation, where
-        # the reverse loop calls the model T times per batch): rebuilt when the parameter's version counter moved
+
+    def _vhat(self, bufs):
+        """V / |v| only changes with the item table (every optimiser step while training; never during evaluation, where
+        the reverse loop calls the model T times per batch): rebuilt when the parameter's version counter moved."""
+        lib, st, V = self.lib, _lib.stream_ptr(), self.model.embedding_item.weight
         key = (V.data_ptr(), V._version)
         if getattr(bufs, "vhat_key", None) != key:
             _lib.check(lib.gdmcf_row_norms_f32(V.data_ptr(), V.stride(0), self.I, bufs.D, None, bufs.rn_v.data_ptr(), st))
             core.rowscale(lib, V, bufs.rn_v, self.I, bufs.D, bufs.Vhat, st)
             bufs.vhat_key = key
+
+    # -- reverse loop in the first hidden layer's space: pred = uhat . Vhat^T, so M = W1x . Vhat and there is no v --------------
+    def _latent_second(self, bufs, out):
+        self._vhat(bufs)
+        m = self.model
+        behind = (m.embedding_item.weight,)  # (what the user vector is made of changes A, not the cached operands)
+        return bufs.Vhat, bufs.D, None, behind
+
+    def _latent_A(self, bufs, out, B, index):
+        self._user_operand(bufs, B, index)
+        return bufs.uhat
+
+    def _set_hcat(self, bufs, t):
+        bufs.hcat = bufs.ucat = t
 
     def _user_vector(self, bufs, B):
         return bufs.ucat

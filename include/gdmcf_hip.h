@@ -249,6 +249,26 @@ int gdmcf_gather_fwd_f32(const float* pre, int64_t ldpre, const float* base, con
                          const int64_t* rows, const float* table, int64_t ldt, int I, const float* a, int64_t lda,
                          const float* tblE, int64_t ldte, int E, const float* bias, int act, int B, int N, float* out, int64_t ldo,
                          void* stream);
+/* One reverse-diffusion step carried in the first hidden layer's space (START_X target, no sampling noise: between two hidden
+ * activations the loop of gaussian_diffusion.py:161-220 is linear in x_t, so p_t = W1x x_t can be stepped instead of x_t):
+ *   s[b,n]      = sum_k A[b,k] * M[n,k]
+ *   p_next[b,n] = c1[b] * (s[b,n] + v[n]) + c2[b] * p_cur[b,n]      (v NULL: 0)
+ *   h_next[b,n] = act(p_next[b,n] + e[n])    (e NULL: 0; act 0 none, 1 tanh; h_next NULL: not written)
+ * A [B, lda], M [N, ldm] (K-contiguous, the orientation of an nn.Linear weight), p_cur/p_next/h_next row-major with
+ * their own leading dimensions, c1/c2 float32 [B], v/e float32 [N].  p_next may be p_cur.  float32 throughout.
+ * A row with c2[b] == 0 does not read p_cur (its p_cur may hold anything).  B, N, K, the leading dimensions and the alignment
+ * of every pointer are free: rows that are not 16-byte aligned (or lda / ldm not multiples of 4) take a scalar load path.
+ * Order of the sum, per element, all in float32 (v_mfma_f32_16x16x4_f32 = a k-ordered fma chain): K is cut into chunks of 16;
+ * chunk c belongs to partial sum c % 4; a partial sum starts at 0 and takes its chunks in ascending order, within a chunk at k0
+ * the terms k0 + j + 4 q for j = 0..3 (outer), q = 0..3 (inner), each by one fma; then s = ((s_0 + s_1) + s_2) + s_3;
+ * t = s + v; p_next = fma(c2, p_cur, c1 * t); h_next = act(p_next + e).  One launch, no atomics, no host synchronisation
+ * (capture-safe): the same bits on every run.  The four partial sums meet in LDS, so no workspace is needed:
+ * gdmcf_latent_step_ws_bytes returns 0 and `ws` may be NULL (the arguments are kept for a later split over workgroups).    */
+int gdmcf_latent_step_f32(const float* A, int64_t lda, const float* M, int64_t ldm, const float* v,
+                          const float* p_cur, int64_t ldpc, const float* c1, const float* c2, const float* e, int act,
+                          int B, int N, int K, float* p_next, int64_t ldpn, float* h_next, int64_t ldh,
+                          void* ws, size_t ws_bytes, void* stream);
+size_t gdmcf_latent_step_ws_bytes(int B, int N, int K);
 /* Last layer fused with the per-row diffusion loss (gaussian_diffusion.py:335 mean_flat):
  *   out = A @ W^T + bias ;  diff[m,n] = alpha[m]*out[m,n] - target[m,n]   (alpha NULL -> 1)
  *   rowsum[m] = sum_n diff[m,n]^2  (deterministic two-stage reduction)
