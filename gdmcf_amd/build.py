@@ -127,7 +127,8 @@ def lint_vmcnt(asm_text, only=None):
     slot that has not landed.  Path-insensitive: kernels whose waits are selected by the same predicate as their loads
     (gemm_f32.hip, gemm_bf16.hip: `if (more) load(); ... if (more) wait(N) else wait(0)`) raise false alarms and are not run
     through it; gemm_dr_tn.hip (both kernels) and gemm_split.hip verify cleanly and are checked at every build.  (gemm_dr_fat.hip and
-    gemm_dr_kn.hip have no inline-asm loads: every wait in them is hipcc's own.)"""
+    gemm_dr_kn.hip have no inline-asm loads: every wait in them is hipcc's own, but for the vmcnt(0) that gemm_dr_fat.hip places by
+    builtin in front of the reads of its LDS-DMA pieces -- lint_fat_dma.)"""
     bad, nk = [], 0
     for m in re.finditer(r"^(_Z\S+):[^\n]*\n(.*?)\n\s*s_endpgm", asm_text, flags=re.S | re.M):
         name, body = m.group(1), m.group(2)
@@ -271,6 +272,49 @@ def lint_store_data(asm_text):
     return bad
 
 
+def lint_fat_dma(asm_text, kernel="dr_fat_kernel"):
+    """gemm_dr_fat.hip, the instantiations that load the weight's pieces straight into LDS (`buffer_load_dwordx4 ... lds`).
+    (1) hipcc places no wait between such a load and a ds_read of the bytes it writes, and the hardware orders the two by nothing but
+    the issuing wave's vmcnt: the kernel opens every chunk with s_waitcnt vmcnt(0).  In program order, between any `... lds` load of
+    16 bytes and the next ds_read_b128 there must be an s_waitcnt whose vmcnt field is 0.  (2) The k loop -- the block of MFMAs that
+    branches back to itself -- holds no spill, no v_accvgpr_* and no v_mov_*: the registers the staging copy no longer needs must not
+    come back as moves on the vector port the MFMAs issue on."""
+    bad, n_dma = [], 0
+    for m in re.finditer(r"^(_Z\S*%s\S*):[^\n]*\n(.*?)\n\s*s_endpgm" % kernel, asm_text, flags=re.S | re.M):
+        name, body = m.group(1), m.group(2)
+        lines = [ln.split(";")[0].strip() for ln in body.splitlines()]
+        lines = [ln for ln in lines if ln and (not ln.startswith(".") or ln.endswith(":"))]
+        if not any(ln.startswith("buffer_load_dwordx4") and ln.endswith(" lds") for ln in lines):
+            continue
+        n_dma += 1
+        pending = None
+        for ln in lines:
+            if ln.startswith("buffer_load_dwordx4") and ln.endswith(" lds"):
+                pending = ln
+            elif ln.startswith("s_waitcnt") and re.search(r"vmcnt\(0\)", ln):
+                pending = None
+            elif ln.startswith("ds_read_b128") and pending:
+                bad.append(f"{name}: `{ln}` follows `{pending}` with no s_waitcnt vmcnt(0) in between")
+                break
+        loops, label, blk = 0, None, []
+        for ln in lines + ["end:"]:
+            if not ln.endswith(":"):
+                blk.append(ln)
+                continue
+            if label and any(i.startswith("v_mfma") for i in blk) and any(
+                    i.startswith(("s_cbranch", "s_branch")) and i.split()[-1] == label for i in blk):
+                loops += 1
+                moved = [i for i in blk if i.startswith(("scratch_", "v_accvgpr", "v_mov"))]
+                if moved:
+                    bad.append(f"{name}: {len(moved)} spill / move instruction(s) in the k loop, e.g. `{moved[0]}`")
+            label, blk = ln[:-1], []
+        if not loops:
+            bad.append(f"{name}: no k loop found (lint out of date?)")
+    if not n_dma:
+        bad.append(f"no *{kernel}* with `buffer_load_dwordx4 ... lds` in the assembly (lint out of date?)")
+    return bad
+
+
 def build(force=False, verbose=True):
     stamp = os.path.join(CSRC, ".build_stamp")
     dig = _digest()
@@ -316,8 +360,10 @@ def build(force=False, verbose=True):
                 bad += lint_vmcnt(text)
             if src == "gemm_dr_tn.hip":
                 bad += lint_ring_registers(text)
+            if src == "gemm_dr_fat.hip":
+                bad += lint_fat_dma(text)
             if bad:
-                raise RuntimeError(f"{src}: ISA lint failed (lint_store_data / lint_vmcnt / lint_ring_registers):\n  " + "\n  ".join(bad[:12]))
+                raise RuntimeError(f"{src}: ISA lint failed (lint_store_data / lint_vmcnt / lint_ring_registers / lint_fat_dma):\n  " + "\n  ".join(bad[:12]))
         return obj
 
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:

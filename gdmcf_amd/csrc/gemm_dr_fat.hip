@@ -4,6 +4,10 @@
 
 #include "gemm_dr.h"
 
+#ifndef GD_FAT_DMA_DEFAULT
+#define GD_FAT_DMA_DEFAULT 1  // GDMCF_FAT_DMA when the environment does not set it
+#endif
+
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -30,11 +34,31 @@ namespace {
 //   * No instruction of the loop is inline asm: every load of a chunk is waited for inside the chunk that issued it (nothing is
 //     in flight across the loop's back edge), so hipcc's own counted waits are exact; sched_barriers pin the placement.
 // acc[i][b][t] = C[m0 + 16 i + 4 q + t][n0 + 16 b + r].  Deterministic: fixed k order, one wave per tile, static assignment.
+//
+// DMA = 1 (GDMCF_FAT_DMA): the same loop with B's pieces loaded STRAIGHT INTO THE LDS IMAGE by LDS-DMA (buffer_load_dwordx4
+// ... lds, 16 bytes per lane) -- no staging registers G, no ds_write_b128: 11 of a chunk's 38 non-MFMA instructions less (NB = 11).
+// Same MFMAs, same operands, same k order: bit-identical to DMA = 0, which stays as the route for sources that are not 16-byte
+// aligned and as the A/B partner.
+//   * An LDS-DMA load writes wave-uniform base + lane x 16 B: lane l of piece p lands at row l >> 2, PHYSICAL slot l & 3.  The image
+//     keeps its conflict-free swizzle (what r_off reads is unchanged), so the swizzle moves to the SOURCE: lane l fetches the
+//     global slot (l & 3) ^ 2 ((row >> 2) & 1) of its row, the one whose place in the image is l & 3.
+//   * hipcc puts NO wait between an LDS-DMA load and a ds_read of the bytes it writes, and the hardware orders the two by
+//     nothing but the issuing wave's vmcnt.  Every chunk therefore opens with s_waitcnt vmcnt(0) between sched_barriers, before
+//     its first fragment read: that retires the pieces the previous chunk (or the fill) issued into this chunk's image, and with
+//     them A's loads and the posterior's x_t touches -- nothing is in flight across a chunk boundary, no count is needed.
+//     The build disassembles this file and fails if any ds_read_b128 follows a ... lds load without such a wait (build.py).
+//   * WAR: the pieces of chunk c + 1 go into the image that chunk c - 1 read; those fragments were MFMA operands of chunk c - 1,
+//     so their ds_reads have retired.  The last chunk's parked loads (range-checked: no fetch, zeros) still WRITE their image:
+//     a vmcnt(0) after the loop retires them before the epilogue stages rows in the same LDS, and the fill of the NEXT tile waits
+//     lgkmcnt(0) for the epilogue's last reads of that staging.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NB, int EPI>
+template <int NB, int EPI, int DMA>
 __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
     static_assert(EPI == GD_EPI_LOSS || EPI == GD_EPI_POST, "output layer with a fused epilogue");
     static_assert(NB >= 4 && NB <= 12, "5 x NB accumulator blocks must fit 256 registers");
+    static_assert(DMA == 0 || DMA == 1, "B through staging registers, or straight into LDS");
+    typedef __attribute__((address_space(3))) void* lds_vp;
+    constexpr int WAIT_VM0 = 0x0F70, WAIT_LGKM0 = 0xC07F;  // s_waitcnt vmcnt(0) / lgkmcnt(0), the other counters left alone
     constexpr int TMB = 5;
     const GdGemm& g = d.g;
     const int lane = threadIdx.x & 63;
@@ -52,7 +76,9 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
     const int NCH = d.ksp;       // chunks of 16 k per tile: ceil(K / 16) -- the loop runs them in pairs, an odd last one alone
     const int c_mask = g.K >> 4;  // first chunk that reaches past K
     // LDS float offsets: write -- piece p = rows 16 p + (lane >> 2), slot lane & 3; read -- block b = rows 16 b + r, slot q
+    // (DMA: the write lands lane-linear, row lane >> 2, slot lane & 3; the lane fetches the global slot g_slot that belongs there)
     const int w_off = (lane >> 2) * 16 + (((lane & 3) ^ ((((lane >> 2) >> 2) & 1) << 1)) << 2);
+    const int g_slot = DMA ? ((lane & 3) ^ ((((lane >> 2) >> 2) & 1) << 1)) : (lane & 3);
     const int r_off = r * 16 + ((q ^ (((r >> 2) & 1) << 1)) << 2);
     for (int tile = wl; tile < ntiles; tile += n_waves) {
         const int tm = tile % d.tiles_m, tn = tile / d.tiles_m;
@@ -61,30 +87,52 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
 #pragma unroll
         for (int i = 0; i < TMB; ++i) offA[i] = (uint32_t)((m0 + 16 * i + r) * g.lda + 4 * q) * 4u;
 #pragma unroll
-        for (int p = 0; p < NB; ++p) offB[p] = (uint32_t)(((int64_t)(n0 + 16 * p + (lane >> 2)) * g.ldb + 4 * (lane & 3)) * 4);
+        for (int p = 0; p < NB; ++p) offB[p] = (uint32_t)(((int64_t)(n0 + 16 * p + (lane >> 2)) * g.ldb + 4 * g_slot) * 4);
         f32x4 acc[TMB][NB];
 #pragma unroll
         for (int i = 0; i < TMB; ++i)
 #pragma unroll
             for (int b = 0; b < NB; ++b) acc[i][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        f32x4 xa[2][TMB], G[NB], FB[NB];
-        // ---- fill: chunk 0 of A into xa[0], chunk 0 of B through LDS image 0 ----
+        f32x4 xa[2][TMB], G[DMA ? 1 : NB], FB[NB];
+        // ---- fill: chunk 0 of A into xa[0], chunk 0 of B through LDS image 0 (DMA: into the registers and the image of parity hp,
+        // see the loop) ----
+        const int hp = DMA ? (c_mask & 1) : 0;
+        if (hp) {
 #pragma unroll
-        for (int i = 0; i < TMB; ++i) xa[0][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdA, offA[i], 0, 0));
+            for (int i = 0; i < TMB; ++i) xa[1][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdA, offA[i], 0, 0));
+        } else {
 #pragma unroll
-        for (int p = 0; p < NB; ++p) G[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdB, offB[p], 0, 0));
+            for (int i = 0; i < TMB; ++i) xa[0][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdA, offA[i], 0, 0));
+        }
+        if constexpr (DMA) {
+            // (the previous tile's epilogue has read its row staging out of this LDS: those reads retire before a piece may land)
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int p = 0; p < NB; ++p) *reinterpret_cast<f32x4*>(lds + p * 256 + w_off) = G[p];
+            for (int p = 0; p < NB; ++p) __builtin_amdgcn_raw_ptr_buffer_load_lds(srdB, (lds_vp)(lds + hp * (NB * 256) + p * 256), 16, (int)offB[p], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int p = 0; p < NB; ++p) G[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdB, offB[p], 0, 0));
+#pragma unroll
+            for (int p = 0; p < NB; ++p) *reinterpret_cast<f32x4*>(lds + p * 256 + w_off) = G[p];
+        }
 
         // one chunk: PAR = its parity (A registers xa[PAR], LDS image PAR); the loads of chunk c + 1 ride in k steps 0 and 1,
-        // its LDS writes in k step 3
-#define GD_FAT_CHUNK(PAR, c)                                                                                          \
+        // its LDS writes in k step 3 (DMA: the pieces go straight into the other image, and the chunk opens with the wait that
+        // retires everything the previous chunk issued -- the pieces of ITS image first of all -- before the first fragment read)
+#define GD_FAT_CHUNK(PAR, c, MSK)                                                                                         \
         {                                                                                                             \
             /* scalar offset of the next chunk; past the last chunk it parks the loads outside both matrices (0, no fetch) */ \
             const uint32_t kn = ((c) + 1 < NCH) ? (uint32_t)((c) + 1) * 64u : 0x80000000u;                            \
+            if constexpr (DMA) {                                                                                      \
+                __builtin_amdgcn_sched_barrier(0);                                                                    \
+                __builtin_amdgcn_s_waitcnt(WAIT_VM0);                                                                 \
+                __builtin_amdgcn_sched_barrier(0);                                                                    \
+            }                                                                                                         \
             _Pragma("unroll") for (int b = 0; b < NB; ++b)                                                            \
                 FB[b] = *reinterpret_cast<const f32x4*>(lds + (PAR) * (NB * 256) + b * 256 + r_off);                  \
-            if ((c) >= c_mask) { /* the chunk(s) that reach past K: zero every k >= K of both operands (what lies behind a row's K */ \
+            if (MSK) { /* the chunk(s) that reach past K: zero every k >= K of both operands (what lies behind a row's K */ \
                 /* elements -- the next row, or the padding of a leading dimension > K -- may hold anything, NaN included) */ \
                 _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                       \
                     const bool keep = (c) * 16 + 4 * q + e < g.K;                                                     \
@@ -107,13 +155,17 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
                             if (l < TMB)                                                                              \
                                 xa[(PAR) ^ 1][l] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(   \
                                     srdA, offA[l], kn, 0));                                                           \
+                            else if constexpr (DMA)                                                                   \
+                                __builtin_amdgcn_raw_ptr_buffer_load_lds(                                             \
+                                    srdB, (lds_vp)(lds + ((PAR) ^ 1) * (NB * 256) + (l - TMB) * 256), 16,             \
+                                    (int)offB[l - TMB], (int)kn, 0, 0);                                               \
                             else                                                                                      \
                                 G[l - TMB] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(         \
                                     srdB, offB[l - TMB], kn, 0));                                                     \
                             __builtin_amdgcn_sched_barrier(0);                                                        \
                         }                                                                                             \
                     }                                                                                                 \
-                    if (sx == 3 && n % 4 == 1 && n / 4 < NB) { /* the pieces have landed: into the other LDS image */  \
+                    if (!DMA && sx == 3 && n % 4 == 1 && n / 4 < NB) { /* the pieces have landed: into the other LDS image */ \
                         __builtin_amdgcn_sched_barrier(0);                                                            \
                         *reinterpret_cast<f32x4*>(lds + ((PAR) ^ 1) * (NB * 256) + (n / 4) * 256 + w_off) = G[n / 4]; \
                         __builtin_amdgcn_sched_barrier(0);                                                            \
@@ -125,13 +177,27 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
         // Reverse step: the epilogue reads the tile's x_t (80 x 16 NB floats per wave, 55 MB per launch at the Yelp shape) in the same
         // burst in which every wave writes x_{t-1} -- the only HBM-bound stretch of the kernel, while the k loop leaves HBM nearly
         // idle.  Some chunks (default ten, ~30 us) before the end the wave touches one dword of every 128-byte line of its x_t tile with LDS-DMA
-        // loads (buffer_load_dword ... lds into a scratch line of its own: no registers, nothing waits for them), so the epilogue's
+        // loads (buffer_load_dword ... lds into a scratch line of its own: no registers; DMA = 0: nothing waits for them, DMA = 1: they
+        // retire with everything else at the next chunk's opening vmcnt(0), some 7 000 cycles of MFMAs later), so the epilogue's
         // reads find the lines in L2 / the Infinity Cache.
         const int c_pf = d.stagger > 0 ? ((NCH > d.stagger + 2 ? NCH - d.stagger : 0) & ~1) : -2;  // (d.stagger: chunks before the end; 0 = off)
-        for (int c = 0; c + 1 < NCH; c += 2) {
+        // DMA = 0 asks every chunk whether it reaches past K; the two arms of that branch meet in 32 register copies per chunk.
+        // DMA = 1 does not ask.  At most ONE chunk reaches past K, the last (NCH - c_mask <= 1): it is an instantiation of its own,
+        // at parity 0, behind a pair loop that runs only chunks inside K.  The parities are labels (which registers, which image),
+        // so an odd number of inside chunks is evened out in FRONT: chunk 0 then runs alone at parity 1, which is where the fill put
+        // it (hp).  Same chunks, same k order, same MFMAs as DMA = 0.
+        const int c_pairs = DMA ? c_mask : NCH;                                           // the pair loop runs chunks [hp, c_pairs & ~1 | hp)
+        const int c_pfl = (DMA && c_pf >= 0) ? min(c_pf | hp, c_pairs - 2) : c_pf;         // (the touches ride on a pair of the loop)
+        int c = 0;
+        if constexpr (DMA) {
+            if (hp) {
+                GD_FAT_CHUNK(1, 0, false);
+                c = 1;
+            }
+        }
+        for (; c + 1 < c_pairs; c += 2) {
             if constexpr (EPI == GD_EPI_POST) {
-                if (c == c_pf) {
-                    typedef __attribute__((address_space(3))) void* lds_vp;
+                if (c == c_pfl) {
                     constexpr int NJL = (16 * NB * 4 + 127) / 128 + 1;   // touches per row: one per line + the row's last element
                     constexpr int NPI = (80 * NJL + 63) / 64;
                     float* const scratch = dr_lds + 4 * (2 * NB * 256) + wave * 64;
@@ -146,13 +212,28 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
                     }
                 }
             }
-            GD_FAT_CHUNK(0, c);
-            GD_FAT_CHUNK(1, c + 1);
+            if constexpr (DMA) {
+                GD_FAT_CHUNK(0, c, false);
+                GD_FAT_CHUNK(1, c + 1, false);
+            } else {
+                GD_FAT_CHUNK(0, c, c >= c_mask);
+                GD_FAT_CHUNK(1, c + 1, c + 1 >= c_mask);
+            }
         }
         // an odd number of chunks (K = 1 000: 63, the last one half masked): the last chunk alone, not a pair with an all-zero
         // partner (1.6 % of the product's matrix instructions at K = 1 000)
-        if (NCH & 1) GD_FAT_CHUNK(0, NCH - 1);
+        if constexpr (DMA) {
+            if (c < NCH) GD_FAT_CHUNK(0, c, true);  // (c == c_mask here)
+        } else {
+            if (NCH & 1) GD_FAT_CHUNK(0, NCH - 1, NCH - 1 >= c_mask);
+        }
 #undef GD_FAT_CHUNK
+        if constexpr (DMA) {
+            // the last chunk's parked pieces write zeros into the image the epilogue is about to stage rows in: retired first
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(WAIT_VM0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
 
         // ---- epilogue: the tile goes through the wave's LDS (the chunk images are dead) one block of 16 rows at a time and leaves
         // in ROWS -- lane (r, q) owns four consecutive columns 4 (r + 16 j) of row 4 p + q: 16-byte accesses, 256 contiguous bytes
@@ -296,17 +377,19 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
 }
 
 template <int NB>
-int dr_fat_go(const DrArgs& d, int epi, int n_cu, hipStream_t s) {
+int dr_fat_go(const DrArgs& d, int epi, int dma, int n_cu, hipStream_t s) {
     const size_t lds = (size_t)4 * 2 * NB * 256 * sizeof(float) + 4 * 64 * sizeof(float);  // chunk images + a scratch line per wave (x_t prefetch)
-    void (*kern)(const DrArgs) = epi == GD_EPI_LOSS ? dr_fat_kernel<NB, GD_EPI_LOSS> : dr_fat_kernel<NB, GD_EPI_POST>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[epi == GD_EPI_LOSS] && lds > 48 * 1024) {
+    void (*kern)(const DrArgs) = dma ? (epi == GD_EPI_LOSS ? dr_fat_kernel<NB, GD_EPI_LOSS, 1> : dr_fat_kernel<NB, GD_EPI_POST, 1>)
+                                     : (epi == GD_EPI_LOSS ? dr_fat_kernel<NB, GD_EPI_LOSS, 0> : dr_fat_kernel<NB, GD_EPI_POST, 0>);
+    static bool attr_set[4] = {false, false, false, false};
+    const int ai = 2 * dma + (epi == GD_EPI_LOSS);
+    if (!attr_set[ai] && lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             gdmcf_set_error("hipFuncSetAttribute(dr_fat_kernel, LDS=%zu): %s", lds, hipGetErrorString(e));
             return GDMCF_E_HIP;
         }
-        attr_set[epi == GD_EPI_LOSS] = true;
+        attr_set[ai] = true;
     }
     hipLaunchKernelGGL(kern, dim3(n_cu), dim3(256), lds, s, d);
     return GDMCF_OK;
@@ -352,6 +435,10 @@ int gd_dr_fat_launch(int epi, GdGemm& g, hipStream_t s) {
         static const int pf = getenv("GDMCF_FAT_PF") ? atoi(getenv("GDMCF_FAT_PF")) : 10;
         d.stagger = pf;  // (DrArgs: the field doubles as this kernel's prefetch distance)
     }
+    // B's pieces straight into LDS (GDMCF_FAT_DMA=1; 0: through staging registers): 16 bytes per lane from a 16-byte-aligned source,
+    // any other weight runs the register-staged loop
+    static const int dma_env = getenv("GDMCF_FAT_DMA") ? atoi(getenv("GDMCF_FAT_DMA")) : GD_FAT_DMA_DEFAULT;
+    const int dma = (dma_env > 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0 && (g.ldb & 3) == 0) ? 1 : 0;
     g.tiles_m = d.tiles_m;
     g.tiles_n = d.tiles_n;
     d.g = g;
@@ -360,11 +447,11 @@ int gd_dr_fat_launch(int epi, GdGemm& g, hipStream_t s) {
     {
         GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
         switch (nb) {
-            case 8: rc = dr_fat_go<8>(d, epi, n_cu, s); break;
-            case 9: rc = dr_fat_go<9>(d, epi, n_cu, s); break;
-            case 10: rc = dr_fat_go<10>(d, epi, n_cu, s); break;
-            case 11: rc = dr_fat_go<11>(d, epi, n_cu, s); break;
-            default: rc = dr_fat_go<12>(d, epi, n_cu, s); break;
+            case 8: rc = dr_fat_go<8>(d, epi, dma, n_cu, s); break;
+            case 9: rc = dr_fat_go<9>(d, epi, dma, n_cu, s); break;
+            case 10: rc = dr_fat_go<10>(d, epi, dma, n_cu, s); break;
+            case 11: rc = dr_fat_go<11>(d, epi, dma, n_cu, s); break;
+            default: rc = dr_fat_go<12>(d, epi, dma, n_cu, s); break;
         }
     }
     if (rc != GDMCF_OK) return rc;
