@@ -41,6 +41,8 @@ def main():
     ap.add_argument("--gemm", default=None, choices=["f32", "bf16", "f32x3"],
                     help="GEMM mode of the DNN denoiser (f32x3: float32 products from three-term bf16 splits, DESIGN 4.4b)")
     ap.add_argument("--sparse-rows", action="store_true", help="feed the training rows as CSR batches (never densified)")
+    ap.add_argument("--recommend-eval", action="store_true",
+                    help="evaluate through gdmcf_amd.recommend (top-k per user id from device CSR rows; ignores --latent-eval)")
     ap.add_argument("--latent-eval", action="store_true",
                     help="evaluate with the reverse loop in the first hidden layer's space (p_sample(latent=True)) where it applies")
     ap.add_argument("--graph", action="store_true", help="replay the training step from one hipGraph (single GPU, dnn backbone)")
@@ -137,7 +139,8 @@ def main():
         gstep.close()
     if rank == 0:
         t0 = time.perf_counter()
-        res = driver.evaluate(diffusion, model, train, test, train, topN, 0, False, args.batch, dev, latent=args.latent_eval)
+        res = driver.evaluate(diffusion, model, train, test, train, topN, 0, False, args.batch, dev, latent=args.latent_eval,
+                              recommend=args.recommend_eval)
         print(f"evaluation of {U} users: {time.perf_counter() - t0:.2f} s")
         print_results(None, None, res)
     if world > 1:

@@ -29,13 +29,37 @@ __device__ __forceinline__ uint32_t masked_key(const float* __restrict__ row, co
     return order_key(row[i]);
 }
 
+// gdmcf_topk_masked_rows_f32: what the row-indirected instantiations take behind the plain kernels' arguments.  Both kernels
+// below end in a parameter pack EXT that is either empty -- gdmcf_topk_masked_f32: the parameter list, the kernel arguments and
+// the code are what they were without the pack -- or one TopkRowsArgs.
+struct TopkRowsArgs {
+    const int64_t* indptr2;   // second CSR (or nullptr)
+    const int32_t* indices2;
+    const int64_t* rows;      // [B] row of both CSRs per pred row (nullptr: the pred row's own number)
+    const float* scale;       // [B] factor of the returned values (nullptr: none)
+};
+__device__ __forceinline__ const TopkRowsArgs& rows_args(const TopkRowsArgs& e) { return e; }
+
+// bits of CSR row r into the LDS bitmap, as the plain kernels set their own row's (entries outside [0, I) skipped)
+template <int NT>
+__device__ __forceinline__ void mask_row_bits(uint32_t* bitmap, int I, const int64_t* __restrict__ indptr,
+                                              const int32_t* __restrict__ indices, int64_t r, int tid) {
+    const int64_t beg = indptr[r], end = indptr[r + 1];
+    for (int64_t j = beg + tid; j < end; j += NT) {
+        const int c = indices[j];
+        if (c >= 0 && c < I) atomicOr(&bitmap[c >> 5], 1u << (c & 31));
+    }
+}
+
 // NT threads per row: 1024 when the row is staged in LDS (the staged row allows one workgroup per CU anyway, and
 // the select is a chain of short LDS loops -- 16 waves hide their latency, 4 waves measured 2.4x slower)
-template <bool STAGE, int NT>
+template <bool STAGE, int NT, class... EXT>
 __global__ __launch_bounds__(NT) void topk_kernel(const float* __restrict__ pred, int64_t ldp, int I,
                                                    const int64_t* __restrict__ indptr,
                                                    const int32_t* __restrict__ indices, int k, int KP,
-                                                   int64_t* __restrict__ idx_out, float* __restrict__ val_out, int redo) {
+                                                   int64_t* __restrict__ idx_out, float* __restrict__ val_out, int redo,
+                                                   const EXT... ext) {
+    constexpr bool ROWS = sizeof...(EXT) != 0;
     // redo: second launch behind topk_fast_kernel -- only the rows it marked (first index -1) are selected here
     if (redo && idx_out[(int64_t)blockIdx.x * k] != -1) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -55,7 +79,12 @@ __global__ __launch_bounds__(NT) void topk_kernel(const float* __restrict__ pred
     for (int w = tid; w < nwords; w += NT) bitmap[w] = 0u;
     for (int j = tid; j < KP; j += NT) cand[j] = 0ull;
     __syncthreads();
-    if (indptr) {
+    if constexpr (ROWS) {
+        const TopkRowsArgs& e = rows_args(ext...);
+        const int64_t mr = e.rows ? e.rows[row_id] : (int64_t)row_id;
+        if (indptr) mask_row_bits<NT>(bitmap, I, indptr, indices, mr, tid);
+        if (e.indptr2) mask_row_bits<NT>(bitmap, I, e.indptr2, e.indices2, mr, tid);
+    } else if (indptr) {
         const int64_t beg = indptr[row_id], end = indptr[row_id + 1];
         for (int64_t j = beg + tid; j < end; j += NT) {
             const int c = indices[j];
@@ -195,6 +224,19 @@ __global__ __launch_bounds__(NT) void topk_kernel(const float* __restrict__ pred
             __syncthreads();
         }
     }
+    if constexpr (ROWS) {  // the same list, the values times the row's factor
+        const TopkRowsArgs& e = rows_args(ext...);
+        const float sc = (val_out && e.scale) ? e.scale[row_id] : 1.f;
+        for (int j = tid; j < k; j += NT) {
+            const unsigned long long c = cand[j];
+            idx_out[(int64_t)row_id * k + j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(c & 0xFFFFFFFFull));
+            if (val_out) {
+                const float v = key_to_float((uint32_t)(c >> 32));
+                val_out[(int64_t)row_id * k + j] = e.scale ? v * sc : v;
+            }
+        }
+        return;
+    }
     for (int j = tid; j < k; j += NT) {
         const unsigned long long c = cand[j];
         idx_out[(int64_t)row_id * k + j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(c & 0xFFFFFFFFull));
@@ -213,10 +255,12 @@ __global__ __launch_bounds__(NT) void topk_kernel(const float* __restrict__ pred
 // the number of unmasked items) the row is marked -- first index -1 -- and topk_kernel selects it in the launch that follows.
 // ---------------------------------------------------------------------------------------------
 constexpr int TOPK_FAST_CAP = 1024;
-template <int NT, int KPT>
+template <int NT, int KPT, class... EXT>
 __global__ __launch_bounds__(NT, 8) void topk_fast_kernel(const float* __restrict__ pred, int64_t ldp, int I,
                                                          const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-                                                         int k, int64_t* __restrict__ idx_out, float* __restrict__ val_out) {
+                                                         int k, int64_t* __restrict__ idx_out, float* __restrict__ val_out,
+                                                         const EXT... ext) {
+    constexpr bool ROWS = sizeof...(EXT) != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned long long* cand = reinterpret_cast<unsigned long long*>(smem_raw);  // [TOPK_FAST_CAP]
     uint32_t* tmax = reinterpret_cast<uint32_t*>(cand + TOPK_FAST_CAP);         // [NT]
@@ -229,7 +273,12 @@ __global__ __launch_bounds__(NT, 8) void topk_fast_kernel(const float* __restric
     for (int w = tid; w < nwords; w += NT) bitmap[w] = 0u;
     if (tid == 0) ctl[0] = 0u;
     __syncthreads();
-    if (indptr) {
+    if constexpr (ROWS) {
+        const TopkRowsArgs& e = rows_args(ext...);
+        const int64_t mr = e.rows ? e.rows[row_id] : (int64_t)row_id;
+        if (indptr) mask_row_bits<NT>(bitmap, I, indptr, indices, mr, tid);
+        if (e.indptr2) mask_row_bits<NT>(bitmap, I, e.indptr2, e.indices2, mr, tid);
+    } else if (indptr) {
         const int64_t beg = indptr[row_id], end = indptr[row_id + 1];
         for (int64_t j = beg + tid; j < end; j += NT) {
             const int c = indices[j];
@@ -320,6 +369,19 @@ __global__ __launch_bounds__(NT, 8) void topk_fast_kernel(const float* __restric
             }
             __syncthreads();
         }
+    }
+    if constexpr (ROWS) {  // the same list, the values times the row's factor
+        const TopkRowsArgs& e = rows_args(ext...);
+        const float sc = (val_out && e.scale) ? e.scale[row_id] : 1.f;
+        for (int j = tid; j < k; j += NT) {
+            const unsigned long long c = cand[j];
+            idx_out[(int64_t)row_id * k + j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(c & 0xFFFFFFFFull));
+            if (val_out) {
+                const float v = key_to_float((uint32_t)(c >> 32));
+                val_out[(int64_t)row_id * k + j] = e.scale ? v * sc : v;
+            }
+        }
+        return;
     }
     for (int j = tid; j < k; j += NT) {
         const unsigned long long c = cand[j];
@@ -569,6 +631,64 @@ __global__ __launch_bounds__(256) void topn_metrics_kernel(const int64_t* __rest
     }
 }
 
+// Both top-k entries: the fast path where it applies, then the radix-select kernel (alone, or for the rows the fast path marked).
+// EXT is the kernels' own pack: empty (gdmcf_topk_masked_f32) or one TopkRowsArgs, handed on behind the plain arguments.
+template <class... EXT>
+int topk_launch(const char* what, const float* pred, int64_t ldp, int B, int I, const int64_t* mask_indptr,
+                const int32_t* mask_indices, int k, int64_t* idx_out, float* val_out, hipStream_t stream, const EXT... ext) {
+    int KP = 2;
+    while (KP < k) KP <<= 1;
+    const size_t lds_base = (size_t)KP * 8 + (256 + 24) * 4 + (size_t)((I + 31) / 32) * 4;
+    GdProfScope prof(9, 4.0 * B * (double)I, stream);  // (both launches)
+    // the fast path (topk_fast_kernel): rows up to 40 960 wide, k <= 256 -- followed by topk_kernel for the rows it marks
+    static const int fast_on = getenv("GDMCF_TOPK_FAST") ? atoi(getenv("GDMCF_TOPK_FAST")) : 1;  // 0: the radix-select kernel only
+    const bool fast = fast_on && k <= 256 && I <= 1024 * 40 && k <= I;
+    if (fast) {
+        const size_t lds_f = (size_t)TOPK_FAST_CAP * 8 + (1024 + 4) * 4 + (size_t)((I + 31) / 32) * 4;
+        if (I <= 1024 * 8)
+            hipLaunchKernelGGL((topk_fast_kernel<1024, 8, EXT...>), dim3(B), dim3(1024), lds_f, stream, pred, ldp, I, mask_indptr,
+                               mask_indices, k, idx_out, val_out, ext...);
+        else if (I <= 1024 * 34)
+            hipLaunchKernelGGL((topk_fast_kernel<1024, 34, EXT...>), dim3(B), dim3(1024), lds_f, stream, pred, ldp, I, mask_indptr,
+                               mask_indices, k, idx_out, val_out, ext...);
+        else
+            hipLaunchKernelGGL((topk_fast_kernel<1024, 40, EXT...>), dim3(B), dim3(1024), lds_f, stream, pred, ldp, I, mask_indptr,
+                               mask_indices, k, idx_out, val_out, ext...);
+    }
+    const int redo = fast ? 1 : 0;
+    // (behind the fast path the marked rows are rare: the variant that does not stage the row needs 6 KB of LDS instead of 140 and
+    // its workgroups -- all but the marked ones return at once -- are dispatched many per CU)
+    const bool stage = !redo && lds_base + (size_t)I * 4 <= 150 * 1024;
+    const size_t lds = lds_base + (stage ? (size_t)I * 4 : 0);
+    if (lds > 160 * 1024) {
+        gdmcf_set_error("%s: row width %d needs %zu B of LDS (> 160 KiB)", what, I, lds);
+        return GDMCF_E_UNSUPPORTED;
+    }
+    static bool attr_set = false;  // (one per instantiation of this function, for its own two kernels)
+    if (!attr_set) {
+        void (*const k_stage)(const float*, int64_t, int, const int64_t*, const int32_t*, int, int, int64_t*, float*, int, EXT...) =
+            &topk_kernel<true, 1024, EXT...>;
+        void (*const k_plain)(const float*, int64_t, int, const int64_t*, const int32_t*, int, int, int64_t*, float*, int, EXT...) =
+            &topk_kernel<false, 1024, EXT...>;
+        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stage), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            160 * 1024);
+        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            160 * 1024);
+        if (e1 != hipSuccess || e2 != hipSuccess) {
+            gdmcf_set_error("%s: hipFuncSetAttribute failed", what);
+            return GDMCF_E_HIP;
+        }
+        attr_set = true;
+    }
+    if (stage)
+        hipLaunchKernelGGL((topk_kernel<true, 1024, EXT...>), dim3(B), dim3(1024), lds, stream, pred, ldp, I, mask_indptr,
+                           mask_indices, k, KP, idx_out, val_out, redo, ext...);
+    else
+        hipLaunchKernelGGL((topk_kernel<false, 1024, EXT...>), dim3(B), dim3(1024), lds, stream, pred, ldp, I, mask_indptr,
+                           mask_indices, k, KP, idx_out, val_out, redo, ext...);
+    return gd_launch_status(what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -579,53 +699,22 @@ int gdmcf_topk_masked_f32(const float* pred, int64_t ldp, int B, int I, const in
     GD_CHECK_SHAPE(k >= 1 && k <= I, "topk: k out of range (selected index k out of range)");
     GD_CHECK_ARG(k <= 2048, "topk: k > 2048 unsupported");
     GD_CHECK_ARG((mask_indptr == nullptr) == (mask_indices == nullptr), "topk: mask indptr/indices mismatch");
-    int KP = 2;
-    while (KP < k) KP <<= 1;
-    const size_t lds_base = (size_t)KP * 8 + (256 + 24) * 4 + (size_t)((I + 31) / 32) * 4;
-    GdProfScope prof(9, 4.0 * B * (double)I, (hipStream_t)stream);  // (both launches)
-    // the fast path (topk_fast_kernel): rows up to 40 960 wide, k <= 256 -- followed by topk_kernel for the rows it marks
-    static const int fast_on = getenv("GDMCF_TOPK_FAST") ? atoi(getenv("GDMCF_TOPK_FAST")) : 1;  // 0: the radix-select kernel only
-    const bool fast = fast_on && k <= 256 && I <= 1024 * 40 && k <= I;
-    if (fast) {
-        const size_t lds_f = (size_t)TOPK_FAST_CAP * 8 + (1024 + 4) * 4 + (size_t)((I + 31) / 32) * 4;
-        if (I <= 1024 * 8)
-            hipLaunchKernelGGL((topk_fast_kernel<1024, 8>), dim3(B), dim3(1024), lds_f, (hipStream_t)stream, pred, ldp, I, mask_indptr,
-                               mask_indices, k, idx_out, val_out);
-        else if (I <= 1024 * 34)
-            hipLaunchKernelGGL((topk_fast_kernel<1024, 34>), dim3(B), dim3(1024), lds_f, (hipStream_t)stream, pred, ldp, I, mask_indptr,
-                               mask_indices, k, idx_out, val_out);
-        else
-            hipLaunchKernelGGL((topk_fast_kernel<1024, 40>), dim3(B), dim3(1024), lds_f, (hipStream_t)stream, pred, ldp, I, mask_indptr,
-                               mask_indices, k, idx_out, val_out);
-    }
-    const int redo = fast ? 1 : 0;
-    // (behind the fast path the marked rows are rare: the variant that does not stage the row needs 6 KB of LDS instead of 140 and
-    // its workgroups -- all but the marked ones return at once -- are dispatched many per CU)
-    const bool stage = !redo && lds_base + (size_t)I * 4 <= 150 * 1024;
-    const size_t lds = lds_base + (stage ? (size_t)I * 4 : 0);
-    if (lds > 160 * 1024) {
-        gdmcf_set_error("topk: row width %d needs %zu B of LDS (> 160 KiB)", I, lds);
-        return GDMCF_E_UNSUPPORTED;
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_kernel<true, 1024>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_kernel<false, 1024>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            gdmcf_set_error("topk: hipFuncSetAttribute failed");
-            return GDMCF_E_HIP;
-        }
-        attr_set = true;
-    }
-    if (stage)
-        hipLaunchKernelGGL((topk_kernel<true, 1024>), dim3(B), dim3(1024), lds, (hipStream_t)stream, pred, ldp, I, mask_indptr,
-                           mask_indices, k, KP, idx_out, val_out, redo);
-    else
-        hipLaunchKernelGGL((topk_kernel<false, 1024>), dim3(B), dim3(1024), lds, (hipStream_t)stream, pred, ldp, I, mask_indptr,
-                           mask_indices, k, KP, idx_out, val_out, redo);
-    return gd_launch_status("topk");
+    return topk_launch("topk", pred, ldp, B, I, mask_indptr, mask_indices, k, idx_out, val_out, (hipStream_t)stream);
+}
+
+int gdmcf_topk_masked_rows_f32(const float* pred, int64_t ldp, int B, int I, const int64_t* indptr, const int32_t* indices,
+                               const int64_t* indptr2, const int32_t* indices2, const int64_t* rows, const float* scale, int k,
+                               int64_t* idx_out, float* val_out, void* stream) {
+    GD_CHECK_SHAPE(B > 0 && I > 0 && ldp >= I, "gdmcf_topk_masked_rows_f32: bad shape (B > 0, I > 0, ldp >= I)");
+    GD_CHECK_SHAPE(k >= 1 && k <= I, "gdmcf_topk_masked_rows_f32: k out of range (selected index k out of range)");
+    GD_CHECK_ARG(k <= 2048, "gdmcf_topk_masked_rows_f32: k > 2048 unsupported");
+    GD_CHECK_ARG((indptr == nullptr) == (indices == nullptr), "gdmcf_topk_masked_rows_f32: mask indptr/indices mismatch");
+    GD_CHECK_ARG((indptr2 == nullptr) == (indices2 == nullptr), "gdmcf_topk_masked_rows_f32: second mask indptr/indices mismatch");
+    GD_CHECK_ARG(indptr2 == nullptr || indptr != nullptr, "gdmcf_topk_masked_rows_f32: a second CSR needs the first");
+    GD_CHECK_ARG(pred && idx_out, "gdmcf_topk_masked_rows_f32: null pred / idx_out");
+    const TopkRowsArgs ext = {indptr2, indices2, rows, scale};
+    return topk_launch("gdmcf_topk_masked_rows_f32", pred, ldp, B, I, indptr, indices, k, idx_out, val_out, (hipStream_t)stream,
+                       ext);
 }
 
 int gdmcf_spmm_csr_f32(const int64_t* vbeg, const int64_t* vend, const int32_t* vrow, const int32_t* vslot, int n_virtual, int n_short,

@@ -48,18 +48,27 @@ def train_one_epoch(diffusion, model, optimizer, train_csr, batch_size, device, 
 
 @torch.no_grad()
 def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps, sampling_noise, batch_size,
-             device, sparse=False, latent=False):
+             device, sparse=False, latent=False, recommend=False):
     """Precision / Recall / NDCG / MRR @topN exactly as reference main.py:267-310.
 
     data_csr: rows fed to p_sample (the reference feeds the training rows); data_te: ground-truth CSR;
     mask_his: CSR of interactions to exclude from the ranking.  sparse=True: p_sample receives each batch as a
     data_utils.CsrBatch (never densified where the reverse loop takes sparse rows; densified inside p_sample otherwise).
     latent=True: p_sample(latent=True) -- the reverse loop in the first hidden layer's space where
-    GaussianDiffusion._latent_reverse_ok holds; composes with sparse=True."""
+    GaussianDiffusion._latent_reverse_ok holds; composes with sparse=True.
+    recommend=True: each batch's list comes from gdmcf_amd.recommend with mask_his as a DeviceCSR -- uploaded once
+    per call, or passed through when it already is one -- so no batch slices a matrix on the host; `sparse` and `latent` are
+    then ignored (recommend picks its own route, `diffusion.last_recommend_route`)."""
     model.eval()
     n = mask_his.shape[0]
     predict_items = []
     dcsr = data_csr if isinstance(data_csr, DeviceCSR) else DeviceCSR(data_csr, device)
+    if recommend:
+        from .recommend import recommend as recommend_fn
+        mask = mask_his if isinstance(mask_his, DeviceCSR) else DeviceCSR(mask_his, device)
+        lists = recommend_fn(diffusion, model, dcsr, np.arange(n), topN[-1], mask=mask, sampling_steps=sampling_steps,
+                             sampling_noise=sampling_noise, batch_size=batch_size)  # (the same batches, made inside)
+        return evaluate_utils.computeTopNAccuracy_device(data_te, lists, topN)
     for lo in range(0, n, batch_size):
         rows = np.arange(lo, min(lo + batch_size, n))
         batch = dcsr.batch(torch.from_numpy(rows)) if sparse else dcsr.rows(torch.from_numpy(rows))

@@ -369,9 +369,10 @@ class DenoiserEngine(EngineBase):
     # ------------------------------------------------------------------------------------------
     @with_precision
     def p_sample_loop(self, x_start, steps, T, tabs32, eps_mode, sampling_noise, noise0=None, step_noise=None,
-                      capture=None, draw_noise=None, latent=False):
+                      capture=None, draw_noise=None, latent=False, _stop=False):
         """latent: carry the loop in the first hidden layer's space (_latent_loop; the caller has checked
-        GaussianDiffusion._latent_reverse_ok).
+        GaussianDiffusion._latent_reverse_ok).  _stop (with latent; gdmcf_amd.recommend): end the loop at its last operands and
+        return (A, second, K, b_out) instead of x_0.
         tabs32: dict of float32 device tables [T] (sqrt_ab, sqrt_1mab, c1, c2, r1, r2, sigma).  draw_noise(like) -> [B, I]
         float32 N(0,1): the reverse loop's th.randn_like(x_t) (reference :210-217); default: gdmcf_randn_f32 on the engine's
         Philox seed (stream 7, one offset per draw).
@@ -400,7 +401,7 @@ class DenoiserEngine(EngineBase):
             if eps_mode or sampling_noise or capture is not None or m.norm or self.gemm_dtype != "f32":
                 raise RuntimeError("gdmcf_amd: the latent reverse loop takes the x0 target without sampling noise, capture or "
                                    "F.normalize, in float32 products (GaussianDiffusion._latent_reverse_ok)")
-            return self._latent_loop(bufs, layers, x_start, csr, steps, T, tabs32, noise0)
+            return self._latent_loop(bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=_stop)
         if bufs.xin2 is None:
             bufs.xin2 = torch.zeros_like(bufs.xin)
         if self.gemm_dtype == "bf16" and getattr(bufs, "sh_xin2", None) is None:
@@ -480,14 +481,16 @@ class DenoiserEngine(EngineBase):
         del keep
         return out
 
-    def _latent_loop(self, bufs, layers, x_start, csr, steps, T, tabs32, noise0):
+    def _latent_loop(self, bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=False):
         """The reverse loop in the first hidden layer's space.  With the x0 target and no sampling noise the loop is linear in x_t
         between two hidden activations, x_{t-1} = c1[t] (W_out a_t + b_out) + c2[t] x_t, so p_t = W1x x_t obeys
             p_{t-1} = c1[t] (M a_t + v) + c2[t] p_t,    M = W1x W_out,  v = W1x b_out,    h_{t-1} = tanh(p_{t-1} + e_{t-1})
         (one gdmcf_latent_step_f32 per step; M, v and the table e are _latent_operands).  Two item-wide products remain whatever T
         is: the first layer on x_T into p (no time columns, no activation; a gather on CSR rows) and the output product of the last
         step, x_0 = c1[0] (W_out a_0 + b_out) -- posterior_mean_coef2[0] is exactly 0.  x_T is built as in the item-space loop: same
-        builder, same Philox offsets."""
+        builder, same Philox offsets.
+        stop: return (A, second, K, b_out), the operands of the last product x_0 = c1[0] (A second^T + b_out), without running it;
+        on CSR rows no builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had."""
         lib, st, I = self.lib, _lib.stream_ptr(), self.I
         B, dev = x_start.shape[0], x_start.device
         (w1, b1, act1), (w, bias, _) = layers[0], layers[-1]
@@ -507,7 +510,10 @@ class DenoiserEngine(EngineBase):
         p = bufs.lat_p
         t_vec = torch.full((B,), max(steps - 1, 0), dtype=torch.int64, device=dev)
         if csr is not None:
-            keep = self._prep_csr(bufs, csr, t_vec, None, None, None, None, False)  # x_T = x_0 (the output product's x_t operand)
+            if stop:
+                keep, self.offset = None, self.offset + 1  # (where _prep_csr would have drawn)
+            else:
+                keep = self._prep_csr(bufs, csr, t_vec, None, None, None, None, False)  # x_T = x_0 (the output product's x_t operand)
             wt = self._transposed(w1)
             core.gather_fwd(lib, None, None, csr, wt, I, None, None, 0, None, 0, B, h1, p, st)
         else:
@@ -526,6 +532,9 @@ class DenoiserEngine(EngineBase):
                 core.linear_fwd(lib, bufs, A, wl, bl, al, B, wl.shape[0], wl.shape[1], out, st)
                 A = out
             if i == 0:
+                if stop:
+                    x0 = (A, w, K, bias)
+                    break
                 x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
                 core.posterior_fwd(lib, A, w, bias, bufs.xin, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
                 break

@@ -408,6 +408,18 @@ class EngineBase:
         self._latent = (key, o)
         return o
 
+    @with_precision
+    def score_product(self, A, second, K, b_out, B, device):
+        """A second^T + b_out into the [B, I] score buffer of this batch size (made on first use, reused by every later call): the
+        last product of a latent reverse loop that was ended at its operands (gdmcf_amd.recommend), without the posterior
+        epilogue -- c2[0] is 0 and the caller's top-k does not need the factor c1[0]."""
+        bufs = self.buffers(B, device)
+        if getattr(bufs, "scores", None) is None:
+            bufs.scores = torch.empty(B, self.I, dtype=torch.float32, device=device)
+        self._grow_workspace(bufs, B, device, [(self.I, K)])
+        linear_fwd(self.lib, bufs, A, second, b_out, 0, B, self.I, K, bufs.scores, _lib.stream_ptr())
+        return bufs.scores
+
     def _gather_first_layer(self, bufs, batch, w, bias, act, xin, B, out, st):
         """act([x_0 | emb] @ w^T + bias) for the binary, undropped CSR rows of `batch` as a sum of rows of the cached w^T
         (gdmcf_gather_fwd_f32) instead of the [B, I + E] x [I + E, N] product; `xin` holds this step's embedding columns."""

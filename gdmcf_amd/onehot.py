@@ -444,7 +444,7 @@ class OneHotEngine(EngineBase):
         bufs.hcat = t
 
     @with_precision
-    def latent_loop(self, x_T, x_U, T, c1, c2, index=None, before_step=None):
+    def latent_loop(self, x_T, x_U, T, c1, c2, index=None, before_step=None, _stop=False):
         """The whole reverse loop with x_t carried as p_t = W1x x_t, the first layer of branch 1 without its time columns
         (DenoiserEngine._latent_loop has the algebra): per step one gdmcf_latent_step_f32 with A = the activation behind
         [h | h_U] that feeds the last product and M = W1x . W_out (an embedding backbone: W1x . V^), plus the small layers.
@@ -453,7 +453,9 @@ class OneHotEngine(EngineBase):
         gdmcf_gather_fwd_f32 with that step's row of the time table as the bias.  Item-wide work per call: branch 1's first layer
         on x_T (a gather on CSR rows), branch 2's once, and the last product, x_0 = c1[0] (W_out a_0 + b_out).
         x_T: dense [B, I] rows or a data_utils.CsrBatch of binary rows; x_U: the [B, 2I] image or a SparseXU; c1, c2: [T, B]
-        tables; before_step(n, i): called ahead of step n (timestep i), e.g. the degree-guided graph update."""
+        tables; before_step(n, i): called ahead of step n (timestep i), e.g. the degree-guided graph update.
+        _stop (gdmcf_amd.recommend): return (A, second, K, b_out), the operands of the last product, without running it; on CSR
+        rows no builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had."""
         from .data_utils import CsrBatch
         lib, st, I = self.lib, _lib.stream_ptr(), self.I
         B, dev = x_T.shape[0], x_T.device
@@ -480,7 +482,11 @@ class OneHotEngine(EngineBase):
             bufs.lat_P2 = torch.zeros(B, _ceil64(hf2), **f32)
         p = bufs.lat_p
         # p_T and the x_t operand of the last product (c2[0] == 0: it only has to be finite)
-        if isinstance(x_T, CsrBatch):
+        if isinstance(x_T, CsrBatch) and _stop:
+            self.offset += 1  # (where the builder would have drawn)
+            keep = xdense = None
+            core.gather_fwd(lib, None, None, x_T, self._transposed(w1), I, None, None, 0, None, 0, B, hf1, p, st)
+        elif isinstance(x_T, CsrBatch):
             if bufs.x0bits is None:
                 bufs.x0bits = torch.zeros(B, (I + 31) // 32, dtype=torch.int32, device=dev)
             self.offset += 1
@@ -522,7 +528,9 @@ class OneHotEngine(EngineBase):
                 core.gather_fwd(lib, P2, None, None, None, I, None, None, 0, e2[i], act2, B, hf2, o2, st)
                 self._chain_forward(bufs, br2[1:], bufs.acts2[1:], o2, B, hcat2)
                 A = self._latent_A(bufs, out, B, index)
-                if i == 0:
+                if i == 0 and _stop:
+                    x0 = (A, second, K, b_out)
+                elif i == 0:
                     x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
                     core.posterior_fwd(lib, A, second, b_out, xdense, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
                 else:

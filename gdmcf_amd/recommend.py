@@ -1,0 +1,172 @@
+"""`recommend`: ranked top-k items per user id for the diffusion models, in one call, from rows that stay on the device
+(DESIGN 4.10).  What `driver.evaluate` does per batch -- reverse loop, history mask, top-k (reference main.py:288-301) -- with the
+mask rows picked on the device by user id (gdmcf_topk_masked_rows_f32) and, where the reverse loop runs in the first hidden
+layer's space, without the dense x_T, the posterior epilogue and x_0 itself: the top-k is invariant under the positive factor
+c1[0], so the raw scores of the last product are ranked and only the k returned values are scaled."""
+import numpy as np
+import torch
+
+from . import _lib
+from . import engine_core as core
+from .data_utils import CsrBatch, DeviceCSR
+
+
+def _c1_0_positive(diffusion):
+    """posterior_mean_coef1[0] > 0 as float32, from the host's float64 table (gdmcf_schedule_build; no device read); once per
+    table set."""
+    c1 = diffusion._t32.get("c1")
+    rec = getattr(diffusion, "_recommend_c1_rec", None)
+    if rec is None or rec[0] is not c1:
+        from .gaussian_diffusion import _SCHEDULE_KIND
+        tabs = _lib.schedule_tables(_SCHEDULE_KIND[diffusion.noise_schedule], diffusion.noise_scale, diffusion.noise_min,
+                                    diffusion.noise_max, diffusion.steps, diffusion.beta_fixed)
+        c1_0 = np.float32(tabs[_lib.TABLE_NAMES.index("posterior_mean_coef1")][0])
+        rec = diffusion._recommend_c1_rec = (c1, bool(np.isfinite(c1_0) and c1_0 > 0))
+    return rec[1]
+
+
+def route_of(diffusion, model, rows, sampling_steps=0, sampling_noise=False):
+    """Which route `recommend` takes for this call:
+      "latent-csr"  GaussianDiffusion._latent_reverse_ok holds (x0 target, no sampling noise, no F.normalize, no active dropout,
+                    float32 products, DNN / DNNOneHot / DNNOneHotEmbedding / DNNOneHotEmbeddingGCN), sampling_steps == 0 and every
+                    value of `rows` is 1: gathered first layers, latent steps, one item-wide product, top-k on the raw scores
+      "latent"      _latent_reverse_ok holds but x_T is not the binary rows (sampling_steps > 0, values other than 1): the same,
+                    from dense rows
+      "item"        everything else: p_sample as driver.evaluate calls it, then the top-k."""
+    if not (diffusion._latent_reverse_ok(model, sampling_noise, None) and _c1_0_positive(diffusion)):
+        return "item"
+    return "latent-csr" if (sampling_steps == 0 and rows.values is None) else "latent"
+
+
+def _step_tables(diffusion, B, cache):
+    """[T, B] float32 tables of posterior_mean_coef1 / 2, one pair per batch size of the call."""
+    if B not in cache:
+        T = diffusion.steps
+        cache[B] = tuple(diffusion._t32[k][:T, None].expand(T, B).contiguous() for k in ("c1", "c2"))
+    return cache[B]
+
+
+def _latent_operands(diffusion, model, x, steps, index, tabs, noise0=None, sampled0=None):
+    """The latent reverse loop on `x` (a CsrBatch of binary rows with steps == 0, or dense rows), ended before its last product:
+    (A, second, K, b_out).  The one-hot variants' inputs and the degree-guided graph of an `indexIn` loop are built as
+    GaussianDiffusionDiscrete.p_sample(latent=True) builds them: same draws, same `last_graph`."""
+    eng = model.engine
+    if not diffusion.CatOneHot:
+        return eng.p_sample_loop(x, steps, diffusion.steps, diffusion._t32, False, False, noise0=noise0, latent=True, _stop=True)
+    model = diffusion._onehot_model(model)
+    B, dev = x.shape[0], x.device
+    c1, c2 = tabs
+    deg = None
+    if isinstance(x, CsrBatch):
+        x_tU, keep, x_t = eng.onehot_rows_sparse(x), None, x
+        if diffusion.indexIn:
+            ip = x.csr.indptr
+            deg = (ip[x.row_ids + 1] - ip[x.row_ids]).to(torch.float32)
+    else:
+        x0 = x.float().contiguous()
+        if steps == 0:
+            x_tU, keep = eng.onehot_rows(x0, None, (x0 != 0).to(torch.uint8), diffusion.discrete)
+            x_t = x0
+        else:
+            t = torch.full((B,), steps - 1, dtype=torch.int64, device=dev)
+            x_tU, keep = eng.onehot_rows(x0, t, sampled0, diffusion.discrete)
+            x_t = diffusion.q_sample(x0, t, noise0)
+        if diffusion.indexIn:
+            deg = x0.sum(dim=1)
+    graph = degp = None
+    if deg is not None:
+        graph = torch.zeros(B, x.shape[1], dtype=torch.uint8, device=dev)
+        degp = (deg / deg.max()).float().contiguous()
+
+    def before_step(n, i):
+        if graph is not None:
+            diffusion._graph_step(graph, torch.full((B,), i, dtype=torch.int64, device=dev), degp, None, None)
+
+    ops = eng.latent_loop(x_t, x_tU, diffusion.steps, c1, c2, index=index if diffusion.indexIn else None,
+                          before_step=before_step, _stop=True)
+    del keep
+    diffusion.last_graph = graph
+    return ops
+
+
+def _as_mask(mask, rows):
+    if mask is None:
+        return ()
+    if isinstance(mask, str):
+        if mask != "rows":
+            raise ValueError('recommend: mask is "rows", None, a DeviceCSR or a pair of DeviceCSRs')
+        return (rows,)
+    masks = (mask,) if isinstance(mask, DeviceCSR) else tuple(mask)
+    if not 1 <= len(masks) <= 2 or not all(isinstance(m, DeviceCSR) for m in masks):
+        raise ValueError('recommend: mask is "rows", None, a DeviceCSR or a pair of DeviceCSRs')
+    return masks
+
+
+def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_steps=0, sampling_noise=False, batch_size=400,
+              return_values=False, noise0=None, sampled0=None):
+    """Top-k item ids [n, k] (int64, on the device; with return_values: (values [n, k] float32, ids)) for the users `user_ids` of
+    the DeviceCSR `rows`: the reverse loop from each user's row, the mask's items set to -inf, the k largest predictions in
+    descending order, equal ones in ascending item index (evaluate_utils.masked_topk's conventions).
+
+    user_ids: int64 tensor or sequence, any order, repeats allowed; uploaded once.  mask: "rows" (the same matrix, as the
+    reference's evaluation), None, a DeviceCSR, or a pair of them (both are masked: train + valid without a summed matrix).
+    The users are worked in chunks of `batch_size`; per chunk only launches are enqueued -- no scipy slicing, no copy from the
+    host, no synchronisation.  `diffusion.last_recommend_route` names the route (route_of).  On the two latent routes the values
+    are c1[0] times the raw scores of the last product, within float32 rounding of p_sample's x_0; on the "item" route values and
+    ids are masked_topk(p_sample(...))'s bits.  With `diffusion.indexIn` the chunk's ids are the model's `index`.
+    The ids are range-checked once per call (the kernels do not check them): on the host for a host sequence; ids that already
+    live on the device cost the call's one synchronising copy there.
+    noise0 [n, I] / sampled0 [n, I] inject the draws of x_T with sampling_steps > 0, row for row of user_ids, as p_sample's
+    keywords of the same names do (parity runs)."""
+    if not isinstance(rows, DeviceCSR):
+        raise TypeError("gdmcf_amd.recommend: rows must be a gdmcf_amd.data_utils.DeviceCSR")
+    _lib.require_gpu(rows.indptr, "rows")
+    masks = _as_mask(mask, rows)
+    for m in masks:
+        _lib.require_gpu(m.indptr, "mask")
+    dev, (U, I) = rows.device, rows.shape
+    k, batch_size = int(k), int(batch_size)
+    if not 1 <= k <= I:
+        raise AssertionError("selected index k out of range")
+    if batch_size < 1:
+        raise ValueError("recommend: batch_size must be positive")
+    ids = torch.as_tensor(user_ids, dtype=torch.int64).reshape(-1)
+    n_ok = min([U] + [m.shape[0] for m in masks])
+    if ids.numel():  # (a device tensor costs one synchronising copy per call here; a host sequence none)
+        lo, hi = torch.aminmax(ids)
+        if not (0 <= int(lo) and int(hi) < n_ok):
+            raise IndexError("recommend: user_ids out of range")
+    ids = ids.to(dev).contiguous()
+    n = ids.numel()
+    route = route_of(diffusion, model, rows, sampling_steps, sampling_noise)
+    diffusion.last_recommend_route = route
+    idx = torch.empty(n, k, dtype=torch.int64, device=dev)
+    val = torch.empty(n, k, dtype=torch.float32, device=dev) if return_values else None
+    if n == 0:
+        return (val, idx) if return_values else idx
+    lib, eng = _lib.load(), model.engine
+    ip1, ix1 = (masks[0].indptr, masks[0].indices) if masks else (None, None)
+    ip2, ix2 = (masks[1].indptr, masks[1].indices) if len(masks) > 1 else (None, None)
+    tabs = {}
+    for lo in range(0, n, batch_size):
+        chunk = ids[lo:lo + batch_size]
+        B = chunk.numel()
+        index = chunk if getattr(diffusion, "indexIn", False) else None
+        scale = None
+        inj = {name: t[lo:lo + B].to(dev) for name, t in (("noise0", noise0), ("sampled0", sampled0)) if t is not None}
+        if route == "item":
+            kw = dict(inj, index=index) if index is not None else inj
+            scores = core._f32_rows(diffusion.p_sample(model, rows.rows(chunk), sampling_steps, sampling_noise, **kw))
+        else:
+            x = rows.batch(chunk) if route == "latent-csr" else rows.rows(chunk)
+            c1, c2 = _step_tables(diffusion, B, tabs)
+            with torch.no_grad():
+                A, second, K, b_out = _latent_operands(diffusion, model, x, sampling_steps, index, (c1, c2), **inj)
+                scores = eng.score_product(A, second, K, b_out, B, dev)
+            scale = c1[0]
+            diffusion.last_reverse_route = "latent"
+        v = val[lo:lo + B] if val is not None else None
+        _lib.check(lib.gdmcf_topk_masked_rows_f32(
+            scores.data_ptr(), scores.stride(0), B, I, _lib.ptr(ip1), _lib.ptr(ix1), _lib.ptr(ip2), _lib.ptr(ix2),
+            chunk.data_ptr(), _lib.ptr(scale), k, idx[lo:lo + B].data_ptr(), _lib.ptr(v), _lib.stream_ptr()))
+    return (val, idx) if return_values else idx

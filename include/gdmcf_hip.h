@@ -472,6 +472,18 @@ int gdmcf_adamw_bf16s_f32(const int64_t* table, const int64_t* shadow_table, int
 int gdmcf_topk_masked_f32(const float* pred, int64_t ldp, int B, int I, const int64_t* mask_indptr,
                           const int32_t* mask_indices, int k, int64_t* idx_out, float* val_out,
                           void* stream);
+/* The same selection with the mask picked by row id (gdmcf_amd.recommend): row b of pred is masked by row rows[b] of the FULL
+ * CSR (indptr int64 [n_users + 1], indices int32; both NULL = no mask) and, when given, of a second full CSR over the same
+ * rows (indptr2 / indices2; needs the first) -- the reference's mask_tv = train + valid without a summed matrix.  rows int64
+ * [B], every entry a row of both CSRs (not checked on the device); NULL = rows 0..B-1.  Selection, tie rule (equal scores in
+ * ascending item index), degenerate rows (masked items count as -inf and appear, lowest index first, only when fewer than k
+ * items are unmasked) and the handling of unsorted, repeated or out-of-range indices are gdmcf_topk_masked_f32's: with
+ * scale == NULL idx_out / val_out are bit for bit what it returns for the same pred and the sub-CSR csr[rows] (or
+ * (csr + csr2)[rows]).  scale (optional, float32 [B], > 0) multiplies the returned values only, after selection:
+ * val_out[b, j] *= scale[b].  Same shape limits and error codes; no global atomics, no workspace, no host synchronisation. */
+int gdmcf_topk_masked_rows_f32(const float* pred, int64_t ldp, int B, int I, const int64_t* indptr, const int32_t* indices,
+                               const int64_t* indptr2, const int32_t* indices2, const int64_t* rows, const float* scale, int k,
+                               int64_t* idx_out, float* val_out, void* stream);
 
 /* ---- LightGCN ranking: score product fused with the masked top-k (lightGCN.py:67-127, get_metrics) -----------
  * replaces `relevance_score = user_emb @ item_emb.T`, the dense -inf mask of the training interactions added to it and
