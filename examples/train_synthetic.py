@@ -42,9 +42,11 @@ def main():
                     help="GEMM mode of the DNN denoiser (f32x3: float32 products from three-term bf16 splits, DESIGN 4.4b)")
     ap.add_argument("--sparse-rows", action="store_true", help="feed the training rows as CSR batches (never densified)")
     ap.add_argument("--recommend-eval", action="store_true",
-                    help="evaluate through gdmcf_amd.recommend (top-k per user id from device CSR rows; ignores --latent-eval)")
-    ap.add_argument("--latent-eval", action="store_true",
-                    help="evaluate with the reverse loop in the first hidden layer's space (p_sample(latent=True)) where it applies")
+                    help="evaluate through gdmcf_amd.recommend (top-k per user id from device CSR rows; of --latent-eval only `extended` matters)")
+    ap.add_argument("--latent-eval", nargs="?", const=True, default=False, choices=["extended"],
+                    help="evaluate with the reverse loop in the first hidden layer's space (p_sample(latent=True)) where it applies; "
+                         "`--latent-eval extended`: p_sample(latent=\"extended\"), the eps target and DNNCat too (also with "
+                         "--recommend-eval)")
     ap.add_argument("--graph", action="store_true", help="replay the training step from one hipGraph (single GPU, dnn backbone)")
     ap.add_argument("--backbone", default="dnn", choices=["dnn", "onehot", "onehot-emb", "onehot-gcn"],
                     help="onehot: GaussianDiffusionDiscrete(CatOneHot=True) + DNNOneHot; onehot-emb: + user / item embedding "

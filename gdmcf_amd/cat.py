@@ -21,8 +21,8 @@ run on `csr.rows(ids)`.  The default stays
 eps target, values other than 1, torch-drawn noise).
 
 Not built (each raises NotImplementedError): `norm=True`, GEMM inputs other than f32, AdamW fused into the backward pass
-(dxin reads W1: the first layer's update must not run before it), the graphed step, data parallel; the reverse loop takes
-dense rows only.  Constructor, parameter names and initialisation draw order are the reference's, so checkpoints interchange.
+(dxin reads W1: the first layer's update must not run before it), the graphed step, data parallel; the item-space
+reverse loop takes dense rows only (the latent one, `p_sample(latent="extended")`, also binary CSR rows: CatEngine.latent_loop).  Constructor, parameter names and initialisation draw order are the reference's, so checkpoints interchange.
 """
 import numpy as np
 import torch
@@ -31,7 +31,7 @@ import torch.nn as nn
 from . import _lib
 from . import engine_core as core
 from .engine import DenoiserEngine
-from .engine_core import with_precision
+from .engine_core import _Bufs, with_precision
 from .onehot import OneHotEngine
 
 
@@ -163,6 +163,121 @@ class CatEngine(DenoiserEngine):
         res = self._last_layer(bufs, A, w, bias, act, B, w.shape[0], w.shape[1], keep[0], posterior)
         del keep
         return res
+
+    # -- reverse loop in the first hidden layer's space (GaussianDiffusionDiscrete.p_sample(latent="extended")) ----------------
+    def _latent_cat_tables(self, bufs, ops, c1, B, sparse):
+        """What the loop needs of cat_layer's parameters, which live on the device: per-row coefficient vectors [B] for
+        gdmcf_latent_acc_f32, the step table c1 . w0 [T, B] and, on CSR rows, the time table with (w1 + c) S added.  Made by
+        torch from the parameters (no host read, no synchronisation) and kept until one of them, c1 or the operands change."""
+        cw, cb_ = self._cat_params()
+        key = (cw.data_ptr(), cw._version, cb_.data_ptr(), cb_._version, sparse)
+        t = getattr(bufs, "lat_cat", None)
+        if t is not None and t.key == key and t.c1_src is c1 and t.ops is ops:
+            return t
+        wv, h = cw.detach().reshape(-1), ops.S.shape[0]
+        t = _Bufs()
+        t.key, t.c1_src, t.ops = key, c1, ops
+        t.w0 = wv[0].expand(B).contiguous()
+        t.neg_w0 = -t.w0
+        t.beta = (wv[2] - wv[1]).expand(B).contiguous()
+        t.one, t.zero = torch.ones_like(t.w0), torch.zeros_like(t.w0)
+        t.c1 = c1 * wv[0]
+        t.e = ops.e
+        if sparse:
+            t.e = ops.e.clone()
+            t.e[:, :h] += (wv[1] + cb_.detach().reshape(-1)[0]) * ops.S
+        bufs.lat_cat = t
+        return t
+
+    @with_precision
+    def latent_loop(self, x_T, x_U, T, c1, c2, index=None, before_step=None, _stop=False, eps=None):
+        """OneHotEngine.latent_loop's call for this backbone.  x_tU is the same image at every step and dropout is off, so the
+        first layer's input is z_t = w0 x_t + u with u = w1 xU0 + w2 xU1 + c fixed, and its pre-activation is
+            w0 p_t + r + e_t,    p_t = W1x x_t,   r = W1x u  [B, h], once per call.
+        p~_t = w0 p_t is carried: the step of DenoiserEngine._latent_loop with c1 times w0, and h = tanh((p~ + r) + e)
+        (gdmcf_latent_step_ex_f32's row addend).
+          x_T a data_utils.CsrBatch of binary rows (x_U None: xU0 = 1 - x, xU1 = x): r = (w1 + c) S + (w2 - w1) p_T with
+            S = W1x 1 cached beside M and v; the first term is added to the time table, p_T is the one gather -- no [B, 2I]
+            image, no builder.  Item-wide work: the last product.
+          dense rows with the [B, 2I] image x_U: gdmcf_cat_prep_input_f32 once for z_T and x_T, two first-layer products
+            (W1x z_T, W1x x_T), r = W1x z_T - w0 p_T.  Item-wide work: those two and the last product, whatever T is.
+        eps / _stop: as OneHotEngine.latent_loop.  The Philox position advances as on the item-space route (the class draws,
+        then one builder per step), whether or not those kernels ran."""
+        from .data_utils import CsrBatch
+        self.flush_weight_waiters()
+        lib, st, I = self.lib, _lib.stream_ptr(), self.I
+        B, dev = x_T.shape[0], x_T.device
+        layers = self._layers()
+        bufs = self.buffers(B, dev)
+        self._shadows_on(bufs, layers)
+        self.version += 1
+        self._saved = None
+        (w1, b1, act1), (w, bias, _) = layers[0], layers[-1]
+        h1, K = w1.shape[0], w.shape[1]
+        for wl, _, _ in layers:
+            self._use_weight(wl)
+        emb = self.model.emb_layer
+        ops = self._latent_operands(w1, b1, w, K, bias, T, (w1, b1, w, bias, emb.weight, emb.bias))
+        c1_last = c1
+        if eps is not None:
+            et = eps.on(dev, B)
+            c1, c2 = et["neg_d"], et["g"]
+        sparse = isinstance(x_T, CsrBatch)
+        t = self._latent_cat_tables(bufs, ops, c1, B, sparse)
+        if getattr(bufs, "lat_p", None) is None:
+            f32 = dict(dtype=torch.float32, device=dev)
+            for name in ("lat_p", "lat_h", "lat_pT", "lat_r", "lat_s"):
+                setattr(bufs, name, torch.zeros(B, core._ceil64(h1), **f32))
+            bufs.lat_q = torch.zeros(B, core._ceil64(K), **f32)
+        p, pT, r, s, Q = bufs.lat_p, bufs.lat_pT, bufs.lat_r, bufs.lat_s, bufs.lat_q
+        if sparse:
+            self.offset += 1 + T  # (the class draws and the T builders of the item-space route)
+            keep = None
+            core.gather_fwd(lib, None, None, x_T, self._transposed(w1), I, None, None, 0, None, 0, B, h1, pT, st)
+            core.latent_acc(lib, r, t.zero, pT, t.beta, B, h1, r, st)  # r = (w2 - w1) p_T; (w1 + c) S sits in t.e
+            xdense = None if _stop else x_T.dense()
+        else:
+            xu = x_U.reshape(B, -1)
+            if xu.shape[1] != 2 * I:
+                raise RuntimeError("gdmcf_amd.DNNCat: x_U must hold two columns per item")
+            ts = torch.full((B,), T - 1, dtype=torch.int64, device=dev)
+            keep = self._cat_input(bufs, x_T, core._f32_rows(xu), ts, None, None, None, None, False), ts  # xin = z_T, xt = x_T
+            self.offset += T - 1
+            core.linear_fwd(lib, bufs, (bufs.xin.data_ptr(), bufs.xin.stride(0)), w1, None, 0, B, h1, I, s, st)
+            core.linear_fwd(lib, bufs, (bufs.xt.data_ptr(), bufs.xt.stride(0)), w1, None, 0, B, h1, I, pT, st)
+            core.latent_acc(lib, s, t.one, pT, t.neg_w0, B, h1, r, st)  # r = W1x z_T - w0 p_T
+            xdense = bufs.xt
+        core.latent_acc(lib, p, t.zero, pT, t.w0, B, h1, p, st)  # p~_T = w0 p_T
+        core.latent_acc(lib, p, t.one, r, t.one, B, h1, s, st)  # p~_T + r, then + e and tanh
+        hcur, hnxt = bufs.acts[0], bufs.lat_h
+        core.gather_fwd(lib, s, None, None, None, I, None, None, 0, t.e[T - 1], act1, B, h1, hcur, st)
+        for n, i in enumerate(range(T - 1, -1, -1)):
+            if before_step is not None:
+                before_step(n, i)
+            A = hcur
+            for li in range(1, len(layers) - 1):
+                wl, bl, al = layers[li]
+                out = bufs.acts[li]
+                core.linear_fwd(lib, bufs, A, wl, bl, al, B, wl.shape[0], wl.shape[1], out, st)
+                A = out
+            if i > 0:
+                acc = (Q, et["qa"][i], et["qb"][i], Q) if eps is not None else None
+                core.latent_step_ex(lib, A, ops.M, ops.v, p, t.c1[i], c2[i], r, t.e[i - 1], act1, B, h1, K, p, hnxt, acc, st)
+                hcur, hnxt = hnxt, hcur
+                continue
+            if eps is not None:
+                qa0, qb0 = (et["qa0_neg"], et["qb0_neg"]) if _stop else (et["qa"][0], et["qb"][0])
+                core.latent_acc(lib, Q, qa0, A, qb0, B, K, Q, st)
+                x0 = (Q, w, K, ops.neg_b, et["G"], et["D"])
+                post = (Q, et["one"], et["zero"], et["G"], et["D"])
+            else:
+                x0 = (A, w, K, bias)
+                post = (A, c1_last[0], c2[0], None, None)
+            if not _stop:
+                x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
+                core.posterior_fwd(lib, post[0], w, bias, xdense, post[1], post[2], post[3], post[4], None, None, B, I, K, x0, None, st)
+        del keep
+        return x0
 
 
 class DNNCat(nn.Module):

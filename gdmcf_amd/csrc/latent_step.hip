@@ -19,6 +19,17 @@
 //   * tails: rows past B / N are clamped for the loads (their results are never stored), the last partial chunk and every chunk of
 //     an operand whose rows are not 16-byte aligned go through guarded scalar loads; stores and the epilogue's loads fall back to
 //     scalars per pointer.
+//
+// gdmcf_latent_step_ex_f32 is a second instantiation of the same kernel template (LatentArgsEx) with two optional parts:
+//   * a per-row addend r [B, ldr] in front of the time row: h_next = act((p_next + r[b,n]) + e[n]) (DNNCat's W1x u);
+//   * an accumulator over the activations, q_next[b,k] = fma(qa[b], q_cur[b,k], qb[b] * A[b,k]) for k < K (the eps target's Q).
+//     Chunk c of A's rows b0 .. b0 + 15 already sits in wave c % 4 of EVERY column tile, lane (r, q) holding A[b0 + r, 16 c + 4 q .. + 3]:
+//     the rounds of four chunks are dealt to the column tiles in contiguous runs, and the tile that owns a round writes its 64
+//     elements per row from the operand registers -- every element exactly once, plain vector stores, no further load of A.
+// The instantiation behind gdmcf_latent_step_f32 (LatentArgs) compiles none of this: its instruction stream is the one it had.
+// gdmcf_latent_acc_f32 is the accumulator alone (the last step, where no step kernel runs): the same expression, the same bits.
+#include <type_traits>
+
 #include "common.h"
 #include "gemm_epilogue.h"
 
@@ -71,6 +82,30 @@ __device__ __forceinline__ void ls_store4(float* p, int i, int n, bool vec, f32x
         if (i + c < n) p[i + c] = x[c];
 }
 
+struct LatentArgsEx : LatentArgs {
+    const float* r;  // [B, ldr] or NULL
+    int64_t ldr;
+    const float* q_cur;  // [B, ldqc]
+    int64_t ldqc;
+    const float* qa;
+    const float* qb;
+    float* q_next;  // [B, ldqn] or NULL: no accumulator
+    int64_t ldqn;
+    int r_vec, qc_vec, qn_vec;
+};
+
+// q_next[b, k .. k + 3] = fma(qa, q_cur[b, k .. k + 3], qb * a), k a multiple of four; elements at or past K are neither read nor written
+__device__ __forceinline__ void ls_acc(const float* q_cur, bool qc_vec, float* q_next, bool qn_vec, int k, int K, float qa, float qb,
+                                       const f32x4 a) {
+#pragma clang fp contract(off)
+    f32x4 qc = {0.f, 0.f, 0.f, 0.f};
+    if (qa != 0.f) qc = ls_load4(q_cur, k, K, qc_vec);
+    f32x4 qn;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) qn[j] = __builtin_fmaf(qa, qc[j], qb * a[j]);
+    ls_store4(q_next, k, K, qn_vec, qn);
+}
+
 struct LsFrag {
     f32x4 a;
     f32x4 m[4];
@@ -89,8 +124,10 @@ __device__ __forceinline__ void ls_chunk(f32x4 (&acc)[4], const f32x4 a, const f
         for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(m[t][j], a[j], acc[t], 0, 0, 0);
 }
 
-__global__ __launch_bounds__(LS_THREADS) void latent_step_kernel(const LatentArgs g) {
+template <class Args>
+__global__ __launch_bounds__(LS_THREADS) void latent_step_kernel(const Args g) {
 #pragma clang fp contract(off)
+    constexpr bool EX = std::is_same<Args, LatentArgsEx>::value;
     __shared__ f32x4 s_part[LS_WAVES][4][64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, q = lane >> 4;
@@ -108,6 +145,27 @@ __global__ __launch_bounds__(LS_THREADS) void latent_step_kernel(const LatentArg
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+    // the accumulator (EX): this column tile writes the rounds of four chunks own_lo <= c / 4 < own_hi
+    int own_lo = 0, own_hi = 0;
+    float qa = 0.f, qb = 0.f;
+    const float* qcrow = nullptr;
+    float* qnrow = nullptr;
+    bool qc_vec = false, qn_vec = false;
+    if constexpr (EX) {
+        if (g.q_next && b0 + r < g.B) {
+            const int rounds = ((g.K + LS_KC - 1) / LS_KC + LS_WAVES - 1) / LS_WAVES;
+            const int per = (rounds + (int)gridDim.x - 1) / (int)gridDim.x;
+            own_lo = (int)blockIdx.x * per;
+            own_hi = own_lo + per;  // (a round past the last one does not occur below)
+            qa = g.qa[brow];
+            qb = g.qb[brow];
+            qcrow = g.q_cur + (int64_t)brow * g.ldqc;
+            qnrow = g.q_next + (int64_t)brow * g.ldqn;
+            qc_vec = g.qc_vec != 0;
+            qn_vec = g.qn_vec != 0;
+        }
+    }
+
     int c = wave;
     const int nfull = g.ab_vec ? g.K / LS_KC : 0;  // chunks that end inside K and may be read 16 bytes at a time
     if (c < nfull) {
@@ -124,6 +182,12 @@ __global__ __launch_bounds__(LS_THREADS) void latent_step_kernel(const LatentArg
             ls_load(g1, arow, mrow, (c + 3 * LS_WAVES < last ? c + 3 * LS_WAVES : last) * LS_KC + 4 * q);
             ls_chunk(acc, f0.a, f0.m);
             if (c + LS_WAVES < nfull) ls_chunk(acc, f1.a, f1.m);
+            if constexpr (EX) {
+                const int rd = c / LS_WAVES;
+                if (rd >= own_lo && rd < own_hi) ls_acc(qcrow, qc_vec, qnrow, qn_vec, c * LS_KC + 4 * q, g.K, qa, qb, f0.a);
+                if (c + LS_WAVES < nfull && rd + 1 >= own_lo && rd + 1 < own_hi)
+                    ls_acc(qcrow, qc_vec, qnrow, qn_vec, (c + LS_WAVES) * LS_KC + 4 * q, g.K, qa, qb, f1.a);
+            }
             c += 2 * LS_WAVES;
             if (c >= nfull) break;
             f0 = g0;
@@ -139,6 +203,9 @@ __global__ __launch_bounds__(LS_THREADS) void latent_step_kernel(const LatentArg
 #pragma unroll
         for (int t = 0; t < 4; ++t) m[t] = ls_load4(mrow[t], k, g.K, false);
         ls_chunk(acc, a, m);
+        if constexpr (EX) {
+            if (c / LS_WAVES >= own_lo && c / LS_WAVES < own_hi) ls_acc(qcrow, qc_vec, qnrow, qn_vec, k, g.K, qa, qb, a);
+        }
     }
 
 #pragma unroll
@@ -160,12 +227,51 @@ __global__ __launch_bounds__(LS_THREADS) void latent_step_kernel(const LatentArg
     for (int j = 0; j < 4; ++j) p[j] = __builtin_fmaf(c2, pc[j], c1 * s[j]);
     ls_store4(g.p_next + (int64_t)b * g.ldpn, nb, g.N, g.pn_vec != 0, p);
     if (!g.h_next) return;
+    if constexpr (EX) {
+        if (g.r) p += ls_load4(g.r + (int64_t)b * g.ldr, nb, g.N, g.r_vec != 0);
+    }
     if (g.e) p += ls_load4(g.e, nb, g.N, g.e_vec != 0);
     if (g.act == 1) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) p[j] = gd_tanh(p[j]);
     }
     ls_store4(g.h_next + (int64_t)b * g.ldh, nb, g.N, g.h_vec != 0, p);
+}
+
+// the accumulator alone: one thread per four consecutive k of a row
+__global__ __launch_bounds__(256) void latent_acc_kernel(const float* q_cur, int64_t ldqc, const float* qa, const float* A, int64_t lda,
+                                                         const float* qb, int B, int K, float* q_next, int64_t ldqn, int a_vec,
+                                                         int qc_vec, int qn_vec) {
+    const int k4 = (K + 3) / 4;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * k4) return;
+    const int b = (int)(i / k4), k = 4 * (int)(i % k4);
+    const f32x4 a = ls_load4(A + (int64_t)b * lda, k, K, a_vec != 0);
+    ls_acc(q_cur + (int64_t)b * ldqc, qc_vec != 0, q_next + (int64_t)b * ldqn, qn_vec != 0, k, K, qa[b], qb[b], a);
+}
+
+int ls_check(const float* A, int64_t lda, const float* M, int64_t ldm, const float* p_cur, int64_t ldpc,
+             const float* c1, const float* c2, int act, int B, int N, int K, float* p_next, int64_t ldpn, float* h_next, int64_t ldh) {
+    GD_CHECK_SHAPE(B > 0 && N > 0 && K > 0, "latent_step: empty product");
+    GD_CHECK_SHAPE(B <= 65535 * LS_TB, "latent_step: too many rows in one launch");
+    GD_CHECK_ARG(A && M && p_cur && c1 && c2 && p_next, "latent_step: A / M / p_cur / c1 / c2 / p_next missing");
+    GD_CHECK_ARG(act == 0 || act == 1, "latent_step: act must be 0 (none) or 1 (tanh)");
+    GD_CHECK_SHAPE(lda >= K && ldm >= K, "latent_step: lda / ldm below K");
+    GD_CHECK_SHAPE(ldpc >= N && ldpn >= N && (!h_next || ldh >= N), "latent_step: leading dimension of p_cur / p_next / h_next below N");
+    return 0;
+}
+
+void ls_fill(LatentArgs& g, const float* A, int64_t lda, const float* M, int64_t ldm, const float* v, const float* p_cur, int64_t ldpc,
+             const float* c1, const float* c2, const float* e, int act, int B, int N, int K, float* p_next, int64_t ldpn,
+             float* h_next, int64_t ldh) {
+    g.A = A; g.lda = lda; g.M = M; g.ldm = ldm; g.v = v; g.p_cur = p_cur; g.ldpc = ldpc; g.c1 = c1; g.c2 = c2; g.e = e;
+    g.act = act; g.B = B; g.N = N; g.K = K; g.p_next = p_next; g.ldpn = ldpn; g.h_next = h_next; g.ldh = ldh;
+    g.ab_vec = gd_aligned16(A) && gd_aligned16(M) && (lda % 4) == 0 && (ldm % 4) == 0;
+    g.v_vec = v && gd_aligned16(v);
+    g.e_vec = e && gd_aligned16(e);
+    g.pc_vec = gd_aligned16(p_cur) && (ldpc % 4) == 0;
+    g.pn_vec = gd_aligned16(p_next) && (ldpn % 4) == 0;
+    g.h_vec = h_next && gd_aligned16(h_next) && (ldh % 4) == 0;
 }
 
 }  // namespace
@@ -181,23 +287,46 @@ int gdmcf_latent_step_f32(const float* A, int64_t lda, const float* M, int64_t l
                           int64_t ldpc, const float* c1, const float* c2, const float* e, int act, int B, int N, int K,
                           float* p_next, int64_t ldpn, float* h_next, int64_t ldh, void* ws, size_t ws_bytes, void* stream) {
     (void)ws; (void)ws_bytes;
-    GD_CHECK_SHAPE(B > 0 && N > 0 && K > 0, "latent_step: empty product");
-    GD_CHECK_SHAPE(B <= 65535 * LS_TB, "latent_step: too many rows in one launch");
-    GD_CHECK_ARG(A && M && p_cur && c1 && c2 && p_next, "latent_step: A / M / p_cur / c1 / c2 / p_next missing");
-    GD_CHECK_ARG(act == 0 || act == 1, "latent_step: act must be 0 (none) or 1 (tanh)");
-    GD_CHECK_SHAPE(lda >= K && ldm >= K, "latent_step: lda / ldm below K");
-    GD_CHECK_SHAPE(ldpc >= N && ldpn >= N && (!h_next || ldh >= N), "latent_step: leading dimension of p_cur / p_next / h_next below N");
+    if (int rc = ls_check(A, lda, M, ldm, p_cur, ldpc, c1, c2, act, B, N, K, p_next, ldpn, h_next, ldh)) return rc;
     LatentArgs g;
-    g.A = A; g.lda = lda; g.M = M; g.ldm = ldm; g.v = v; g.p_cur = p_cur; g.ldpc = ldpc; g.c1 = c1; g.c2 = c2; g.e = e;
-    g.act = act; g.B = B; g.N = N; g.K = K; g.p_next = p_next; g.ldpn = ldpn; g.h_next = h_next; g.ldh = ldh;
-    g.ab_vec = gd_aligned16(A) && gd_aligned16(M) && (lda % 4) == 0 && (ldm % 4) == 0;
-    g.v_vec = v && gd_aligned16(v);
-    g.e_vec = e && gd_aligned16(e);
-    g.pc_vec = gd_aligned16(p_cur) && (ldpc % 4) == 0;
-    g.pn_vec = gd_aligned16(p_next) && (ldpn % 4) == 0;
-    g.h_vec = h_next && gd_aligned16(h_next) && (ldh % 4) == 0;
-    hipLaunchKernelGGL(latent_step_kernel, dim3(gd_cdiv(N, LS_TN), gd_cdiv(B, LS_TB)), dim3(LS_THREADS), 0, (hipStream_t)stream, g);
+    ls_fill(g, A, lda, M, ldm, v, p_cur, ldpc, c1, c2, e, act, B, N, K, p_next, ldpn, h_next, ldh);
+    hipLaunchKernelGGL(latent_step_kernel<LatentArgs>, dim3(gd_cdiv(N, LS_TN), gd_cdiv(B, LS_TB)), dim3(LS_THREADS), 0, (hipStream_t)stream, g);
     return gd_launch_status("latent_step");
+}
+
+int gdmcf_latent_step_ex_f32(const float* A, int64_t lda, const float* M, int64_t ldm, const float* v, const float* p_cur,
+                             int64_t ldpc, const float* c1, const float* c2, const float* r, int64_t ldr, const float* e, int act,
+                             int B, int N, int K, float* p_next, int64_t ldpn, float* h_next, int64_t ldh, const float* q_cur,
+                             int64_t ldqc, const float* qa, const float* qb, float* q_next, int64_t ldqn, void* ws, size_t ws_bytes,
+                             void* stream) {
+    (void)ws; (void)ws_bytes;
+    if (int rc = ls_check(A, lda, M, ldm, p_cur, ldpc, c1, c2, act, B, N, K, p_next, ldpn, h_next, ldh)) return rc;
+    GD_CHECK_SHAPE(!r || ldr >= N, "latent_step_ex: ldr below N");
+    GD_CHECK_ARG(!q_next || (q_cur && qa && qb), "latent_step_ex: q_next without q_cur / qa / qb");
+    GD_CHECK_SHAPE(!q_next || (ldqc >= K && ldqn >= K), "latent_step_ex: ldq below K");
+    GD_CHECK_ARG(!q_next || q_next != A, "latent_step_ex: q_next must not be A (other column tiles still read it)");
+    LatentArgsEx g;
+    ls_fill(g, A, lda, M, ldm, v, p_cur, ldpc, c1, c2, e, act, B, N, K, p_next, ldpn, h_next, ldh);
+    g.r = r; g.ldr = ldr; g.q_cur = q_cur; g.ldqc = ldqc; g.qa = qa; g.qb = qb; g.q_next = q_next; g.ldqn = ldqn;
+    g.r_vec = r && gd_aligned16(r) && (ldr % 4) == 0;
+    g.qc_vec = q_next && gd_aligned16(q_cur) && (ldqc % 4) == 0;
+    g.qn_vec = q_next && gd_aligned16(q_next) && (ldqn % 4) == 0;
+    hipLaunchKernelGGL(latent_step_kernel<LatentArgsEx>, dim3(gd_cdiv(N, LS_TN), gd_cdiv(B, LS_TB)), dim3(LS_THREADS), 0, (hipStream_t)stream, g);
+    return gd_launch_status("latent_step_ex");
+}
+
+int gdmcf_latent_acc_f32(const float* q_cur, int64_t ldqc, const float* qa, const float* A, int64_t lda, const float* qb, int B, int K,
+                         float* q_next, int64_t ldqn, void* stream) {
+    GD_CHECK_SHAPE(B > 0 && K > 0, "latent_acc: empty update");
+    GD_CHECK_ARG(q_cur && qa && A && qb && q_next, "latent_acc: q_cur / qa / A / qb / q_next missing");
+    GD_CHECK_SHAPE(lda >= K && ldqc >= K && ldqn >= K, "latent_acc: lda / ldq below K");
+    GD_CHECK_ARG(q_next != A, "latent_acc: q_next must not be A");
+    const int64_t n = (int64_t)B * ((K + 3) / 4);
+    GD_CHECK_SHAPE((n + 255) / 256 <= 0x7fffffff, "latent_acc: too many elements in one launch");
+    hipLaunchKernelGGL(latent_acc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q_cur, ldqc, qa, A, lda, qb,
+                       B, K, q_next, ldqn, gd_aligned16(A) && (lda % 4) == 0, gd_aligned16(q_cur) && (ldqc % 4) == 0,
+                       gd_aligned16(q_next) && (ldqn % 4) == 0);
+    return gd_launch_status("latent_acc");
 }
 
 }  // extern "C"

@@ -55,10 +55,11 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
     mask_his: CSR of interactions to exclude from the ranking.  sparse=True: p_sample receives each batch as a
     data_utils.CsrBatch (never densified where the reverse loop takes sparse rows; densified inside p_sample otherwise).
     latent=True: p_sample(latent=True) -- the reverse loop in the first hidden layer's space where
-    GaussianDiffusion._latent_reverse_ok holds; composes with sparse=True.
+    GaussianDiffusion._latent_reverse_ok holds; composes with sparse=True.  latent="extended" is passed through as it is
+    (the EPSILON target and DNNCat too), also to gdmcf_amd.recommend with recommend=True.
     recommend=True: each batch's list comes from gdmcf_amd.recommend with mask_his as a DeviceCSR -- uploaded once
-    per call, or passed through when it already is one -- so no batch slices a matrix on the host; `sparse` and `latent` are
-    then ignored (recommend picks its own route, `diffusion.last_recommend_route`)."""
+    per call, or passed through when it already is one -- so no batch slices a matrix on the host; `sparse` is then ignored and
+    of `latent` only the value "extended" matters (recommend picks its own route, `diffusion.last_recommend_route`)."""
     model.eval()
     n = mask_his.shape[0]
     predict_items = []
@@ -67,14 +68,15 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
         from .recommend import recommend as recommend_fn
         mask = mask_his if isinstance(mask_his, DeviceCSR) else DeviceCSR(mask_his, device)
         lists = recommend_fn(diffusion, model, dcsr, np.arange(n), topN[-1], mask=mask, sampling_steps=sampling_steps,
-                             sampling_noise=sampling_noise, batch_size=batch_size)  # (the same batches, made inside)
+                             sampling_noise=sampling_noise, batch_size=batch_size,  # (the same batches, made inside)
+                             **(dict(latent="extended") if isinstance(latent, str) and latent == "extended" else {}))
         return evaluate_utils.computeTopNAccuracy_device(data_te, lists, topN)
     for lo in range(0, n, batch_size):
         rows = np.arange(lo, min(lo + batch_size, n))
         batch = dcsr.batch(torch.from_numpy(rows)) if sparse else dcsr.rows(torch.from_numpy(rows))
         kw = dict(index=torch.from_numpy(rows)) if getattr(diffusion, "indexIn", False) else {}
         if latent:
-            kw["latent"] = True
+            kw["latent"] = "extended" if isinstance(latent, str) and latent == "extended" else True
         prediction = diffusion.p_sample(model, batch, sampling_steps, sampling_noise, **kw)
         indptr, cols = evaluate_utils.csr_rows_to_device(mask_his, rows, device)
         predict_items.append(masked_topk(prediction, topN[-1], indptr, cols))

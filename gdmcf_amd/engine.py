@@ -369,10 +369,12 @@ class DenoiserEngine(EngineBase):
     # ------------------------------------------------------------------------------------------
     @with_precision
     def p_sample_loop(self, x_start, steps, T, tabs32, eps_mode, sampling_noise, noise0=None, step_noise=None,
-                      capture=None, draw_noise=None, latent=False, _stop=False):
+                      capture=None, draw_noise=None, latent=False, _stop=False, eps=None):
         """latent: carry the loop in the first hidden layer's space (_latent_loop; the caller has checked
         GaussianDiffusion._latent_reverse_ok).  _stop (with latent; gdmcf_amd.recommend): end the loop at its last operands and
-        return (A, second, K, b_out) instead of x_0.
+        return (A, second, K, b_out) instead of x_0.  eps (with latent and eps_mode; p_sample(latent="extended")): the
+        engine_core.EpsTables of the schedule -- the EPSILON target's latent loop; with _stop it returns
+        (-Q^, second, K, -b_out, G, D), x_0 = G x_T + D ((-Q^) second^T + (-b_out)).
         tabs32: dict of float32 device tables [T] (sqrt_ab, sqrt_1mab, c1, c2, r1, r2, sigma).  draw_noise(like) -> [B, I]
         float32 N(0,1): the reverse loop's th.randn_like(x_t) (reference :210-217); default: gdmcf_randn_f32 on the engine's
         Philox seed (stream 7, one offset per draw).
@@ -398,10 +400,10 @@ class DenoiserEngine(EngineBase):
         st = _lib.stream_ptr()
         self.version += 1
         if latent:
-            if eps_mode or sampling_noise or capture is not None or m.norm or self.gemm_dtype != "f32":
+            if (eps_mode and eps is None) or sampling_noise or capture is not None or m.norm or self.gemm_dtype != "f32":
                 raise RuntimeError("gdmcf_amd: the latent reverse loop takes the x0 target without sampling noise, capture or "
                                    "F.normalize, in float32 products (GaussianDiffusion._latent_reverse_ok)")
-            return self._latent_loop(bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=_stop)
+            return self._latent_loop(bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=_stop, eps=eps if eps_mode else None)
         if bufs.xin2 is None:
             bufs.xin2 = torch.zeros_like(bufs.xin)
         if self.gemm_dtype == "bf16" and getattr(bufs, "sh_xin2", None) is None:
@@ -481,7 +483,7 @@ class DenoiserEngine(EngineBase):
         del keep
         return out
 
-    def _latent_loop(self, bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=False):
+    def _latent_loop(self, bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=False, eps=None):
         """The reverse loop in the first hidden layer's space.  With the x0 target and no sampling noise the loop is linear in x_t
         between two hidden activations, x_{t-1} = c1[t] (W_out a_t + b_out) + c2[t] x_t, so p_t = W1x x_t obeys
             p_{t-1} = c1[t] (M a_t + v) + c2[t] p_t,    M = W1x W_out,  v = W1x b_out,    h_{t-1} = tanh(p_{t-1} + e_{t-1})
@@ -490,7 +492,12 @@ class DenoiserEngine(EngineBase):
         step, x_0 = c1[0] (W_out a_0 + b_out) -- posterior_mean_coef2[0] is exactly 0.  x_T is built as in the item-space loop: same
         builder, same Philox offsets.
         stop: return (A, second, K, b_out), the operands of the last product x_0 = c1[0] (A second^T + b_out), without running it;
-        on CSR rows no builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had."""
+        on CSR rows no builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had.
+        eps (engine_core.EpsTables): the EPSILON target.  The step is x_{t-1} = g_t x_t - d_t (W_out a_t + b_out), the same kernel
+        with c1 := -d_t, c2 := g_t (gdmcf_latent_step_ex_f32, which also keeps Q <- g_t Q + d_t a_t); the last step's accumulation
+        is gdmcf_latent_acc_f32 with the factor 1 / D folded in, and x_0 = G x_T - D (W_out Q^ + b_out) is the posterior epilogue in
+        its eps form (r1 = G, r2 = D, c1 = 1, c2 = 0) on the dense x_T.  stop: (-Q^, second, K, -b_out, G, D), the operands of the
+        product gdmcf_amd.recommend ranks (scale D > 0) and the per-row scalars."""
         lib, st, I = self.lib, _lib.stream_ptr(), self.I
         B, dev = x_start.shape[0], x_start.device
         (w1, b1, act1), (w, bias, _) = layers[0], layers[-1]
@@ -504,6 +511,12 @@ class DenoiserEngine(EngineBase):
             bufs.lat_tabs = {k: tabs32[k][:T, None].expand(T, B).contiguous() for k in ("c1", "c2")}
             bufs.lat_tabs_key = key
         c1, c2 = bufs.lat_tabs["c1"], bufs.lat_tabs["c2"]
+        if eps is not None:
+            et = eps.on(dev, B)
+            c1, c2 = et["neg_d"], et["g"]
+            if getattr(bufs, "lat_q", None) is None:
+                bufs.lat_q = torch.zeros(B, _ceil64(K), dtype=torch.float32, device=dev)
+            Q = bufs.lat_q
         if getattr(bufs, "lat_p", None) is None:
             bufs.lat_p = torch.zeros(B, _ceil64(h1), dtype=torch.float32, device=dev)
             bufs.lat_h = torch.zeros(B, _ceil64(h1), dtype=torch.float32, device=dev)
@@ -531,6 +544,15 @@ class DenoiserEngine(EngineBase):
                 out = bufs.acts[li]
                 core.linear_fwd(lib, bufs, A, wl, bl, al, B, wl.shape[0], wl.shape[1], out, st)
                 A = out
+            if i == 0 and eps is not None:
+                if stop:  # the sign goes into the last accumulation: -Q^ beside the cached -b_out
+                    core.latent_acc(lib, Q, et["qa0_neg"], A, et["qb0_neg"], B, K, Q, st)
+                    x0 = (Q, w, K, ops.neg_b, et["G"], et["D"])
+                    break
+                core.latent_acc(lib, Q, et["qa"][0], A, et["qb"][0], B, K, Q, st)
+                x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
+                core.posterior_fwd(lib, Q, w, bias, bufs.xin, et["one"], et["zero"], et["G"], et["D"], None, None, B, I, K, x0, None, st)
+                break
             if i == 0:
                 if stop:
                     x0 = (A, w, K, bias)
@@ -538,7 +560,11 @@ class DenoiserEngine(EngineBase):
                 x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
                 core.posterior_fwd(lib, A, w, bias, bufs.xin, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
                 break
-            core.latent_step(lib, A, ops.M, ops.v, p, c1[i], c2[i], ops.e[i - 1], act1, B, h1, K, p, hnxt, st)
+            if eps is not None:
+                core.latent_step_ex(lib, A, ops.M, ops.v, p, c1[i], c2[i], None, ops.e[i - 1], act1, B, h1, K, p, hnxt,
+                                    (Q, et["qa"][i], et["qb"][i], Q), st)
+            else:
+                core.latent_step(lib, A, ops.M, ops.v, p, c1[i], c2[i], ops.e[i - 1], act1, B, h1, K, p, hnxt, st)
             hcur, hnxt = hnxt, hcur
         self._saved = None
         del keep

@@ -183,6 +183,60 @@ def latent_step(lib, A, M, v, p_cur, c1, c2, e, act, B, N, K, p_next, h_next, st
                                          B, N, K, pn, ldpn, h, ldh, None, 0, st))
 
 
+def latent_step_ex(lib, A, M, v, p_cur, c1, c2, r, e, act, B, N, K, p_next, h_next, acc, st):
+    """gdmcf_latent_step_ex_f32: latent_step with h_next = act((p_next + r) + e) for a row addend r [B, .] (or None) and, with
+    acc = (q_cur, qa, qb, q_next), q_next = qa . q_cur + qb . A in the same launch (acc None: no accumulator)."""
+    (a, lda), (m, ldm), (pc, ldpc), (pn, ldpn), (h, ldh), (rp, ldr) = _pl(A), _pl(M), _pl(p_cur), _pl(p_next), _pl(h_next), _pl(r)
+    (qc, ldqc), (qn, ldqn) = (_pl(acc[0]), _pl(acc[3])) if acc is not None else ((None, 0), (None, 0))
+    qa, qb = (acc[1].data_ptr(), acc[2].data_ptr()) if acc is not None else (None, None)
+    _lib.check(lib.gdmcf_latent_step_ex_f32(a, lda, m, ldm, _lib.ptr(v), pc, ldpc, c1.data_ptr(), c2.data_ptr(), rp, ldr, _lib.ptr(e),
+                                            act, B, N, K, pn, ldpn, h, ldh, qc, ldqc, qa, qb, qn, ldqn, None, 0, st))
+
+
+def latent_acc(lib, q_cur, qa, A, qb, B, K, q_next, st):
+    """gdmcf_latent_acc_f32: q_next = qa . q_cur + qb . A, the accumulator of latent_step_ex as a launch of its own."""
+    (qc, ldqc), (a, lda), (qn, ldqn) = _pl(q_cur), _pl(A), _pl(q_next)
+    _lib.check(lib.gdmcf_latent_acc_f32(qc, ldqc, qa.data_ptr(), a, lda, qb.data_ptr(), B, K, qn, ldqn, st))
+
+
+class EpsTables:
+    """Host side of the EPSILON target's latent loop.  The item-space step is x_{t-1} = g_t x_t - d_t (second a_t + b_out)
+    with g_t = c1[t] r1[t] + c2[t], d_t = c1[t] r2[t]; unrolled, x_0 = G x_T - D (second Q^ + b_out) with G = prod g_t,
+    D <- g_t D + d_t and Q^ = Q / D, Q <- g_t Q + d_t a_t.  Everything here is formed in float64 from the host's schedule tables
+    and rounded once: no device read.  g, d: float32 [T]; qa, qb: float32 [T], the accumulator's coefficients (qa[T-1] = 0: Q_T
+    is 0 and is not read; step 0's carry the factor 1 / D); G, D: floats; ok: all finite and D > 0."""
+
+    def __init__(self, c1, c2, r1, r2, T):
+        import numpy as np
+        c1, c2, r1, r2 = (np.asarray(t, dtype=np.float64)[:T] for t in (c1, c2, r1, r2))
+        g, d = c1 * r1 + c2, c1 * r2
+        G, D = 1.0, 0.0
+        with np.errstate(all="ignore"):
+            for t in range(T - 1, -1, -1):
+                G, D = g[t] * G, g[t] * D + d[t]
+            qa, qb = g.copy(), d.copy()
+            qa[T - 1] = 0.0
+            qa[0], qb[0] = qa[0] / D, qb[0] / D
+        self.g, self.d, self.qa, self.qb = (t.astype(np.float32) for t in (g, d, qa, qb))
+        self.G, self.D = float(np.float32(G)), float(np.float32(D))
+        self.ok = bool(all(np.isfinite(t).all() for t in (self.g, self.d, self.qa, self.qb)) and np.isfinite(self.G)
+                       and np.isfinite(self.D) and self.D > 0)
+        self._dev = {}  # (device, B) -> the device tables: see on()
+
+    def on(self, device, B):
+        """The device tables of one batch size, made once: neg_d, g, qa, qb [T, B]; G, D, qa0_neg, qb0_neg [B]; negative d because
+        the step kernel forms c1 (M a + v) + c2 p with c1 := -d, c2 := g."""
+        rec, key = self._dev, (str(device), int(B))
+        if key not in rec:
+            def tab(a):
+                return torch.from_numpy(a).to(device)[:, None].expand(len(a), B).contiguous()
+            f = dict(dtype=torch.float32, device=device)
+            rec[key] = dict(neg_d=tab(-self.d), g=tab(self.g), qa=tab(self.qa), qb=tab(self.qb), G=torch.full((B,), self.G, **f),
+                            D=torch.full((B,), self.D, **f), one=torch.ones(B, **f), zero=torch.zeros(B, **f))
+            rec[key]["qa0_neg"], rec[key]["qb0_neg"] = -rec[key]["qa"][0], -rec[key]["qb"][0]  # the last step of a stopped loop: -Q^
+        return rec[key]
+
+
 def linear_bwd_input(lib, bufs, dz, W, rs, A_prev, act_prev, B, N, K, d_prev, st):
     """d_prev = ((rs .) dz @ W) * act_prev'(A_prev)"""
     (z, ldz), (w, ldw), (a, lda), (d, ldd) = _pl(dz), _pl(W), _pl(A_prev), _pl(d_prev)
@@ -384,9 +438,11 @@ class EngineBase:
           M [h, K] = W1x . second     W1x = w1[:, :I] (read in place, its own leading dimension); second [I, K] = the output layer's
                                       weight (or an embedding backbone's normalised item vectors): gdmcf_linear_bwd_input_f32
           v [h]    = W1x . b_out      (None without b_out): gdmcf_linear_fwd_f32 on the one row b_out
+          S [h]    = W1x . 1          the same product on a row of ones (DNNCat from binary CSR rows)
+          neg_b [I] = -b_out          (None without b_out) for the eps ranking of gdmcf_amd.recommend
           e [T, h] = W1e emb(t) + b1  the first layer's time columns and bias for every timestep (_emb_table)
           tabs                        the same table for every (weight, bias, item columns) of `tables`
-        Returns a _Bufs with M, v, e, tabs.  One item-wide product per weight version; an evaluation pass pays it once."""
+        Returns a _Bufs with M, v, S, neg_b, e, tabs.  One item-wide product per weight version; an evaluation pass pays it once."""
         lib, st = self.lib, _lib.stream_ptr()
         key = tuple((t.data_ptr(), t._version, str(t.device)) for t in entering) + (int(T), int(K), b_out is None)
         if self._latent is not None and self._latent[0] == key:
@@ -399,10 +455,16 @@ class EngineBase:
         w1x = (w1.data_ptr(), w1.stride(0))
         o.M = torch.zeros(h, _ceil64(K), **f32)
         linear_bwd_input(lib, ws, w1x, second, None, None, 0, h, I, K, o.M, st)
-        o.v = None
+        o.v = o.neg_b = None
         if b_out is not None:
             o.v = torch.zeros(h, **f32)
             linear_fwd(lib, ws, (b_out.data_ptr(), I), w1x, None, 0, 1, h, I, (o.v.data_ptr(), h), st)
+            o.neg_b = -b_out.detach()  # the eps ranking of gdmcf_amd.recommend: second (-Q^) + (-b_out), scale D
+        # S [h] = W1x . 1 (DNNCat on binary CSR rows: r = (w1 + c) S + (w2 - w1) p_T)
+        ones = torch.ones(I, **f32)
+        o.S = torch.zeros(h, **f32)
+        linear_fwd(lib, ws, (ones.data_ptr(), I), w1x, None, 0, 1, h, I, (o.S.data_ptr(), h), st)
+        o.keep_S = ones
         o.e, o.keep = self._emb_table(w1, bias1, I, T, st)
         o.tabs = [self._emb_table(w, b, cols, T, st) for w, b, cols in tables]
         self._latent = (key, o)

@@ -295,22 +295,55 @@ class GaussianDiffusion(nn.Module):
             rec = self._latent_tabs_rec = (c1, c2, ok)
         return rec[2]
 
-    def _latent_reverse_ok(self, model, sampling_noise=False, capture=None):
+    @staticmethod
+    def _latent_backbones_extended():
+        """_latent_backbones plus DNNCat (exact type): what p_sample(latent="extended") carries in the hidden space."""
+        from .cat import DNNCat
+        return GaussianDiffusion._latent_backbones() + (DNNCat,)
+
+    def _eps_tables(self):
+        """engine_core.EpsTables of this schedule (the EPSILON target's latent loop): g_t, d_t, G, D from the host's float64
+        tables (gdmcf_schedule_build; no device read) with the four inputs rounded to float32 first, as the item-space route
+        reads them; once per table set."""
+        c1 = self._t32.get("c1")
+        rec = getattr(self, "_eps_tabs_rec", None)
+        if rec is None or rec[0] is not c1:
+            from .engine_core import EpsTables
+            tabs = _lib.schedule_tables(_SCHEDULE_KIND[self.noise_schedule], self.noise_scale, self.noise_min, self.noise_max,
+                                        self.steps, self.beta_fixed)
+            row = lambda name: tabs[_lib.TABLE_NAMES.index(name)].astype("float32")
+            et = EpsTables(row("posterior_mean_coef1"), row("posterior_mean_coef2"), row("sqrt_recip_alphas_cumprod"),
+                           row("sqrt_recipm1_alphas_cumprod"), self.steps)
+            rec = self._eps_tabs_rec = (c1, et)
+        return rec[1]
+
+    def _latent_reverse_ok(self, model, sampling_noise=False, capture=None, extended=False):
         """Whether p_sample(latent=True) may carry the reverse loop in the first hidden layer's space: between two
         hidden activations the loop must be linear in x_t -- x0 target, no sampling noise, no F.normalize, no dropout -- nothing may
         ask for the per-step x_t (capture), the products are float32, the last step needs no x_1 (c2[0] == 0), and the backbone's
-        engine has the loop (exact types).  Anything else takes the item-space route, to the bit."""
-        return (self.mean_type == ModelMeanType.START_X and self.noise_scale != 0.0 and not sampling_noise and capture is None
-                and not model.norm and (not model.training or model.drop.p == 0)
-                and getattr(model, "gemm_dtype", "f32") == "f32" and type(model) in self._latent_backbones()
-                and self._latent_tables_ok())
+        engine has the loop (exact types).  Anything else takes the item-space route, to the bit.
+        extended (p_sample(latent="extended")): the same predicate with the EPSILON target allowed -- its tables must give finite
+        g, d, G, D and D > 0 (_eps_tables) instead of c2[0] == 0 -- and DNNCat among the backbones."""
+        common = (self.noise_scale != 0.0 and not sampling_noise and capture is None
+                  and not model.norm and (not model.training or model.drop.p == 0)
+                  and getattr(model, "gemm_dtype", "f32") == "f32")
+        if not extended:
+            return (self.mean_type == ModelMeanType.START_X and common and type(model) in self._latent_backbones()
+                    and self._latent_tables_ok())
+        if not (common and type(model) in self._latent_backbones_extended() and "c1" in self._t32):
+            return False
+        if self.mean_type == ModelMeanType.START_X:
+            return self._latent_tables_ok()
+        return self.mean_type == ModelMeanType.EPSILON and self._eps_tables().ok
 
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,
                  capture=None, latent=False):
         """x_start: dense [B, n_items] rows, or a data_utils.CsrBatch -- kept sparse where _sparse_reverse_ok holds (the first
         reverse step's first hidden layer is then a gather of the rows' weight rows), densified here otherwise.
         latent=True: where _latent_reverse_ok holds, the loop runs in the first hidden layer's space (two item-wide products per
-        call instead of two per step; same [B, n_items] result up to float32 rounding); `last_reverse_route` says which route ran."""
+        call instead of two per step; same [B, n_items] result up to float32 rounding); `last_reverse_route` says which route ran.
+        latent="extended": the same with _latent_reverse_ok(extended=True) -- the EPSILON target too (and, in the discrete class,
+        DNNCat); everything latent=True covers runs exactly as under latent=True."""
         assert steps <= self.steps, "Too much steps in inference."
         _lib.require_gpu(x_start, "x_start")
         if not isinstance(model, DNN):
@@ -318,8 +351,10 @@ class GaussianDiffusion(nn.Module):
         from .data_utils import CsrBatch
         if isinstance(x_start, CsrBatch) and not self._sparse_reverse_ok(model, x_start, steps):
             x_start = x_start.dense()
-        latent = bool(latent) and self._latent_reverse_ok(model, sampling_noise, capture)
+        extended = isinstance(latent, str) and latent == "extended"
+        latent = bool(latent) and self._latent_reverse_ok(model, sampling_noise, capture, extended=extended)
         self.last_reverse_route = "latent" if latent else "item"
+        eps_mode = self.mean_type == ModelMeanType.EPSILON
         if self.noise_scale == 0.0:
             x_t = x_start
             with torch.no_grad():
@@ -328,11 +363,12 @@ class GaussianDiffusion(nn.Module):
                     x_t = model(x_t, t)
             return x_t
         with torch.no_grad():
-            return model.engine.p_sample_loop(x_start, steps, self.steps, self._t32,
-                                              self.mean_type == ModelMeanType.EPSILON, bool(sampling_noise),
+            kw = dict(latent=True) if latent else {}
+            if latent and eps_mode:
+                kw["eps"] = self._eps_tables()
+            return model.engine.p_sample_loop(x_start, steps, self.steps, self._t32, eps_mode, bool(sampling_noise),
                                               noise0=noise0, step_noise=step_noise, capture=capture,
-                                              draw_noise=lambda like: self._draw_noise(like, stream_id=7),
-                                              **(dict(latent=True) if latent else {}))
+                                              draw_noise=lambda like: self._draw_noise(like, stream_id=7), **kw)
 
 
 class GaussianDiffusionDiscrete(GaussianDiffusion):
@@ -447,18 +483,25 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         assert steps <= self.steps, "Too much steps in inference."
         _lib.require_gpu(x_start, "x_start")
         model = self._onehot_model(model)
-        latent = bool(latent) and self._latent_reverse_ok(model, sampling_noise, capture)
+        extended = isinstance(latent, str) and latent == "extended"
+        latent = bool(latent) and self._latent_reverse_ok(model, sampling_noise, capture, extended=extended)
         self.last_reverse_route = "latent" if latent else "item"
+        from .cat import DNNCat
         from .data_utils import CsrBatch
         csr_batch = None
+        cat_csr = False  # DNNCat keeps CSR rows on the latent route only (its item-space loop takes dense rows)
         if isinstance(x_start, CsrBatch):
             if self._sparse_reverse_ok(model, x_start, steps):
                 csr_batch = x_start
+            elif latent and type(model) is DNNCat and steps == 0 and x_start.csr.values is None:
+                csr_batch, cat_csr = x_start, True
             else:
                 x_start = x_start.dense()
         B, dev = x_start.shape[0], x_start.device
         with torch.no_grad():
-            if csr_batch is not None:
+            if cat_csr:
+                x0, x_tU, keep, x_t = None, None, None, csr_batch  # xU0 = 1 - x, xU1 = x: CatEngine.latent_loop needs no image
+            elif csr_batch is not None:
                 # rows left sparse (steps == 0): neither the [B, 2I] image nor the second branch's input is built -- a handle
                 # carries that branch's step-independent pre-activation, gathered once; the first step's x_t is the rows themselves
                 x0 = None
@@ -497,8 +540,9 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
                         self._graph_step(graph, torch.full((B,), i, dtype=torch.int64, device=dev), degp,
                                          None if graph_sampled is None else graph_sampled[n],
                                          None if graph_pick is None else graph_pick[n])
+                kw = dict(eps=self._eps_tables()) if eps_mode else {}
                 x_0 = model.engine.latent_loop(x_t, x_tU, self.steps, tabs["c1"], tabs["c2"],
-                                               index=index if self.indexIn else None, before_step=before_step)
+                                               index=index if self.indexIn else None, before_step=before_step, **kw)
                 del keep
                 self.last_graph = graph
                 return x_0

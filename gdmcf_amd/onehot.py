@@ -444,7 +444,7 @@ class OneHotEngine(EngineBase):
         bufs.hcat = t
 
     @with_precision
-    def latent_loop(self, x_T, x_U, T, c1, c2, index=None, before_step=None, _stop=False):
+    def latent_loop(self, x_T, x_U, T, c1, c2, index=None, before_step=None, _stop=False, eps=None):
         """The whole reverse loop with x_t carried as p_t = W1x x_t, the first layer of branch 1 without its time columns
         (DenoiserEngine._latent_loop has the algebra): per step one gdmcf_latent_step_f32 with A = the activation behind
         [h | h_U] that feeds the last product and M = W1x . W_out (an embedding backbone: W1x . V^), plus the small layers.
@@ -455,7 +455,10 @@ class OneHotEngine(EngineBase):
         x_T: dense [B, I] rows or a data_utils.CsrBatch of binary rows; x_U: the [B, 2I] image or a SparseXU; c1, c2: [T, B]
         tables; before_step(n, i): called ahead of step n (timestep i), e.g. the degree-guided graph update.
         _stop (gdmcf_amd.recommend): return (A, second, K, b_out), the operands of the last product, without running it; on CSR
-        rows no builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had."""
+        rows no builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had.
+        eps (engine_core.EpsTables; p_sample(latent="extended")): the EPSILON target, as in DenoiserEngine._latent_loop -- c1, c2
+        are ignored for the tables (-d, g), the step kernel also keeps Q, and x_0 = G x_T - D (second Q^ + b_out) comes from the
+        posterior epilogue in its eps form on the dense x_T; with _stop the loop returns (-Q^, second, K, -b_out, G, D)."""
         from .data_utils import CsrBatch
         lib, st, I = self.lib, _lib.stream_ptr(), self.I
         B, dev = x_T.shape[0], x_T.device
@@ -481,7 +484,13 @@ class OneHotEngine(EngineBase):
             bufs.lat_hcat = torch.zeros_like(bufs.hcat)
             bufs.lat_P2 = torch.zeros(B, _ceil64(hf2), **f32)
         p = bufs.lat_p
-        # p_T and the x_t operand of the last product (c2[0] == 0: it only has to be finite)
+        if eps is not None:
+            et = eps.on(dev, B)
+            c1, c2 = et["neg_d"], et["g"]
+            if getattr(bufs, "lat_q", None) is None:
+                bufs.lat_q = torch.zeros(B, _ceil64(K), dtype=torch.float32, device=dev)
+            Q = bufs.lat_q
+        # p_T and the x_t operand of the last product (x0 target: c2[0] == 0, it only has to be finite; eps: it carries G x_T)
         if isinstance(x_T, CsrBatch) and _stop:
             self.offset += 1  # (where the builder would have drawn)
             keep = xdense = None
@@ -528,11 +537,23 @@ class OneHotEngine(EngineBase):
                 core.gather_fwd(lib, P2, None, None, None, I, None, None, 0, e2[i], act2, B, hf2, o2, st)
                 self._chain_forward(bufs, br2[1:], bufs.acts2[1:], o2, B, hcat2)
                 A = self._latent_A(bufs, out, B, index)
-                if i == 0 and _stop:
+                if i == 0 and eps is not None:
+                    if _stop:  # the sign goes into the last accumulation: -Q^ beside the cached -b_out
+                        core.latent_acc(lib, Q, et["qa0_neg"], A, et["qb0_neg"], B, K, Q, st)
+                        x0 = (Q, second, K, ops.neg_b, et["G"], et["D"])
+                    else:
+                        core.latent_acc(lib, Q, et["qa"][0], A, et["qb"][0], B, K, Q, st)
+                        x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
+                        core.posterior_fwd(lib, Q, second, b_out, xdense, et["one"], et["zero"], et["G"], et["D"], None, None, B, I, K,
+                                           x0, None, st)
+                elif i == 0 and _stop:
                     x0 = (A, second, K, b_out)
                 elif i == 0:
                     x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
                     core.posterior_fwd(lib, A, second, b_out, xdense, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
+                elif eps is not None:
+                    core.latent_step_ex(lib, A, ops.M, ops.v, p, c1[i], c2[i], None, ops.e[i - 1], act1, B, hf1, K, p, first(nxt),
+                                        (Q, et["qa"][i], et["qb"][i], Q), st)
                 else:
                     core.latent_step(lib, A, ops.M, ops.v, p, c1[i], c2[i], ops.e[i - 1], act1, B, hf1, K, p, first(nxt), st)
         finally:

@@ -25,17 +25,32 @@ def _c1_0_positive(diffusion):
     return rec[1]
 
 
-def route_of(diffusion, model, rows, sampling_steps=0, sampling_noise=False):
+def route_of(diffusion, model, rows, sampling_steps=0, sampling_noise=False, extended=False, masks=None):
     """Which route `recommend` takes for this call:
       "latent-csr"  GaussianDiffusion._latent_reverse_ok holds (x0 target, no sampling noise, no F.normalize, no active dropout,
                     float32 products, DNN / DNNOneHot / DNNOneHotEmbedding / DNNOneHotEmbeddingGCN), sampling_steps == 0 and every
                     value of `rows` is 1: gathered first layers, latent steps, one item-wide product, top-k on the raw scores
       "latent"      _latent_reverse_ok holds but x_T is not the binary rows (sampling_steps > 0, values other than 1): the same,
                     from dense rows
-      "item"        everything else: p_sample as driver.evaluate calls it, then the top-k."""
-    if not (diffusion._latent_reverse_ok(model, sampling_noise, None) and _c1_0_positive(diffusion)):
+      "item"        everything else: p_sample as driver.evaluate calls it, then the top-k.
+    extended (recommend(latent="extended")): _latent_reverse_ok(extended=True) decides, so DNNCat takes the same two routes, and
+    so does the EPSILON target with one more condition on "latent-csr": x_0 = G x_T - D (second Q^ + b_out) is ranked without
+    its first term, which is only right where G x_T touches masked items alone -- `rows` itself must be among `masks` (the
+    tuple of DeviceCSRs the call masks with); otherwise "latent" (dense rows, x_0 from the posterior epilogue)."""
+    if not extended:
+        if not (diffusion._latent_reverse_ok(model, sampling_noise, None) and _c1_0_positive(diffusion)):
+            return "item"
+        return "latent-csr" if (sampling_steps == 0 and rows.values is None) else "latent"
+    if not diffusion._latent_reverse_ok(model, sampling_noise, None, extended=True):
         return "item"
-    return "latent-csr" if (sampling_steps == 0 and rows.values is None) else "latent"
+    from .gaussian_diffusion import ModelMeanType
+    eps = diffusion.mean_type == ModelMeanType.EPSILON
+    if not eps and not _c1_0_positive(diffusion):
+        return "item"
+    binary = sampling_steps == 0 and rows.values is None
+    if eps:
+        return "latent-csr" if binary and masks is not None and any(m is rows for m in masks) else "latent"
+    return "latent-csr" if binary else "latent"
 
 
 def _step_tables(diffusion, B, cache):
@@ -46,19 +61,24 @@ def _step_tables(diffusion, B, cache):
     return cache[B]
 
 
-def _latent_operands(diffusion, model, x, steps, index, tabs, noise0=None, sampled0=None):
+def _latent_operands(diffusion, model, x, steps, index, tabs, noise0=None, sampled0=None, eps=None, stop=True):
     """The latent reverse loop on `x` (a CsrBatch of binary rows with steps == 0, or dense rows), ended before its last product:
     (A, second, K, b_out).  The one-hot variants' inputs and the degree-guided graph of an `indexIn` loop are built as
-    GaussianDiffusionDiscrete.p_sample(latent=True) builds them: same draws, same `last_graph`."""
+    GaussianDiffusionDiscrete.p_sample(latent=True) builds them: same draws, same `last_graph`.
+    eps (engine_core.EpsTables): the EPSILON target -- (-Q^, second, K, -b_out, G, D).  stop=False: the loop's x_0 instead."""
     eng = model.engine
+    ekw = dict(eps=eps) if eps is not None else {}
     if not diffusion.CatOneHot:
-        return eng.p_sample_loop(x, steps, diffusion.steps, diffusion._t32, False, False, noise0=noise0, latent=True, _stop=True)
+        return eng.p_sample_loop(x, steps, diffusion.steps, diffusion._t32, eps is not None, False, noise0=noise0, latent=True,
+                                 _stop=stop, **ekw)
     model = diffusion._onehot_model(model)
+    from .cat import DNNCat
+    cat = type(model) is DNNCat
     B, dev = x.shape[0], x.device
     c1, c2 = tabs
     deg = None
     if isinstance(x, CsrBatch):
-        x_tU, keep, x_t = eng.onehot_rows_sparse(x), None, x
+        x_tU, keep, x_t = (None if cat else eng.onehot_rows_sparse(x)), None, x
         if diffusion.indexIn:
             ip = x.csr.indptr
             deg = (ip[x.row_ids + 1] - ip[x.row_ids]).to(torch.float32)
@@ -83,7 +103,7 @@ def _latent_operands(diffusion, model, x, steps, index, tabs, noise0=None, sampl
             diffusion._graph_step(graph, torch.full((B,), i, dtype=torch.int64, device=dev), degp, None, None)
 
     ops = eng.latent_loop(x_t, x_tU, diffusion.steps, c1, c2, index=index if diffusion.indexIn else None,
-                          before_step=before_step, _stop=True)
+                          before_step=before_step, _stop=stop, **ekw)
     del keep
     diffusion.last_graph = graph
     return ops
@@ -103,7 +123,7 @@ def _as_mask(mask, rows):
 
 
 def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_steps=0, sampling_noise=False, batch_size=400,
-              return_values=False, noise0=None, sampled0=None):
+              return_values=False, noise0=None, sampled0=None, latent=True):
     """Top-k item ids [n, k] (int64, on the device; with return_values: (values [n, k] float32, ids)) for the users `user_ids` of
     the DeviceCSR `rows`: the reverse loop from each user's row, the mask's items set to -inf, the k largest predictions in
     descending order, equal ones in ascending item index (evaluate_utils.masked_topk's conventions).
@@ -117,7 +137,10 @@ def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_step
     The ids are range-checked once per call (the kernels do not check them): on the host for a host sequence; ids that already
     live on the device cost the call's one synchronising copy there.
     noise0 [n, I] / sampled0 [n, I] inject the draws of x_T with sampling_steps > 0, row for row of user_ids, as p_sample's
-    keywords of the same names do (parity runs)."""
+    keywords of the same names do (parity runs).
+    latent: True -- the routes above; "extended" -- route_of(extended=True): DNNCat on both latent routes, and the EPSILON
+    target: on "latent-csr" (only with `rows` itself among the masks) second (-Q^) + (-b_out) is ranked and the k values scaled by
+    D; on "latent" x_0 comes from the posterior epilogue on dense rows and is ranked as it is."""
     if not isinstance(rows, DeviceCSR):
         raise TypeError("gdmcf_amd.recommend: rows must be a gdmcf_amd.data_utils.DeviceCSR")
     _lib.require_gpu(rows.indptr, "rows")
@@ -138,8 +161,13 @@ def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_step
             raise IndexError("recommend: user_ids out of range")
     ids = ids.to(dev).contiguous()
     n = ids.numel()
-    route = route_of(diffusion, model, rows, sampling_steps, sampling_noise)
+    if not (latent is True or (isinstance(latent, str) and latent == "extended")):
+        raise ValueError('recommend: latent is True or "extended"')
+    extended = latent is not True
+    route = route_of(diffusion, model, rows, sampling_steps, sampling_noise, extended=extended, masks=masks)
     diffusion.last_recommend_route = route
+    from .gaussian_diffusion import ModelMeanType
+    eps = diffusion._eps_tables() if route != "item" and diffusion.mean_type == ModelMeanType.EPSILON else None
     idx = torch.empty(n, k, dtype=torch.int64, device=dev)
     val = torch.empty(n, k, dtype=torch.float32, device=dev) if return_values else None
     if n == 0:
@@ -161,9 +189,17 @@ def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_step
             x = rows.batch(chunk) if route == "latent-csr" else rows.rows(chunk)
             c1, c2 = _step_tables(diffusion, B, tabs)
             with torch.no_grad():
-                A, second, K, b_out = _latent_operands(diffusion, model, x, sampling_steps, index, (c1, c2), **inj)
-                scores = eng.score_product(A, second, K, b_out, B, dev)
-            scale = c1[0]
+                if eps is None:
+                    A, second, K, b_out = _latent_operands(diffusion, model, x, sampling_steps, index, (c1, c2), **inj)
+                    scores = eng.score_product(A, second, K, b_out, B, dev)
+                    scale = c1[0]
+                elif route == "latent-csr":
+                    # x_0 = G x_T + D (second (-Q^) + (-b_out)); G x_T lies on masked items only: rank the bracket, scale by D
+                    nQ, second, K, nb, _, D = _latent_operands(diffusion, model, x, sampling_steps, index, (c1, c2), eps=eps, **inj)
+                    scores = eng.score_product(nQ, second, K, nb, B, dev)
+                    scale = D
+                else:
+                    scores = _latent_operands(diffusion, model, x, sampling_steps, index, (c1, c2), eps=eps, stop=False, **inj)
             diffusion.last_reverse_route = "latent"
         v = val[lo:lo + B] if val is not None else None
         _lib.check(lib.gdmcf_topk_masked_rows_f32(

@@ -269,6 +269,27 @@ int gdmcf_latent_step_f32(const float* A, int64_t lda, const float* M, int64_t l
                           int B, int N, int K, float* p_next, int64_t ldpn, float* h_next, int64_t ldh,
                           void* ws, size_t ws_bytes, void* stream);
 size_t gdmcf_latent_step_ws_bytes(int B, int N, int K);
+/* gdmcf_latent_step_f32 with two optional parts, for the loops that are linear in x_t but not covered by the plain step (the
+ * EPSILON target, DNNCat):
+ *   row addend   r [B, ldr] (NULL: none):  h_next[b,n] = act((p_next[b,n] + r[b,n]) + e[n])  -- in this order, every sum rounded
+ *                to float32; p_next itself is stored without r.  16-byte loads where r and ldr allow, scalars otherwise (as e).
+ *   accumulator  q_next [B, ldqn] (NULL: none; then q_cur / qa / qb are not read), q_cur [B, ldqc], qa, qb float32 [B]:
+ *                  q_next[b,k] = fma(qa[b], q_cur[b,k], qb[b] * A[b,k])      for k < K
+ *                (the product qb * A rounded, then one fma).  A row with qa[b] == 0 does not read q_cur.  q_next may be q_cur,
+ *                never A (other workgroups still read A).  Columns k >= K of q_next are not written.  Every element is written
+ *                exactly once, with plain stores, by the workgroup that holds it as an operand: no further load of A.
+ * With r == NULL and q_next == NULL, p_next and h_next are gdmcf_latent_step_f32's bit for bit (same sums, same order); that
+ * entry's own kernel is unchanged.  One launch, no atomics, no workspace (ws may be NULL), no host synchronisation.             */
+int gdmcf_latent_step_ex_f32(const float* A, int64_t lda, const float* M, int64_t ldm, const float* v,
+                             const float* p_cur, int64_t ldpc, const float* c1, const float* c2, const float* r, int64_t ldr,
+                             const float* e, int act, int B, int N, int K, float* p_next, int64_t ldpn, float* h_next,
+                             int64_t ldh, const float* q_cur, int64_t ldqc, const float* qa, const float* qb, float* q_next,
+                             int64_t ldqn, void* ws, size_t ws_bytes, void* stream);
+/* The accumulator of gdmcf_latent_step_ex_f32 as a launch of its own (the last step of a loop, where no step kernel runs):
+ *   q_next[b,k] = fma(qa[b], q_cur[b,k], qb[b] * A[b,k])   for k < K -- the same expression, the same bits.
+ * All pointers required; lda, ldqc, ldqn >= K; q_next may be q_cur, never A; a row with qa[b] == 0 does not read q_cur.      */
+int gdmcf_latent_acc_f32(const float* q_cur, int64_t ldqc, const float* qa, const float* A, int64_t lda, const float* qb,
+                         int B, int K, float* q_next, int64_t ldqn, void* stream);
 /* Last layer fused with the per-row diffusion loss (gaussian_diffusion.py:335 mean_flat):
  *   out = A @ W^T + bias ;  diff[m,n] = alpha[m]*out[m,n] - target[m,n]   (alpha NULL -> 1)
  *   rowsum[m] = sum_n diff[m,n]^2  (deterministic two-stage reduction)

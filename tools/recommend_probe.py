@@ -2,6 +2,7 @@
 (DESIGN 4.10), back to back in one process on the same model.
 
     python tools/recommend_probe.py [--batches 50] [--rounds 5] [--out profiles/recommend_probe_yelp.json]
+    python tools/recommend_probe.py --mean-type eps --backbones dnn,onehot,dnncat    (recommend(latent="extended"))
 
 Yelp shape (34 395 items, hid 1000, T = 5), f32, eval mode, sampling_steps = 0, k = 20, the four backbones that have the latent
 loop, at n = 400 and n = 16 users per batch.  Legs, alternating for `rounds` rounds of `batches` batches each:
@@ -14,7 +15,9 @@ Two numbers per leg and round:
   wall_ms     per batch by the host's clock around the loop as a user runs it, one synchronisation at the end: the evaluate
               leg's host slicing shows only here.
 Per case the JSON document holds the median and max - min over the rounds of each, `saved_*` = evaluate - recommend, and
-`shown_*`: whether that difference exceeds the larger of the two spreads (a row that misses counts as not shown)."""
+`shown_*`: whether that difference exceeds the larger of the two spreads (a row that misses counts as not shown).
+With --mean-type eps or the backbone dnncat the recommend leg is recommend(latent="extended") and the evaluate leg is the same
+untouched call, which takes the item-space route for these configurations (`evaluate_route` in the document says so)."""
 import argparse
 import json
 import os
@@ -38,6 +41,7 @@ def main(argv=None):
     ap.add_argument("--preheat-seconds", type=float, default=1.5)
     ap.add_argument("--backbones", default=None)
     ap.add_argument("--sizes", default="400,16")
+    ap.add_argument("--mean-type", default="x0", choices=["x0", "eps"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
 
@@ -61,13 +65,15 @@ def main(argv=None):
                     "body of driver.evaluate(sparse=True, latent=True) vs gdmcf_amd.recommend; device_ms between HIP events "
                     "(evaluate's mask pieces uploaded beforehand), wall_ms by the host's clock with one synchronisation at the end; "
                     "median and max - min over rounds of alternating legs",
-               config=dict(n_items=I, n_users=U, pool_rows=n_rows, hidden=hid, T=T, k=k, batches=args.batches, rounds=args.rounds,
+               config=dict(mean_type=args.mean_type, n_items=I, n_users=U, pool_rows=n_rows, hidden=hid, T=T, k=k, batches=args.batches, rounds=args.rounds,
                            warmup=args.warmup, device=torch.cuda.get_device_name(dev)),
                clock_preheat=preheat, cases={})
 
     for backbone in (args.backbones.split(",") if args.backbones else BACKBONES):
         torch.manual_seed(0)
-        model, diffusion, _, _ = _pair(backbone, I, hid, T, U, dev)
+        model, diffusion, _, _ = _pair(backbone, I, hid, T, U, dev, args.mean_type)
+        extended = args.mean_type == "eps" or backbone == "dnncat"
+        ekw = dict(latent="extended") if extended else {}
         model = model.to(dev).eval()
         with_index = backbone in ("onehot-emb", "onehot-gcn")
         for n in (int(s) for s in args.sizes.split(",")):
@@ -84,10 +90,10 @@ def main(argv=None):
                     pred = diffusion.p_sample(model, dcsr.batch(dev_ids[b]), 0, False, latent=True, **kw)
                     ip, ix = pieces[b % per] if sliced else evaluate_utils.csr_rows_to_device(train, host_ids[b], dev)
                     lists["evaluate"] = evaluate_utils.masked_topk(pred, k, ip, ix)
-                assert diffusion.last_reverse_route == "latent"
+                assert diffusion.last_reverse_route == ("item" if extended else "latent")
 
             def recommend_leg(nb, sliced):
-                lists["recommend"] = gdmcf_amd.recommend(diffusion, model, dcsr, all_ids[:nb * n], k, batch_size=n)[-n:]
+                lists["recommend"] = gdmcf_amd.recommend(diffusion, model, dcsr, all_ids[:nb * n], k, batch_size=n, **ekw)[-n:]
                 assert diffusion.last_recommend_route == "latent-csr"
 
             def timed(leg, nb, sliced):
@@ -120,6 +126,7 @@ def main(argv=None):
             a, b = lists["evaluate"].cpu().numpy(), lists["recommend"].cpu().numpy()
             res["list_overlap"] = round(float(np.mean([len(set(x) & set(y)) / k for x, y in zip(a, b)])), 6)
             res["lists_equal"] = bool(np.array_equal(a, b))
+            res["evaluate_route"] = "item" if extended else "latent"
             out["cases"][f"{backbone}/n={n}"] = res
             print(f"{backbone}/n={n}", json.dumps(res), flush=True)
         del model, diffusion
