@@ -165,23 +165,23 @@ class CatEngine(DenoiserEngine):
         return res
 
     # -- reverse loop in the first hidden layer's space (GaussianDiffusionDiscrete.p_sample(latent="extended")) ----------------
-    def _latent_cat_tables(self, bufs, ops, c1, B, sparse):
+    def _latent_cat_tables(self, bufs, ops, B, sparse):
         """What the loop needs of cat_layer's parameters, which live on the device: per-row coefficient vectors [B] for
-        gdmcf_latent_acc_f32, the step table c1 . w0 [T, B] and, on CSR rows, the time table with (w1 + c) S added.  Made by
-        torch from the parameters (no host read, no synchronisation) and kept until one of them, c1 or the operands change."""
+        gdmcf_latent_acc_f32 and, on CSR rows, the time table with (w1 + c) S added.  Made by torch from the parameters (no host
+        read, no synchronisation) and kept until one of them or the operands change; the step table c1 . w0 [T, B] joins it in
+        latent_loop (c1_src, c1)."""
         cw, cb_ = self._cat_params()
         key = (cw.data_ptr(), cw._version, cb_.data_ptr(), cb_._version, sparse)
         t = getattr(bufs, "lat_cat", None)
-        if t is not None and t.key == key and t.c1_src is c1 and t.ops is ops:
+        if t is not None and t.key == key and t.ops is ops:
             return t
         wv, h = cw.detach().reshape(-1), ops.S.shape[0]
         t = _Bufs()
-        t.key, t.c1_src, t.ops = key, c1, ops
+        t.key, t.ops, t.c1_src = key, ops, None
         t.w0 = wv[0].expand(B).contiguous()
         t.neg_w0 = -t.w0
         t.beta = (wv[2] - wv[1]).expand(B).contiguous()
         t.one, t.zero = torch.ones_like(t.w0), torch.zeros_like(t.w0)
-        t.c1 = c1 * wv[0]
         t.e = ops.e
         if sparse:
             t.e = ops.e.clone()
@@ -190,18 +190,17 @@ class CatEngine(DenoiserEngine):
         return t
 
     @with_precision
-    def latent_loop(self, x_T, x_U, T, c1, c2, index=None, before_step=None, _stop=False, eps=None):
+    def latent_loop(self, x_T, x_U, T, tabs32, index=None, before_step=None, stop=False, eps=None):
         """OneHotEngine.latent_loop's call for this backbone.  x_tU is the same image at every step and dropout is off, so the
         first layer's input is z_t = w0 x_t + u with u = w1 xU0 + w2 xU1 + c fixed, and its pre-activation is
             w0 p_t + r + e_t,    p_t = W1x x_t,   r = W1x u  [B, h], once per call.
-        p~_t = w0 p_t is carried: the step of DenoiserEngine._latent_loop with c1 times w0, and h = tanh((p~ + r) + e)
-        (gdmcf_latent_step_ex_f32's row addend).
+        p~_t = w0 p_t is carried: the step of EngineBase._latent_reverse with c1 times w0 and the row addend r.
           x_T a data_utils.CsrBatch of binary rows (x_U None: xU0 = 1 - x, xU1 = x): r = (w1 + c) S + (w2 - w1) p_T with
             S = W1x 1 cached beside M and v; the first term is added to the time table, p_T is the one gather -- no [B, 2I]
             image, no builder.  Item-wide work: the last product.
           dense rows with the [B, 2I] image x_U: gdmcf_cat_prep_input_f32 once for z_T and x_T, two first-layer products
             (W1x z_T, W1x x_T), r = W1x z_T - w0 p_T.  Item-wide work: those two and the last product, whatever T is.
-        eps / _stop: as OneHotEngine.latent_loop.  The Philox position advances as on the item-space route (the class draws,
+        eps / stop: as OneHotEngine.latent_loop.  The Philox position advances as on the item-space route (the class draws,
         then one builder per step), whether or not those kernels ran."""
         from .data_utils import CsrBatch
         self.flush_weight_waiters()
@@ -212,30 +211,20 @@ class CatEngine(DenoiserEngine):
         self._shadows_on(bufs, layers)
         self.version += 1
         self._saved = None
-        (w1, b1, act1), (w, bias, _) = layers[0], layers[-1]
-        h1, K = w1.shape[0], w.shape[1]
-        for wl, _, _ in layers:
-            self._use_weight(wl)
-        emb = self.model.emb_layer
-        ops = self._latent_operands(w1, b1, w, K, bias, T, (w1, b1, w, bias, emb.weight, emb.bias))
-        c1_last = c1
-        if eps is not None:
-            et = eps.on(dev, B)
-            c1, c2 = et["neg_d"], et["g"]
+        w1 = layers[0][0]
+        h1 = w1.shape[0]
+        ops, tabs, p, ld = self._latent_begin(bufs, layers, T, B, tabs32)
         sparse = isinstance(x_T, CsrBatch)
-        t = self._latent_cat_tables(bufs, ops, c1, B, sparse)
-        if getattr(bufs, "lat_p", None) is None:
-            f32 = dict(dtype=torch.float32, device=dev)
-            for name in ("lat_p", "lat_h", "lat_pT", "lat_r", "lat_s"):
-                setattr(bufs, name, torch.zeros(B, core._ceil64(h1), **f32))
-            bufs.lat_q = torch.zeros(B, core._ceil64(K), **f32)
-        p, pT, r, s, Q = bufs.lat_p, bufs.lat_pT, bufs.lat_r, bufs.lat_s, bufs.lat_q
+        t = self._latent_cat_tables(bufs, ops, B, sparse)
+        if getattr(bufs, "lat_pT", None) is None:
+            bufs.lat_pT, bufs.lat_r, bufs.lat_s = (torch.zeros(B, ld, dtype=torch.float32, device=dev) for _ in range(3))
+        pT, r, s = bufs.lat_pT, bufs.lat_r, bufs.lat_s
         if sparse:
             self.offset += 1 + T  # (the class draws and the T builders of the item-space route)
             keep = None
             core.gather_fwd(lib, None, None, x_T, self._transposed(w1), I, None, None, 0, None, 0, B, h1, pT, st)
             core.latent_acc(lib, r, t.zero, pT, t.beta, B, h1, r, st)  # r = (w2 - w1) p_T; (w1 + c) S sits in t.e
-            xdense = None if _stop else x_T.dense()
+            xdense = None if stop else x_T.dense()
         else:
             xu = x_U.reshape(B, -1)
             if xu.shape[1] != 2 * I:
@@ -248,34 +237,15 @@ class CatEngine(DenoiserEngine):
             core.latent_acc(lib, s, t.one, pT, t.neg_w0, B, h1, r, st)  # r = W1x z_T - w0 p_T
             xdense = bufs.xt
         core.latent_acc(lib, p, t.zero, pT, t.w0, B, h1, p, st)  # p~_T = w0 p_T
-        core.latent_acc(lib, p, t.one, r, t.one, B, h1, s, st)  # p~_T + r, then + e and tanh
-        hcur, hnxt = bufs.acts[0], bufs.lat_h
-        core.gather_fwd(lib, s, None, None, None, I, None, None, 0, t.e[T - 1], act1, B, h1, hcur, st)
-        for n, i in enumerate(range(T - 1, -1, -1)):
-            if before_step is not None:
-                before_step(n, i)
-            A = hcur
-            for li in range(1, len(layers) - 1):
-                wl, bl, al = layers[li]
-                out = bufs.acts[li]
-                core.linear_fwd(lib, bufs, A, wl, bl, al, B, wl.shape[0], wl.shape[1], out, st)
-                A = out
-            if i > 0:
-                acc = (Q, et["qa"][i], et["qb"][i], Q) if eps is not None else None
-                core.latent_step_ex(lib, A, ops.M, ops.v, p, t.c1[i], c2[i], r, t.e[i - 1], act1, B, h1, K, p, hnxt, acc, st)
-                hcur, hnxt = hnxt, hcur
-                continue
-            if eps is not None:
-                qa0, qb0 = (et["qa0_neg"], et["qb0_neg"]) if _stop else (et["qa"][0], et["qb"][0])
-                core.latent_acc(lib, Q, qa0, A, qb0, B, K, Q, st)
-                x0 = (Q, w, K, ops.neg_b, et["G"], et["D"])
-                post = (Q, et["one"], et["zero"], et["G"], et["D"])
-            else:
-                x0 = (A, w, K, bias)
-                post = (A, c1_last[0], c2[0], None, None)
-            if not _stop:
-                x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
-                core.posterior_fwd(lib, post[0], w, bias, xdense, post[1], post[2], post[3], post[4], None, None, B, I, K, x0, None, st)
+        core.latent_acc(lib, p, t.one, r, t.one, B, h1, s, st)  # p~_T + r: the first activation's pre-activation without e
+
+        def c1_of(c1):  # the step table c1 . w0 [T, B], kept while `t` and the table stay
+            if t.c1_src is not c1:
+                t.c1_src, t.c1 = c1, c1 * t.w0[0]
+            return t.c1
+
+        x0 = self._latent_run(bufs, layers, ops, tabs, T, B, s, p, t.e, xdense, stop=stop, eps=eps, r=r, c1_of=c1_of,
+                              before_step=before_step)
         del keep
         return x0
 

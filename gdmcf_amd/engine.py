@@ -369,12 +369,11 @@ class DenoiserEngine(EngineBase):
     # ------------------------------------------------------------------------------------------
     @with_precision
     def p_sample_loop(self, x_start, steps, T, tabs32, eps_mode, sampling_noise, noise0=None, step_noise=None,
-                      capture=None, draw_noise=None, latent=False, _stop=False, eps=None):
+                      capture=None, draw_noise=None, latent=False, stop=False, eps=None):
         """latent: carry the loop in the first hidden layer's space (_latent_loop; the caller has checked
-        GaussianDiffusion._latent_reverse_ok).  _stop (with latent; gdmcf_amd.recommend): end the loop at its last operands and
-        return (A, second, K, b_out) instead of x_0.  eps (with latent and eps_mode; p_sample(latent="extended")): the
-        engine_core.EpsTables of the schedule -- the EPSILON target's latent loop; with _stop it returns
-        (-Q^, second, K, -b_out, G, D), x_0 = G x_T + D ((-Q^) second^T + (-b_out)).
+        GaussianDiffusion._latent_reverse_ok).  stop (with latent; gdmcf_amd.recommend): end the loop before its last product and
+        return that product's engine_core.LatentProduct instead of x_0.  eps (with latent and eps_mode; p_sample(latent="extended")):
+        the engine_core.EpsTables of the schedule -- the EPSILON target's latent loop.
         tabs32: dict of float32 device tables [T] (sqrt_ab, sqrt_1mab, c1, c2, r1, r2, sigma).  draw_noise(like) -> [B, I]
         float32 N(0,1): the reverse loop's th.randn_like(x_t) (reference :210-217); default: gdmcf_randn_f32 on the engine's
         Philox seed (stream 7, one offset per draw).
@@ -403,7 +402,7 @@ class DenoiserEngine(EngineBase):
             if (eps_mode and eps is None) or sampling_noise or capture is not None or m.norm or self.gemm_dtype != "f32":
                 raise RuntimeError("gdmcf_amd: the latent reverse loop takes the x0 target without sampling noise, capture or "
                                    "F.normalize, in float32 products (GaussianDiffusion._latent_reverse_ok)")
-            return self._latent_loop(bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=_stop, eps=eps if eps_mode else None)
+            return self._latent_loop(bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=stop, eps=eps if eps_mode else None)
         if bufs.xin2 is None:
             bufs.xin2 = torch.zeros_like(bufs.xin)
         if self.gemm_dtype == "bf16" and getattr(bufs, "sh_xin2", None) is None:
@@ -421,13 +420,10 @@ class DenoiserEngine(EngineBase):
 
         # per-step coefficient vectors [B] and timestep vectors: expanded ONCE per (schedule, batch size) into [T, B]
         # tables whose rows are used as they stand (was 3-6 tiny launches per reverse step)
-        key = (id(tabs32), T, B)
-        if getattr(bufs, "step_tabs_key", None) != key:
-            bufs.step_tabs = {k: tabs32[k][:T, None].expand(T, B).contiguous() for k in ("c1", "c2", "r1", "r2", "sigma")
-                              if k in tabs32}
+        stabs = core.step_tables(tabs32, T, B, ("c1", "c2", "r1", "r2", "sigma"), bufs.tab_cache)
+        if getattr(bufs, "step_ts", None) is None or bufs.step_ts.shape[0] != T:
             bufs.step_ts = torch.arange(T, dtype=torch.int64, device=dev)[:, None].expand(T, B).contiguous()
-            bufs.step_tabs_key = key
-        stabs, step_ts = bufs.step_tabs, bufs.step_ts
+        step_ts = bufs.step_ts
 
         def posterior(i, n, A, xt, xn):
             c1, c2 = stabs["c1"][i], stabs["c2"][i]
@@ -483,44 +479,45 @@ class DenoiserEngine(EngineBase):
         del keep
         return out
 
-    def _latent_loop(self, bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=False, eps=None):
-        """The reverse loop in the first hidden layer's space.  With the x0 target and no sampling noise the loop is linear in x_t
-        between two hidden activations, x_{t-1} = c1[t] (W_out a_t + b_out) + c2[t] x_t, so p_t = W1x x_t obeys
-            p_{t-1} = c1[t] (M a_t + v) + c2[t] p_t,    M = W1x W_out,  v = W1x b_out,    h_{t-1} = tanh(p_{t-1} + e_{t-1})
-        (one gdmcf_latent_step_f32 per step; M, v and the table e are _latent_operands).  Two item-wide products remain whatever T
-        is: the first layer on x_T into p (no time columns, no activation; a gather on CSR rows) and the output product of the last
-        step, x_0 = c1[0] (W_out a_0 + b_out) -- posterior_mean_coef2[0] is exactly 0.  x_T is built as in the item-space loop: same
-        builder, same Philox offsets.
-        stop: return (A, second, K, b_out), the operands of the last product x_0 = c1[0] (A second^T + b_out), without running it;
-        on CSR rows no builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had.
-        eps (engine_core.EpsTables): the EPSILON target.  The step is x_{t-1} = g_t x_t - d_t (W_out a_t + b_out), the same kernel
-        with c1 := -d_t, c2 := g_t (gdmcf_latent_step_ex_f32, which also keeps Q <- g_t Q + d_t a_t); the last step's accumulation
-        is gdmcf_latent_acc_f32 with the factor 1 / D folded in, and x_0 = G x_T - D (W_out Q^ + b_out) is the posterior epilogue in
-        its eps form (r1 = G, r2 = D, c1 = 1, c2 = 0) on the dense x_T.  stop: (-Q^, second, K, -b_out, G, D), the operands of the
-        product gdmcf_amd.recommend ranks (scale D > 0) and the per-row scalars."""
-        lib, st, I = self.lib, _lib.stream_ptr(), self.I
-        B, dev = x_start.shape[0], x_start.device
-        (w1, b1, act1), (w, bias, _) = layers[0], layers[-1]
-        h1, K = w1.shape[0], w.shape[1]
+    def _latent_begin(self, bufs, layers, T, B, tabs32):
+        """What a latent loop of this layer chain starts from, every weight waited for: (cached operands, [T, B] c1 / c2, p and
+        its row width)."""
         for wl, _, _ in layers:
             self._use_weight(wl)
-        emb = self.model.emb_layer
-        ops = self._latent_operands(w1, b1, w, K, bias, T, (w1, b1, w, bias, emb.weight, emb.bias))
-        key = (id(tabs32), T, B)
-        if getattr(bufs, "lat_tabs_key", None) != key:
-            bufs.lat_tabs = {k: tabs32[k][:T, None].expand(T, B).contiguous() for k in ("c1", "c2")}
-            bufs.lat_tabs_key = key
-        c1, c2 = bufs.lat_tabs["c1"], bufs.lat_tabs["c2"]
-        if eps is not None:
-            et = eps.on(dev, B)
-            c1, c2 = et["neg_d"], et["g"]
-            if getattr(bufs, "lat_q", None) is None:
-                bufs.lat_q = torch.zeros(B, _ceil64(K), dtype=torch.float32, device=dev)
-            Q = bufs.lat_q
+        (w1, b1, _), (w, bias, _), emb = layers[0], layers[-1], self.model.emb_layer
+        ops = self._latent_operands(w1, b1, w, w.shape[1], bias, T, (w1, b1, w, bias, emb.weight, emb.bias))
+        ld = _ceil64(w1.shape[0])
         if getattr(bufs, "lat_p", None) is None:
-            bufs.lat_p = torch.zeros(B, _ceil64(h1), dtype=torch.float32, device=dev)
-            bufs.lat_h = torch.zeros(B, _ceil64(h1), dtype=torch.float32, device=dev)
-        p = bufs.lat_p
+            bufs.lat_p = torch.zeros(B, ld, dtype=torch.float32, device=w1.device)
+            bufs.lat_h = torch.zeros_like(bufs.lat_p)
+        return ops, core.step_tables(tabs32, T, B, ("c1", "c2"), bufs.tab_cache), bufs.lat_p, ld
+
+    def _latent_run(self, bufs, layers, ops, tabs, T, B, pre, p, e, x_T, **kw):
+        """EngineBase._latent_reverse on this layer chain: the first activation alternates between two buffers (with one hidden
+        layer it is the step kernel's operand A as well), the layers between it and the last product are the small ones."""
+        (_, _, act1), (w, bias, _), lib, st = layers[0], layers[-1], self.lib, _lib.stream_ptr()
+
+        def middle(n, i, A):
+            for li in range(1, len(layers) - 1):
+                wl, bl, al = layers[li]
+                core.linear_fwd(lib, bufs, A, wl, bl, al, B, wl.shape[0], wl.shape[1], bufs.acts[li], st)
+                A = bufs.acts[li]
+            return A
+
+        return self._latent_reverse(bufs, ops, T, B, w.shape[1], act1, pre, p, (bufs.acts[0], bufs.lat_h),
+                                    middle if len(layers) > 2 else None, e, tabs["c1"], tabs["c2"], w, bias, x_T, **kw)
+
+    def _latent_loop(self, bufs, layers, x_start, csr, steps, T, tabs32, noise0, stop=False, eps=None):
+        """The reverse loop in the first hidden layer's space (EngineBase._latent_reverse has the algebra and the loop): here p_T and
+        the dense x_T.  x_T is built as in the item-space loop -- same builder, same Philox offsets -- into bufs.xin, and p_T = W1x x_T
+        is the first layer on it without time columns and activation (a gather on CSR rows).
+        stop: return the engine_core.LatentProduct of the last product without running it; on CSR rows no builder runs then (nothing
+        reads a dense x_T) -- the Philox position advances as if it had.  eps (engine_core.EpsTables): the EPSILON target."""
+        lib, st, I = self.lib, _lib.stream_ptr(), self.I
+        B, dev = x_start.shape[0], x_start.device
+        w1 = layers[0][0]
+        h1 = w1.shape[0]
+        ops, tabs, p, _ = self._latent_begin(bufs, layers, T, B, tabs32)
         t_vec = torch.full((B,), max(steps - 1, 0), dtype=torch.int64, device=dev)
         if csr is not None:
             if stop:
@@ -534,38 +531,7 @@ class DenoiserEngine(EngineBase):
             keep = self._prep(bufs, x_start, t_vec, ca, cb, noise0, None, False, xin=bufs.xin)  # x_T
             core.linear_fwd(lib, bufs, (bufs.xin.data_ptr(), bufs.xin.stride(0)), w1, None, 0, B, h1, I, p, st)
         bufs.xin_ones = False
-        # the first activation alternates between two buffers: with one hidden layer it is the step kernel's operand A as well
-        hcur, hnxt = bufs.acts[0], bufs.lat_h
-        core.gather_fwd(lib, p, None, None, None, I, None, None, 0, ops.e[T - 1], act1, B, h1, hcur, st)
-        for i in range(T - 1, -1, -1):
-            A = hcur
-            for li in range(1, len(layers) - 1):
-                wl, bl, al = layers[li]
-                out = bufs.acts[li]
-                core.linear_fwd(lib, bufs, A, wl, bl, al, B, wl.shape[0], wl.shape[1], out, st)
-                A = out
-            if i == 0 and eps is not None:
-                if stop:  # the sign goes into the last accumulation: -Q^ beside the cached -b_out
-                    core.latent_acc(lib, Q, et["qa0_neg"], A, et["qb0_neg"], B, K, Q, st)
-                    x0 = (Q, w, K, ops.neg_b, et["G"], et["D"])
-                    break
-                core.latent_acc(lib, Q, et["qa"][0], A, et["qb"][0], B, K, Q, st)
-                x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
-                core.posterior_fwd(lib, Q, w, bias, bufs.xin, et["one"], et["zero"], et["G"], et["D"], None, None, B, I, K, x0, None, st)
-                break
-            if i == 0:
-                if stop:
-                    x0 = (A, w, K, bias)
-                    break
-                x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
-                core.posterior_fwd(lib, A, w, bias, bufs.xin, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
-                break
-            if eps is not None:
-                core.latent_step_ex(lib, A, ops.M, ops.v, p, c1[i], c2[i], None, ops.e[i - 1], act1, B, h1, K, p, hnxt,
-                                    (Q, et["qa"][i], et["qb"][i], Q), st)
-            else:
-                core.latent_step(lib, A, ops.M, ops.v, p, c1[i], c2[i], ops.e[i - 1], act1, B, h1, K, p, hnxt, st)
-            hcur, hnxt = hnxt, hcur
+        x0 = self._latent_run(bufs, layers, ops, tabs, T, B, p, p, ops.e, bufs.xin, stop=stop, eps=eps)
         self._saved = None
         del keep
         return x0

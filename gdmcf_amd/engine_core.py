@@ -4,9 +4,12 @@
   * `EngineBase`: Philox position, buffer cache, the buffers every backbone has, parameter layout check, the fused
     optimiser's state, the input builder with its Philox step, the weight-gradient step (row scale, product) and the input gradient
     of one layer.
+  * the host side of the reverse loop in the first hidden layer's space: `step_tables`, `EpsTables`, `LatentProduct`, and in
+    `EngineBase` the cached operands (`_latent_operands`) and the one step loop with its ending (`_latent_reverse`).
   * `TrainLoss`: the autograd function of the fused training loss.
 PyTorch is used for device memory and streams only; every arithmetic step is a HIP kernel.
 """
+import collections
 import functools
 
 import torch
@@ -199,12 +202,30 @@ def latent_acc(lib, q_cur, qa, A, qb, B, K, q_next, st):
     _lib.check(lib.gdmcf_latent_acc_f32(qc, ldqc, qa.data_ptr(), a, lda, qb.data_ptr(), B, K, qn, ldqn, st))
 
 
+def step_tables(tabs32, T, B, names, cache=None):
+    """{name: [T, B] float32} of the per-timestep tables `names` of tabs32 (those it holds): row t is the per-row coefficient
+    vector of step t as the kernels read it, expanded once instead of per step.  cache: a dict that keeps the last expansion
+    per `names`, reused while (tabs32, T, B) stay the same."""
+    key = (id(tabs32), int(T), int(B))
+    rec = cache.get(names) if cache is not None else None
+    if rec is None or rec[0] != key:
+        rec = (key, {k: tabs32[k][:T, None].expand(T, B).contiguous() for k in names if k in tabs32})
+        if cache is not None:
+            cache[names] = rec
+    return rec[1]
+
+
+# A latent reverse loop ended before its last product (stop=True; gdmcf_amd.recommend ranks it): the prediction is
+# scale . (A second^T + bias) per row, second [I, K].  x0 target: A = the last activation, bias = b_out, scale = c1[0].
+# EPSILON target: A = -Q^, bias = -b_out, scale = D, and the prediction lacks G x_T (EngineBase._latent_reverse).
+LatentProduct = collections.namedtuple("LatentProduct", "A second K bias scale")
+
+
 class EpsTables:
-    """Host side of the EPSILON target's latent loop.  The item-space step is x_{t-1} = g_t x_t - d_t (second a_t + b_out)
-    with g_t = c1[t] r1[t] + c2[t], d_t = c1[t] r2[t]; unrolled, x_0 = G x_T - D (second Q^ + b_out) with G = prod g_t,
-    D <- g_t D + d_t and Q^ = Q / D, Q <- g_t Q + d_t a_t.  Everything here is formed in float64 from the host's schedule tables
-    and rounded once: no device read.  g, d: float32 [T]; qa, qb: float32 [T], the accumulator's coefficients (qa[T-1] = 0: Q_T
-    is 0 and is not read; step 0's carry the factor 1 / D); G, D: floats; ok: all finite and D > 0."""
+    """Host side of the EPSILON target's latent loop (EngineBase._latent_reverse has the algebra): g_t, d_t, G, D and the
+    accumulator's coefficients, formed in float64 from the host's schedule tables and rounded once -- no device read.  g, d: float32
+    [T]; qa, qb: float32 [T] (qa[T-1] = 0: Q_T is 0 and is not read; step 0's carry the factor 1 / D); G, D: floats; ok: all
+    finite and D > 0."""
 
     def __init__(self, c1, c2, r1, r2, T):
         import numpy as np
@@ -470,6 +491,74 @@ class EngineBase:
         self._latent = (key, o)
         return o
 
+    def _latent_reverse(self, bufs, ops, T, B, K, act, pre, p, hpair, small, e, c1, c2, second, b_out, x_T, stop=False, eps=None,
+                        r=None, c1_of=None, before_step=None):
+        """The reverse loop carried in the first hidden layer's space, from p_T to x_0: the one step loop and the one
+        ending of every backbone's latent loop.
+        With the x0 target and no sampling noise the item-space loop is linear in x_t between two hidden activations,
+        x_{t-1} = c1[t] (second a_t + b_out) + c2[t] x_t, so p_t = W1x x_t obeys
+            p_{t-1} = c1[t] (M a_t + v) + c2[t] p_t,    M = W1x second,  v = W1x b_out,    h_{t-1} = act((p_{t-1} + r) + e_{t-1})
+        -- one step kernel per step on the operands of _latent_operands, plus the engine's small layers from h_t to a_t.  Item-wide
+        work is left at the two ends, whatever T is: p_T (the engine's, before this call) and the last product,
+        x_0 = c1[0] (second a_0 + b_out) -- posterior_mean_coef2[0] is exactly 0.
+        eps (EpsTables): the EPSILON target.  The step is x_{t-1} = g_t x_t - d_t (second a_t + b_out) with g_t = c1[t] r1[t] + c2[t],
+        d_t = c1[t] r2[t]: the same kernel with c1 := -d, c2 := g.  Unrolled, x_0 = G x_T - D (second Q^ + b_out) with G = prod g_t,
+        D <- g_t D + d_t, Q <- g_t Q + d_t a_t and Q^ = Q / D: every step's launch also advances Q (gdmcf_latent_step_ex_f32), step
+        0's accumulation is gdmcf_latent_acc_f32 with the factor 1 / D folded in, and x_0 is the posterior epilogue in its eps form
+        (r1 = G, r2 = D, c1 = 1, c2 = 0) on the dense x_T.
+        The step is gdmcf_latent_step_f32 where there is neither a row addend nor an accumulator, gdmcf_latent_step_ex_f32 otherwise.
+          ops            _latent_operands' record (M, v, neg_b);  act: the first layer's activation;  e [T, .]: its time table
+          pre, p         [B, .]: the pre-activation of h_{T-1} without e (p_T, plus r where there is one), and the buffer that holds
+                         p_T and carries p_t
+          hpair          the two buffers the first activation alternates between (one buffer twice where nothing else reads it)
+          small(n, i, h) the engine's layers of step n (timestep i) from the first activation h to a_t, the operand of M and second
+                         (None: there are none, a_t = h)
+          c1, c2         [T, B] posterior_mean_coef1 / 2 (step_tables);  c1_of: maps the step's c1 table (after the eps swap) to the
+                         one the kernel reads (DNNCat: times w0)
+          r              [B, .] row addend or None;  before_step(n, i): called ahead of step n, e.g. the degree-guided graph update
+          x_T            the dense x_T, the x_t operand of the last product's epilogue (x0 target: only finite, c2[0] is 0; eps: it
+                         carries G x_T); not read with stop
+        Returns x_0 [B, I]; stop: the LatentProduct of the last product instead, which is not run (eps: the sign goes into the last
+        accumulation, -Q^ beside the cached -b_out)."""
+        lib, st, I, dev, h = self.lib, _lib.stream_ptr(), self.I, p.device, ops.M.shape[0]
+        s1, s2, Q = c1, c2, None
+        if eps is not None:
+            et = eps.on(dev, B)
+            s1, s2, qa, qb = et["neg_d"], et["g"], et["qa"], et["qb"]
+            if getattr(bufs, "lat_q", None) is None:
+                bufs.lat_q = torch.zeros(B, _ceil64(K), dtype=torch.float32, device=dev)
+            Q = bufs.lat_q
+        if c1_of is not None:
+            s1 = c1_of(s1)
+        plain = r is None and Q is None
+        hcur, hnxt = hpair
+        gather_fwd(lib, pre, None, None, None, I, None, None, 0, e[T - 1], act, B, h, hcur, st)  # h_{T-1}
+        for n, i in enumerate(range(T - 1, -1, -1)):
+            if before_step is not None:
+                before_step(n, i)
+            A = small(n, i, hcur) if small is not None else hcur
+            if i == 0:
+                break
+            if plain:
+                latent_step(lib, A, ops.M, ops.v, p, s1[i], s2[i], e[i - 1], act, B, h, K, p, hnxt, st)
+            else:
+                latent_step_ex(lib, A, ops.M, ops.v, p, s1[i], s2[i], r, e[i - 1], act, B, h, K, p, hnxt,
+                               (Q, qa[i], qb[i], Q) if Q is not None else None, st)
+            hcur, hnxt = hnxt, hcur
+        if eps is not None:
+            qa0, qb0 = (et["qa0_neg"], et["qb0_neg"]) if stop else (qa[0], qb[0])
+            latent_acc(lib, Q, qa0, A, qb0, B, K, Q, st)
+            if stop:
+                return LatentProduct(Q, second, K, ops.neg_b, et["D"])
+        elif stop:
+            return LatentProduct(A, second, K, b_out, c1[0])
+        x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
+        if eps is not None:
+            posterior_fwd(lib, Q, second, b_out, x_T, et["one"], et["zero"], et["G"], et["D"], None, None, B, I, K, x0, None, st)
+        else:
+            posterior_fwd(lib, A, second, b_out, x_T, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
+        return x0
+
     @with_precision
     def score_product(self, A, second, K, b_out, B, device):
         """A second^T + b_out into the [B, I] score buffer of this batch size (made on first use, reused by every later call): the
@@ -509,6 +598,7 @@ class EngineBase:
         b.lu = torch.zeros(B, dtype=torch.float64, device=device)
         b.demb = torch.zeros((B + n_first) * max(E, 1), **f32)  # demb [B,E] + gathered W1[:, I:] [n_first,E]
         b.ws_bytes = 0
+        b.tab_cache = {}  # step_tables' expansions for this batch size (reverse loops)
         self._grow_workspace(b, B, device, [w.shape for w in weights])
 
     def _grow_workspace(self, b, B, device, shapes):

@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from . import _lib
 from .DNN import DNN
-from .engine_core import TrainLoss, prep_input
+from .engine_core import TrainLoss, prep_input, step_tables
 
 _SCHEDULE_KIND = {"linear": 0, "linear-var": 1, "cosine": 2, "binomial": 3}
 
@@ -362,13 +362,21 @@ class GaussianDiffusion(nn.Module):
                     t = torch.full((x_t.shape[0],), i, dtype=torch.int64, device=x_t.device)
                     x_t = model(x_t, t)
             return x_t
+        if latent:
+            return self._latent_sample(model, x_start, steps, noise0=noise0)
         with torch.no_grad():
-            kw = dict(latent=True) if latent else {}
-            if latent and eps_mode:
-                kw["eps"] = self._eps_tables()
             return model.engine.p_sample_loop(x_start, steps, self.steps, self._t32, eps_mode, bool(sampling_noise),
                                               noise0=noise0, step_noise=step_noise, capture=capture,
-                                              draw_noise=lambda like: self._draw_noise(like, stream_id=7), **kw)
+                                              draw_noise=lambda like: self._draw_noise(like, stream_id=7))
+
+    def _latent_sample(self, model, x, steps, index=None, stop=False, noise0=None, sampled0=None):
+        """The latent route of p_sample on `x` (dense rows, or a CsrBatch the route keeps sparse; the caller has checked
+        _latent_reverse_ok).  stop (gdmcf_amd.recommend): the loop ends before its last product and returns that product's
+        engine_core.LatentProduct.  (index, sampled0: the one-hot variant's.)"""
+        eps = self._eps_tables() if self.mean_type == ModelMeanType.EPSILON else None
+        with torch.no_grad():
+            return model.engine.p_sample_loop(x, steps, self.steps, self._t32, eps is not None, False, noise0=noise0, latent=True,
+                                              stop=stop, eps=eps)
 
 
 class GaussianDiffusionDiscrete(GaussianDiffusion):
@@ -398,6 +406,7 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         self.indexIn = False
         self.user_guided = bool(getattr(args, "user_guided", False))  # the only field of `args` the reference reads (:720)
         self.last_graph = None
+        self._step_tabs = {}  # engine_core.step_tables' last expansion for the item-space loop of p_sample
 
     # -- the reference's public pieces of the discrete noise, for callers that use them directly -------------------
     def get_Qt_bar(self, alpha_bar_t):
@@ -468,9 +477,9 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
 
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,
                  capture=None, sampled0=None, graph_sampled=None, graph_pick=None, latent=False):
-        """latent: as GaussianDiffusion.p_sample -- where _latent_reverse_ok holds the loop runs in the engine
-        (OneHotEngine.latent_loop); with `indexIn` the per-step graph update runs exactly as on the item-space route (same draws,
-        same `last_graph`).
+        """latent: as GaussianDiffusion.p_sample -- where _latent_reverse_ok holds the loop runs in the engine (_latent_sample:
+        OneHotEngine.latent_loop / CatEngine.latent_loop); both routes start from _reverse_inputs, and with `indexIn` the per-step
+        graph update runs exactly as on the item-space route (same draws, same `last_graph`).
         Reverse loop of the one-hot variant (reference :668-768).  With `indexIn` (the embedding backbones) every reverse
         step also advances the degree-guided graph of :706-729 on the device (gdmcf_graph_guided_step_u8: classes drawn
         from the accumulated graph's transition rows, one bit per user drawn from its relative degree, AND-ed when
@@ -488,64 +497,24 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         self.last_reverse_route = "latent" if latent else "item"
         from .cat import DNNCat
         from .data_utils import CsrBatch
-        csr_batch = None
-        cat_csr = False  # DNNCat keeps CSR rows on the latent route only (its item-space loop takes dense rows)
-        if isinstance(x_start, CsrBatch):
-            if self._sparse_reverse_ok(model, x_start, steps):
-                csr_batch = x_start
-            elif latent and type(model) is DNNCat and steps == 0 and x_start.csr.values is None:
-                csr_batch, cat_csr = x_start, True
-            else:
-                x_start = x_start.dense()
+        # (DNNCat keeps CSR rows on the latent route only: its item-space loop takes dense rows)
+        if isinstance(x_start, CsrBatch) and not (self._sparse_reverse_ok(model, x_start, steps) or (
+                latent and type(model) is DNNCat and steps == 0 and x_start.csr.values is None)):
+            x_start = x_start.dense()
+        if latent:
+            return self._latent_sample(model, x_start, steps, index, noise0=noise0, sampled0=sampled0, graph_sampled=graph_sampled,
+                                       graph_pick=graph_pick)
         B, dev = x_start.shape[0], x_start.device
         with torch.no_grad():
-            if cat_csr:
-                x0, x_tU, keep, x_t = None, None, None, csr_batch  # xU0 = 1 - x, xU1 = x: CatEngine.latent_loop needs no image
-            elif csr_batch is not None:
-                # rows left sparse (steps == 0): neither the [B, 2I] image nor the second branch's input is built -- a handle
-                # carries that branch's step-independent pre-activation, gathered once; the first step's x_t is the rows themselves
-                x0 = None
-                x_tU, keep = model.engine.onehot_rows_sparse(csr_batch), None
-                x_t = csr_batch
-            elif steps == 0:
-                x0 = x_start.float().contiguous()
-                # the noiseless one-hot image: every true bit survives (sampled == the rows themselves)
-                x_tU, keep = model.engine.onehot_rows(x0, None, (x0 != 0).to(torch.uint8), self.discrete)
-                x_t = x0
-            else:
-                x0 = x_start.float().contiguous()
-                t = torch.full((B,), steps - 1, dtype=torch.int64, device=dev)
-                x_tU, keep = model.engine.onehot_rows(x0, t, sampled0, self.discrete)
-                x_t = self.q_sample(x0, t, noise0) if self.noise_scale != 0.0 else x0
-            graph = degp = None
-            if self.indexIn and self.noise_scale != 0.0:
-                graph = torch.zeros(B, x_start.shape[1], dtype=torch.uint8, device=dev)
-                if csr_batch is not None:  # binary rows: the row sums are the row lengths, exact in float32 either way
-                    ip = csr_batch.csr.indptr
-                    deg = (ip[csr_batch.row_ids + 1] - ip[csr_batch.row_ids]).to(torch.float32)
-                else:
-                    deg = x0.sum(dim=1)
-                degp = (deg / deg.max()).float().contiguous()  # :710-711 (a batch without any interaction gives nan, as there)
+            x_t, x_tU, keep, graph, degp, _ = self._reverse_inputs(model, x_start, steps, noise0, sampled0)
             eps_mode = self.mean_type == ModelMeanType.EPSILON
             if self.mean_type not in (ModelMeanType.START_X, ModelMeanType.EPSILON):
                 raise NotImplementedError(self.mean_type)
             # per-step coefficient vectors [T, B] of the fused posterior epilogue (reference :451-471, :495-498), once
-            tabs = {k: self._t32[k][: self.steps, None].expand(self.steps, B).contiguous() for k in ("c1", "c2", "r1", "r2", "sigma")} \
-                if self.noise_scale != 0.0 else None
+            names = ("c1", "c2") + (("r1", "r2") if eps_mode else ()) + (("sigma",) if sampling_noise else ())
+            tabs = step_tables(self._t32, self.steps, B, names, self._step_tabs) if self.noise_scale != 0.0 else None
             # models of this package fuse the posterior into their output GEMM (`posterior=` of their forward); anything
             # else with the reference's call signature takes the element-wise path below
-            if latent:
-                def before_step(n, i):
-                    if graph is not None:
-                        self._graph_step(graph, torch.full((B,), i, dtype=torch.int64, device=dev), degp,
-                                         None if graph_sampled is None else graph_sampled[n],
-                                         None if graph_pick is None else graph_pick[n])
-                kw = dict(eps=self._eps_tables()) if eps_mode else {}
-                x_0 = model.engine.latent_loop(x_t, x_tU, self.steps, tabs["c1"], tabs["c2"],
-                                               index=index if self.indexIn else None, before_step=before_step, **kw)
-                del keep
-                self.last_graph = graph
-                return x_0
             import inspect
             try:
                 fused_posterior = "posterior" in inspect.signature(getattr(model, "forward", model)).parameters
@@ -600,6 +569,64 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
             del keep
             self.last_graph = graph
             return x_t
+
+    def _reverse_inputs(self, model, x, steps, noise0=None, sampled0=None, graph_sampled=None, graph_pick=None):
+        """What a reverse loop of the one-hot variant starts from, for both routes: (x_t, x_tU, keep, graph, degp, before_step).
+        x: dense [B, I] rows, or a data_utils.CsrBatch the caller keeps sparse (steps == 0, binary rows) -- then x_t is the rows
+        themselves and neither the [B, 2I] image nor the second branch's input is built: x_tU is a handle with that branch's
+        step-independent pre-activation, gathered once (DNNCat: None -- xU0 = 1 - x, xU1 = x, CatEngine.latent_loop needs no image).
+        Dense rows: the noiseless image with steps == 0 (every true bit survives: sampled == the rows themselves), else the class
+        draws (or sampled0) and q_sample (noise0) at steps - 1.  keep: what the kernels read, to keep referenced.
+        graph, degp (with `indexIn`, else None): the zeroed degree-guided graph and the users' relative degrees (:710-711; a batch
+        without any interaction gives nan, as there) -- row lengths on CSR rows, row sums on dense ones, exact in float32 either
+        way.  before_step(n, i): the graph update ahead of step n (timestep i) as the latent loop calls it."""
+        from .cat import DNNCat
+        from .data_utils import CsrBatch
+        eng = model.engine
+        B, dev = x.shape[0], x.device
+        if isinstance(x, CsrBatch):
+            x0, x_t, keep = None, x, None
+            x_tU = None if type(model) is DNNCat else eng.onehot_rows_sparse(x)
+        else:
+            x0 = x.float().contiguous()
+            if steps == 0:
+                x_tU, keep = eng.onehot_rows(x0, None, (x0 != 0).to(torch.uint8), self.discrete)
+                x_t = x0
+            else:
+                t = torch.full((B,), steps - 1, dtype=torch.int64, device=dev)
+                x_tU, keep = eng.onehot_rows(x0, t, sampled0, self.discrete)
+                x_t = self.q_sample(x0, t, noise0) if self.noise_scale != 0.0 else x0
+        graph = degp = None
+        if self.indexIn and self.noise_scale != 0.0:
+            graph = torch.zeros(B, x.shape[1], dtype=torch.uint8, device=dev)
+            if x0 is None:
+                ip = x.csr.indptr
+                deg = (ip[x.row_ids + 1] - ip[x.row_ids]).to(torch.float32)
+            else:
+                deg = x0.sum(dim=1)
+            degp = (deg / deg.max()).float().contiguous()
+
+        def before_step(n, i):
+            if graph is not None:
+                self._graph_step(graph, torch.full((B,), i, dtype=torch.int64, device=dev), degp,
+                                 None if graph_sampled is None else graph_sampled[n], None if graph_pick is None else graph_pick[n])
+
+        return x_t, x_tU, keep, graph, degp, before_step
+
+    def _latent_sample(self, model, x, steps, index=None, stop=False, **draws):
+        """GaussianDiffusion._latent_sample for the one-hot variant: the engine's latent_loop on _reverse_inputs(**draws: noise0,
+        sampled0, graph_sampled, graph_pick), `last_graph` kept."""
+        if not self.CatOneHot:
+            return super()._latent_sample(model, x, steps, index, stop, **draws)
+        model = self._onehot_model(model)
+        with torch.no_grad():
+            x_t, x_tU, keep, graph, _, before_step = self._reverse_inputs(model, x, steps, **draws)
+            eps = self._eps_tables() if self.mean_type == ModelMeanType.EPSILON else None
+            res = model.engine.latent_loop(x_t, x_tU, self.steps, self._t32, index=index if self.indexIn else None,
+                                           before_step=before_step, stop=stop, eps=eps)
+            del keep
+            self.last_graph = graph
+            return res
 
     def _graph_step(self, graph, t, degp, sampled=None, pick=None, sampled_out=None, pick_out=None):
         """graph |= s & (user_guided ? pick : 1) for one reverse step (reference :709-727), in place, on the device."""

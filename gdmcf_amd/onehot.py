@@ -444,21 +444,19 @@ class OneHotEngine(EngineBase):
         bufs.hcat = t
 
     @with_precision
-    def latent_loop(self, x_T, x_U, T, c1, c2, index=None, before_step=None, _stop=False, eps=None):
+    def latent_loop(self, x_T, x_U, T, tabs32, index=None, before_step=None, stop=False, eps=None):
         """The whole reverse loop with x_t carried as p_t = W1x x_t, the first layer of branch 1 without its time columns
-        (DenoiserEngine._latent_loop has the algebra): per step one gdmcf_latent_step_f32 with A = the activation behind
+        (EngineBase._latent_reverse has the algebra and the loop): per step one step kernel with A = the activation behind
         [h | h_U] that feeds the last product and M = W1x . W_out (an embedding backbone: W1x . V^), plus the small layers.
         Branch 2 sees the same image at every step: its first layer's pre-activation without time columns and bias is taken
         ONCE per call -- from the SparseXU handle, or one product on the dense image -- and re-enters every step through
         gdmcf_gather_fwd_f32 with that step's row of the time table as the bias.  Item-wide work per call: branch 1's first layer
-        on x_T (a gather on CSR rows), branch 2's once, and the last product, x_0 = c1[0] (W_out a_0 + b_out).
-        x_T: dense [B, I] rows or a data_utils.CsrBatch of binary rows; x_U: the [B, 2I] image or a SparseXU; c1, c2: [T, B]
-        tables; before_step(n, i): called ahead of step n (timestep i), e.g. the degree-guided graph update.
-        _stop (gdmcf_amd.recommend): return (A, second, K, b_out), the operands of the last product, without running it; on CSR
-        rows no builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had.
-        eps (engine_core.EpsTables; p_sample(latent="extended")): the EPSILON target, as in DenoiserEngine._latent_loop -- c1, c2
-        are ignored for the tables (-d, g), the step kernel also keeps Q, and x_0 = G x_T - D (second Q^ + b_out) comes from the
-        posterior epilogue in its eps form on the dense x_T; with _stop the loop returns (-Q^, second, K, -b_out, G, D)."""
+        on x_T (a gather on CSR rows), branch 2's once, and the last product.
+        x_T: dense [B, I] rows or a data_utils.CsrBatch of binary rows; x_U: the [B, 2I] image or a SparseXU; tabs32: the
+        schedule's float32 tables [T]; before_step(n, i): called ahead of step n (timestep i), e.g. the degree-guided graph update.
+        stop (gdmcf_amd.recommend): return the engine_core.LatentProduct of the last product without running it; on CSR rows no
+        builder runs then (nothing reads a dense x_T) -- the Philox position advances as if it had.
+        eps (engine_core.EpsTables; p_sample(latent="extended")): the EPSILON target."""
         from .data_utils import CsrBatch
         lib, st, I = self.lib, _lib.stream_ptr(), self.I
         B, dev = x_T.shape[0], x_T.device
@@ -478,31 +476,24 @@ class OneHotEngine(EngineBase):
         ops = self._latent_operands(w1, b1, second, K, b_out, T, (w1, b1, w2, b2, m.emb_layer.weight, m.emb_layer.bias) + behind,
                                     tables=[(w2, b2, 2 * I)])
         e2 = ops.tabs[0][0]
+        tabs = core.step_tables(tabs32, T, B, ("c1", "c2"), bufs.tab_cache)
         if getattr(bufs, "lat_p", None) is None:
             f32 = dict(dtype=torch.float32, device=dev)
             bufs.lat_p = torch.zeros(B, _ceil64(hf1), **f32)
             bufs.lat_hcat = torch.zeros_like(bufs.hcat)
             bufs.lat_P2 = torch.zeros(B, _ceil64(hf2), **f32)
         p = bufs.lat_p
-        if eps is not None:
-            et = eps.on(dev, B)
-            c1, c2 = et["neg_d"], et["g"]
-            if getattr(bufs, "lat_q", None) is None:
-                bufs.lat_q = torch.zeros(B, _ceil64(K), dtype=torch.float32, device=dev)
-            Q = bufs.lat_q
-        # p_T and the x_t operand of the last product (x0 target: c2[0] == 0, it only has to be finite; eps: it carries G x_T)
-        if isinstance(x_T, CsrBatch) and _stop:
-            self.offset += 1  # (where the builder would have drawn)
+        # p_T and the dense x_T of the last product's epilogue
+        if isinstance(x_T, CsrBatch):
             keep = xdense = None
-            core.gather_fwd(lib, None, None, x_T, self._transposed(w1), I, None, None, 0, None, 0, B, hf1, p, st)
-        elif isinstance(x_T, CsrBatch):
-            if bufs.x0bits is None:
-                bufs.x0bits = torch.zeros(B, (I + 31) // 32, dtype=torch.int32, device=dev)
-            self.offset += 1
-            ts = torch.full((B,), T - 1, dtype=torch.int64, device=dev)
-            keep = core.prep_input_csr(lib, x_T, ts, None, None, None, None, float(m.drop.p), False, self.seed, self.offset,
-                                       m.emb_layer, self.E, bufs.xin1, bufs.temb, bufs.x0bits, st)
-            xdense = bufs.xin1
+            self.offset += 1  # (the builder's draw, whether it runs or not)
+            if not stop:
+                if bufs.x0bits is None:
+                    bufs.x0bits = torch.zeros(B, (I + 31) // 32, dtype=torch.int32, device=dev)
+                ts = torch.full((B,), T - 1, dtype=torch.int64, device=dev)
+                keep = core.prep_input_csr(lib, x_T, ts, None, None, None, None, float(m.drop.p), False, self.seed, self.offset,
+                                           m.emb_layer, self.E, bufs.xin1, bufs.temb, bufs.x0bits, st)
+                xdense = bufs.xin1
             core.gather_fwd(lib, None, None, x_T, self._transposed(w1), I, None, None, 0, None, 0, B, hf1, p, st)
         else:
             keep = xdense = core._f32_rows(x_T)
@@ -521,45 +512,24 @@ class OneHotEngine(EngineBase):
         # step's h into the buffer it is not reading A from
         pair = (bufs.hcat, bufs.lat_hcat)
         ld = bufs.hcat.stride(0)
-        first = (lambda t: t) if len(br1) == 1 else (lambda t: bufs.acts1[0])  # where the first activation of branch 1 lives
-        x0 = None
+
+        def small(n, i, h):
+            cur = pair[n % 2]
+            self._set_hcat(bufs, cur)
+            hcat2 = (cur.data_ptr() + 4 * bufs.h1, ld)
+            if len(br1) > 1:
+                self._chain_forward(bufs, br1[1:], bufs.acts1[1:], bufs.acts1[0], B, cur)
+            o2 = bufs.acts2[0] if len(br2) > 1 else hcat2
+            core.gather_fwd(lib, P2, None, None, None, I, None, None, 0, e2[i], act2, B, hf2, o2, st)
+            self._chain_forward(bufs, br2[1:], bufs.acts2[1:], o2, B, hcat2)
+            return self._latent_A(bufs, out, B, index)
+
         try:
-            core.gather_fwd(lib, p, None, None, None, I, None, None, 0, ops.e[T - 1], act1, B, hf1, first(pair[0]), st)
-            for n, i in enumerate(range(T - 1, -1, -1)):
-                if before_step is not None:
-                    before_step(n, i)
-                cur, nxt = pair[n % 2], pair[(n + 1) % 2]
-                self._set_hcat(bufs, cur)
-                hcat2 = (cur.data_ptr() + 4 * bufs.h1, ld)
-                if len(br1) > 1:
-                    self._chain_forward(bufs, br1[1:], bufs.acts1[1:], bufs.acts1[0], B, cur)
-                o2 = bufs.acts2[0] if len(br2) > 1 else hcat2
-                core.gather_fwd(lib, P2, None, None, None, I, None, None, 0, e2[i], act2, B, hf2, o2, st)
-                self._chain_forward(bufs, br2[1:], bufs.acts2[1:], o2, B, hcat2)
-                A = self._latent_A(bufs, out, B, index)
-                if i == 0 and eps is not None:
-                    if _stop:  # the sign goes into the last accumulation: -Q^ beside the cached -b_out
-                        core.latent_acc(lib, Q, et["qa0_neg"], A, et["qb0_neg"], B, K, Q, st)
-                        x0 = (Q, second, K, ops.neg_b, et["G"], et["D"])
-                    else:
-                        core.latent_acc(lib, Q, et["qa"][0], A, et["qb"][0], B, K, Q, st)
-                        x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
-                        core.posterior_fwd(lib, Q, second, b_out, xdense, et["one"], et["zero"], et["G"], et["D"], None, None, B, I, K,
-                                           x0, None, st)
-                elif i == 0 and _stop:
-                    x0 = (A, second, K, b_out)
-                elif i == 0:
-                    x0 = torch.empty(B, I, dtype=torch.float32, device=dev)
-                    core.posterior_fwd(lib, A, second, b_out, xdense, c1[0], c2[0], None, None, None, None, B, I, K, x0, None, st)
-                elif eps is not None:
-                    core.latent_step_ex(lib, A, ops.M, ops.v, p, c1[i], c2[i], None, ops.e[i - 1], act1, B, hf1, K, p, first(nxt),
-                                        (Q, et["qa"][i], et["qb"][i], Q), st)
-                else:
-                    core.latent_step(lib, A, ops.M, ops.v, p, c1[i], c2[i], ops.e[i - 1], act1, B, hf1, K, p, first(nxt), st)
+            return self._latent_reverse(bufs, ops, T, B, K, act1, p, p, pair if len(br1) == 1 else (bufs.acts1[0],) * 2, small, ops.e,
+                                        tabs["c1"], tabs["c2"], second, b_out, xdense, stop=stop, eps=eps, before_step=before_step)
         finally:
             self._set_hcat(bufs, pair[0])
-        del keep
-        return x0
+            del keep
 
 
 class DNNOneHot(nn.Module):

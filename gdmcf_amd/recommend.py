@@ -8,7 +8,7 @@ import torch
 
 from . import _lib
 from . import engine_core as core
-from .data_utils import CsrBatch, DeviceCSR
+from .data_utils import DeviceCSR
 
 
 def _c1_0_positive(diffusion):
@@ -51,62 +51,6 @@ def route_of(diffusion, model, rows, sampling_steps=0, sampling_noise=False, ext
     if eps:
         return "latent-csr" if binary and masks is not None and any(m is rows for m in masks) else "latent"
     return "latent-csr" if binary else "latent"
-
-
-def _step_tables(diffusion, B, cache):
-    """[T, B] float32 tables of posterior_mean_coef1 / 2, one pair per batch size of the call."""
-    if B not in cache:
-        T = diffusion.steps
-        cache[B] = tuple(diffusion._t32[k][:T, None].expand(T, B).contiguous() for k in ("c1", "c2"))
-    return cache[B]
-
-
-def _latent_operands(diffusion, model, x, steps, index, tabs, noise0=None, sampled0=None, eps=None, stop=True):
-    """The latent reverse loop on `x` (a CsrBatch of binary rows with steps == 0, or dense rows), ended before its last product:
-    (A, second, K, b_out).  The one-hot variants' inputs and the degree-guided graph of an `indexIn` loop are built as
-    GaussianDiffusionDiscrete.p_sample(latent=True) builds them: same draws, same `last_graph`.
-    eps (engine_core.EpsTables): the EPSILON target -- (-Q^, second, K, -b_out, G, D).  stop=False: the loop's x_0 instead."""
-    eng = model.engine
-    ekw = dict(eps=eps) if eps is not None else {}
-    if not diffusion.CatOneHot:
-        return eng.p_sample_loop(x, steps, diffusion.steps, diffusion._t32, eps is not None, False, noise0=noise0, latent=True,
-                                 _stop=stop, **ekw)
-    model = diffusion._onehot_model(model)
-    from .cat import DNNCat
-    cat = type(model) is DNNCat
-    B, dev = x.shape[0], x.device
-    c1, c2 = tabs
-    deg = None
-    if isinstance(x, CsrBatch):
-        x_tU, keep, x_t = (None if cat else eng.onehot_rows_sparse(x)), None, x
-        if diffusion.indexIn:
-            ip = x.csr.indptr
-            deg = (ip[x.row_ids + 1] - ip[x.row_ids]).to(torch.float32)
-    else:
-        x0 = x.float().contiguous()
-        if steps == 0:
-            x_tU, keep = eng.onehot_rows(x0, None, (x0 != 0).to(torch.uint8), diffusion.discrete)
-            x_t = x0
-        else:
-            t = torch.full((B,), steps - 1, dtype=torch.int64, device=dev)
-            x_tU, keep = eng.onehot_rows(x0, t, sampled0, diffusion.discrete)
-            x_t = diffusion.q_sample(x0, t, noise0)
-        if diffusion.indexIn:
-            deg = x0.sum(dim=1)
-    graph = degp = None
-    if deg is not None:
-        graph = torch.zeros(B, x.shape[1], dtype=torch.uint8, device=dev)
-        degp = (deg / deg.max()).float().contiguous()
-
-    def before_step(n, i):
-        if graph is not None:
-            diffusion._graph_step(graph, torch.full((B,), i, dtype=torch.int64, device=dev), degp, None, None)
-
-    ops = eng.latent_loop(x_t, x_tU, diffusion.steps, c1, c2, index=index if diffusion.indexIn else None,
-                          before_step=before_step, _stop=stop, **ekw)
-    del keep
-    diffusion.last_graph = graph
-    return ops
 
 
 def _as_mask(mask, rows):
@@ -167,7 +111,9 @@ def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_step
     route = route_of(diffusion, model, rows, sampling_steps, sampling_noise, extended=extended, masks=masks)
     diffusion.last_recommend_route = route
     from .gaussian_diffusion import ModelMeanType
-    eps = diffusion._eps_tables() if route != "item" and diffusion.mean_type == ModelMeanType.EPSILON else None
+    # the EPSILON target's x_0 = G x_T + D (second (-Q^) + (-b_out)): where G x_T lies on masked items only ("latent-csr") the bracket
+    # is ranked like the x0 target's last product; on "latent" x_0 itself comes from the posterior epilogue on dense rows
+    stop = route == "latent-csr" or diffusion.mean_type != ModelMeanType.EPSILON
     idx = torch.empty(n, k, dtype=torch.int64, device=dev)
     val = torch.empty(n, k, dtype=torch.float32, device=dev) if return_values else None
     if n == 0:
@@ -175,7 +121,6 @@ def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_step
     lib, eng = _lib.load(), model.engine
     ip1, ix1 = (masks[0].indptr, masks[0].indices) if masks else (None, None)
     ip2, ix2 = (masks[1].indptr, masks[1].indices) if len(masks) > 1 else (None, None)
-    tabs = {}
     for lo in range(0, n, batch_size):
         chunk = ids[lo:lo + batch_size]
         B = chunk.numel()
@@ -187,19 +132,11 @@ def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_step
             scores = core._f32_rows(diffusion.p_sample(model, rows.rows(chunk), sampling_steps, sampling_noise, **kw))
         else:
             x = rows.batch(chunk) if route == "latent-csr" else rows.rows(chunk)
-            c1, c2 = _step_tables(diffusion, B, tabs)
-            with torch.no_grad():
-                if eps is None:
-                    A, second, K, b_out = _latent_operands(diffusion, model, x, sampling_steps, index, (c1, c2), **inj)
-                    scores = eng.score_product(A, second, K, b_out, B, dev)
-                    scale = c1[0]
-                elif route == "latent-csr":
-                    # x_0 = G x_T + D (second (-Q^) + (-b_out)); G x_T lies on masked items only: rank the bracket, scale by D
-                    nQ, second, K, nb, _, D = _latent_operands(diffusion, model, x, sampling_steps, index, (c1, c2), eps=eps, **inj)
-                    scores = eng.score_product(nQ, second, K, nb, B, dev)
-                    scale = D
-                else:
-                    scores = _latent_operands(diffusion, model, x, sampling_steps, index, (c1, c2), eps=eps, stop=False, **inj)
+            res = diffusion._latent_sample(model, x, sampling_steps, index, stop=stop, **inj)  # (as p_sample(latent=...) runs it)
+            if stop:  # the last product's raw scores are ranked, the k returned values scaled
+                scores, scale = eng.score_product(res.A, res.second, res.K, res.bias, B, dev), res.scale
+            else:
+                scores = res
             diffusion.last_reverse_route = "latent"
         v = val[lo:lo + B] if val is not None else None
         _lib.check(lib.gdmcf_topk_masked_rows_f32(

@@ -318,6 +318,34 @@ def test_latent_csr_route_launches_no_builder_no_posterior_and_one_item_wide_pro
     assert names.count("latent_step") == (T - 1) * n_batches
 
 
+def test_recommend_draws_the_graph_and_moves_the_counters_as_latent_p_sample():
+    """recommend's docstring promise for an `indexIn` loop -- same draws, same `last_graph` as p_sample(latent=True) -- from the same
+    engine offset and noise counter: on CSR rows ("latent-csr") and, with injected draws of x_T, on dense rows ("latent")."""
+    I, U, T = 131, 10, 3
+    torch.manual_seed(5)
+    model = gdmcf_amd.DNNOneHotEmbedding([I, 24], [24, I], 10, item_num=I, user_num=U).to(DEV).eval()
+    diff = _discrete(dict(mean_type="x0", scale=0.01, nmin=0.001, nmax=0.01, T=T, discrete=0.99), index_in=True)
+    dcsr = DeviceCSR(sp.csr_matrix(_rows(U, I, 7).numpy().astype(np.float64)), DEV)
+    ids = cu(torch.randperm(U, generator=torch.Generator().manual_seed(2)))
+    noise0, sampled0 = _draws(U, I)
+    eng = model.engine
+
+    def run(call):
+        eng.offset, diff._noise_calls, diff.last_graph = 1000, 0, None
+        call()
+        return diff.last_graph.clone(), eng.offset - 1000, diff._noise_calls
+
+    for steps, route, inj in ((0, "latent-csr", {}), (2, "latent", dict(noise0=cu(noise0), sampled0=cu(sampled0)))):
+        rows = dcsr.batch(ids) if steps == 0 else dcsr.rows(ids)
+        g_p, off_p, calls_p = run(lambda: diff.p_sample(model, rows, steps, False, index=ids, latent=True, **inj))
+        assert diff.last_reverse_route == "latent"
+        g_r, off_r, calls_r = run(lambda: recommend(diff, model, dcsr, ids, 5, batch_size=U, sampling_steps=steps, **inj))
+        assert diff.last_recommend_route == route
+        print(f"steps={steps}: graph bits {int(g_p.sum())} / {int(g_r.sum())}, offset +{off_p} / +{off_r}, noise calls {calls_p} / {calls_r}")
+        assert bool(g_p.any()) and torch.equal(g_p, g_r)
+        assert off_p == off_r and calls_p == calls_r == T
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # chunking and ids
 # ---------------------------------------------------------------------------------------------------------------------

@@ -63,9 +63,9 @@ def test_keyword_defaults():
         assert sig[name].kind is inspect.Parameter.KEYWORD_ONLY
     from gdmcf_amd.engine import DenoiserEngine
     from gdmcf_amd.onehot import OneHotEngine
-    assert inspect.signature(DenoiserEngine.p_sample_loop).parameters["_stop"].default is False
+    assert inspect.signature(DenoiserEngine.p_sample_loop).parameters["stop"].default is False
     assert inspect.signature(DenoiserEngine._latent_loop).parameters["stop"].default is False
-    assert inspect.signature(OneHotEngine.latent_loop).parameters["_stop"].default is False
+    assert inspect.signature(OneHotEngine.latent_loop).parameters["stop"].default is False
 
 
 def _diff(mean_type=ModelMeanType.START_X, scale=0.01, schedule="linear-var"):
