@@ -48,7 +48,7 @@ def train_one_epoch(diffusion, model, optimizer, train_csr, batch_size, device, 
 
 @torch.no_grad()
 def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps, sampling_noise, batch_size,
-             device, sparse=False, latent=False, recommend=False):
+             device, sparse=False, latent=False, recommend=False, candidates=None):
     """Precision / Recall / NDCG / MRR @topN exactly as reference main.py:267-310.
 
     data_csr: rows fed to p_sample (the reference feeds the training rows); data_te: ground-truth CSR;
@@ -59,7 +59,11 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
     (the EPSILON target and DNNCat too), also to gdmcf_amd.recommend with recommend=True.
     recommend=True: each batch's list comes from gdmcf_amd.recommend with mask_his as a DeviceCSR -- uploaded once
     per call, or passed through when it already is one -- so no batch slices a matrix on the host; `sparse` is then ignored and
-    of `latent` only the value "extended" matters (recommend picks its own route, `diffusion.last_recommend_route`)."""
+    of `latent` only the value "extended" matters (recommend picks its own route, `diffusion.last_recommend_route`).
+    candidates (with recommend=True only): [n_users, C], row u the items user u is ranked within (gdmcf_amd.recommend's
+    `candidates`: a retriever's output, an allow-list, the sampled-negatives protocol's one held-out item among sampled ones)."""
+    if candidates is not None and not recommend:
+        raise ValueError("driver.evaluate: candidates needs recommend=True")
     model.eval()
     n = mask_his.shape[0]
     predict_items = []
@@ -69,7 +73,8 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
         mask = mask_his if isinstance(mask_his, DeviceCSR) else DeviceCSR(mask_his, device)
         lists = recommend_fn(diffusion, model, dcsr, np.arange(n), topN[-1], mask=mask, sampling_steps=sampling_steps,
                              sampling_noise=sampling_noise, batch_size=batch_size,  # (the same batches, made inside)
-                             **(dict(latent="extended") if isinstance(latent, str) and latent == "extended" else {}))
+                             **(dict(latent="extended") if isinstance(latent, str) and latent == "extended" else {}),
+                             **(dict(candidates=candidates) if candidates is not None else {}))
         return evaluate_utils.computeTopNAccuracy_device(data_te, lists, topN)
     for lo in range(0, n, batch_size):
         rows = np.arange(lo, min(lo + batch_size, n))

@@ -202,6 +202,22 @@ def latent_acc(lib, q_cur, qa, A, qb, B, K, q_next, st):
     _lib.check(lib.gdmcf_latent_acc_f32(qc, ldqc, qa.data_ptr(), a, lda, qb.data_ptr(), B, K, qn, ldqn, st))
 
 
+def cand_scores(lib, A, W, I, K, bias, scale, cand, ldcand, B, C, mask_ptrs, rows, out, st):
+    """gdmcf_cand_scores_f32: out[b, c] = (A[b, :K] . W[cand[b, c], :K] + bias[cand[b, c]]) * scale[b], -inf for a candidate
+    outside [0, I) or in row rows[b] of the mask CSRs.  mask_ptrs: (indptr, indices, indptr2, indices2) device pointers or
+    None; cand int64 [B, ldcand] (ldcand 0: one list [C])."""
+    (a, lda), (w, ldw), (o, ldo) = _pl(A), _pl(W), _pl(out)
+    _lib.check(lib.gdmcf_cand_scores_f32(a, lda, w, ldw, I, K, _lib.ptr(bias), _lib.ptr(scale), cand.data_ptr(), ldcand, B, C,
+                                         *mask_ptrs, _lib.ptr(rows), o, ldo, st))
+
+
+def cand_pick(lib, dense, B, I, scale, cand, ldcand, C, mask_ptrs, rows, out, st):
+    """gdmcf_cand_pick_f32: out[b, c] = dense[b, cand[b, c]] * scale[b] under cand_scores' contract."""
+    (d, ldd), (o, ldo) = _pl(dense), _pl(out)
+    _lib.check(lib.gdmcf_cand_pick_f32(d, ldd, B, I, _lib.ptr(scale), cand.data_ptr(), ldcand, C, *mask_ptrs, _lib.ptr(rows), o,
+                                       ldo, st))
+
+
 def step_tables(tabs32, T, B, names, cache=None):
     """{name: [T, B] float32} of the per-timestep tables `names` of tabs32 (those it holds): row t is the per-row coefficient
     vector of step t as the kernels read it, expanded once instead of per step.  cache: a dict that keeps the last expansion

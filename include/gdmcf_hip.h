@@ -506,6 +506,30 @@ int gdmcf_topk_masked_rows_f32(const float* pred, int64_t ldp, int B, int I, con
                                const int64_t* indptr2, const int32_t* indices2, const int64_t* rows, const float* scale, int k,
                                int64_t* idx_out, float* val_out, void* stream);
 
+/* ---- candidate lists: score only the items a caller names (gdmcf_amd.score_candidates, recommend(candidates=)) -----------
+ * The gathered product: out[b, c] = (dot(A[b, :K], W[cand[b, c], :K]) + bias[cand[b, c]]) * scale[b] for b < B, c < C -- the
+ * last product of a latent reverse loop (engine_core.LatentProduct) on the rows of W a list names, instead of all I of them.
+ * A [B, lda >= K]; W [I, ldw >= K], rows K-contiguous; bias [I] or NULL; scale float32 [B] or NULL (no multiplication);
+ * cand int64 [B, ldcand >= C], or ldcand == 0: one list [C] shared by all rows; out [B, ldo >= C].  1 <= K <= 4096, any
+ * B >= 1, C >= 1 (GDMCF_E_SHAPE otherwise).  Mask arguments as gdmcf_topk_masked_rows_f32's (indptr / indices, optional
+ * indptr2 / indices2, rows or NULL = rows 0..B-1): a candidate that occurs in row rows[b] of either CSR gets -inf; the rows
+ * may be unsorted and hold repeats and out-of-range entries.  A candidate outside [0, I) -- -1, any huge value: the padding of
+ * a ragged list -- gets -inf too; for neither kind is a row of W or an element of bias read.  Duplicates are each scored.
+ * Summation order, fixed: lane l of a wave adds the products of k = 256 j + 4 l .. + 3 (j ascending, so k ascending) into
+ * one accumulator by fma from +0; the 64 accumulators are added in a butterfly over the lane distances 32, 16, 8, 4, 2, 1,
+ * x(l) + x(l ^ m) at every level; then (sum + bias) * scale.  The bits of (b, item) depend on neither the item's place in
+ * the list, nor C, nor ldcand, nor the run.  No atomics, no workspace, no host synchronisation.                          */
+int gdmcf_cand_scores_f32(const float* A, int64_t lda, const float* W, int64_t ldw, int I, int K, const float* bias,
+                          const float* scale, const int64_t* cand, int64_t ldcand, int B, int C, const int64_t* indptr,
+                          const int32_t* indices, const int64_t* indptr2, const int32_t* indices2, const int64_t* rows, float* out,
+                          int64_t ldo, void* stream);
+/* The same contract with the score taken from a dense matrix: out[b, c] = dense[b, cand[b, c]] * scale[b] (dense [B, ldd >= I];
+ * one float32 multiplication per element, none with scale == NULL), -inf for masked and out-of-range candidates, which are not
+ * read.  For every route that already holds [B, I] scores.                                                              */
+int gdmcf_cand_pick_f32(const float* dense, int64_t ldd, int B, int I, const float* scale, const int64_t* cand, int64_t ldcand,
+                        int C, const int64_t* indptr, const int32_t* indices, const int64_t* indptr2, const int32_t* indices2,
+                        const int64_t* rows, float* out, int64_t ldo, void* stream);
+
 /* ---- LightGCN ranking: score product fused with the masked top-k (lightGCN.py:67-127, get_metrics) -----------
  * replaces `relevance_score = user_emb @ item_emb.T`, the dense -inf mask of the training interactions added to it and
  * `torch.topk(relevance_score, K)` (lightGCN.py:75-90) without the [n_rows, n_items] score matrix (nor the mask) ever being
