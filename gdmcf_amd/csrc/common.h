@@ -196,6 +196,12 @@ struct GdGemm {
 // Split count the register-streaming input-gradient kernel (csrc/gemm_dr_kn.hip: dr_kn_kernel) would use for C[M, N] = A[M, K] B[K, N],
 // or 0 when it does not take the product: gdmcf_linear_ws_bytes sizes the slab workspace with it.
 int gd_dr_kn_splits(int M, int N, int K);
+// The same for the first-layer forward C[M, N] = A[M, K] B[N, K]^T as split-K slabs on the fat-tile loop (csrc/gemm_dr_fat.hip:
+// dr_fat_kernel<NB, GD_EPI_SLAB, 1>): the split count, with the tile width NB (x 16 columns) and the chunks of 16 k per split, or 0
+// when the route does not take the shape (switched off, a CU count that is no multiple of 8, rows that do not tile by 80 within
+// 12 %, N < 128, K < 4096, more tiles than wave slots).  f32 products only: the caller asks in that mode.  The launcher and
+// gdmcf_linear_ws_bytes both plan with it.
+int gd_dr_fat_slab_plan(int M, int N, int K, int* nb, int* cps);
 extern thread_local int t_gd_last_gemm;  // gdmcf_debug_last_gemm (include/gdmcf_hip.h)
 
 // shape classes: 0 = "batch-M" (BM=80, BN=128), 1 = square 128x128, 2 = small 64x64,

@@ -12,6 +12,7 @@
 //   gemm_dr_tn.hip   dr_tn_kernel        [2]  weight gradient dW = dZ^T A: ring of registers, asm loads, ticket queues    GDMCF_DR_DW
 //                    dr_tn_adamw_kernel  [3]  the same with the AdamW update in the epilogue, up to four products per launch  GDMCF_DR_DW, _ADAMW
 //   gemm_dr_fat.hip  dr_fat_kernel       [4]  the output layer with a fused row-loss / posterior epilogue                 GDMCF_DR_FAT
+//                                        [6]  the same loop over a K range per task: the first-layer forward as split-K slabs  GDMCF_DR_FAT_SLAB
 //   gemm_dr_kn.hip   dr_kn_kernel        [5]  the input gradient and the cached-W^T forward as split-K slabs               GDMCF_DR_KN
 //   gemm_dr.hip      the switches, the CU count and gd_gemm_dr_launch: the common refusals and the (layA, layB, epi) dispatch
 //
@@ -43,6 +44,7 @@ struct DrRoutes {
     bool adamw;  // GDMCF_DR_ADAMW: the fused-AdamW ones among them (dr_tn_adamw_kernel)
     bool kn;     // GDMCF_DR_KN: the input gradient and the cached-W^T forward (dr_kn_kernel; also sizes the workspace)
     bool fat;    // GDMCF_DR_FAT: the output layer with the fused row-loss / posterior epilogue (dr_fat_kernel)
+    bool fat_slab;  // GDMCF_DR_FAT_SLAB: the first-layer forward as split-K slabs on dr_fat_kernel's LDS-DMA loop (also sizes the workspace)
 };
 DrRoutes& dr_routes();
 int dr_cu_count();  // compute units of the current device
@@ -52,3 +54,4 @@ int dr_stagger();   // GDMCF_DR_STAGGER (dr_tn_kernel, dr_tn_adamw_kernel)
 int gd_dr_tn_launch(GdGemm& g, hipStream_t s);            // gemm_dr_tn.hip: layouts MC / MC, GD_EPI_STORE
 int gd_dr_kn_launch(GdGemm& g, hipStream_t s);            // gemm_dr_kn.hip: layouts KC / MC, GD_EPI_SLAB
 int gd_dr_fat_launch(int epi, GdGemm& g, hipStream_t s);  // gemm_dr_fat.hip: layouts KC / KC, GD_EPI_LOSS or GD_EPI_POST
+int gd_dr_fat_slab_launch(GdGemm& g, hipStream_t s);      // gemm_dr_fat.hip: layouts KC / KC, GD_EPI_SLAB

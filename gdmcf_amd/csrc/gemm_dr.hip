@@ -14,12 +14,17 @@ int dr_cu_count() {
     return n_cu;
 }
 
-static bool dr_env_on(const char* name) {
+#ifndef GD_FAT_SLAB_DEFAULT
+#define GD_FAT_SLAB_DEFAULT 1  // GDMCF_DR_FAT_SLAB when the environment does not set it
+#endif
+
+static bool dr_env_on(const char* name, bool dflt = true) {
     const char* v = getenv(name);
-    return v == nullptr || atoi(v) != 0;
+    return v == nullptr ? dflt : atoi(v) != 0;
 }
 DrRoutes& dr_routes() {
-    static DrRoutes r = {dr_env_on("GDMCF_DR_DW"), dr_env_on("GDMCF_DR_ADAMW"), dr_env_on("GDMCF_DR_KN"), dr_env_on("GDMCF_DR_FAT")};
+    static DrRoutes r = {dr_env_on("GDMCF_DR_DW"), dr_env_on("GDMCF_DR_ADAMW"), dr_env_on("GDMCF_DR_KN"), dr_env_on("GDMCF_DR_FAT"),
+                         dr_env_on("GDMCF_DR_FAT_SLAB", GD_FAT_SLAB_DEFAULT != 0)};
     return r;
 }
 
@@ -31,7 +36,7 @@ int dr_stagger() {
 // Returns GD_DR_NOT_TAKEN when the product is not one these kernels handle (the caller falls back to the LDS-tiled kernels).
 int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
     if (g.bf16) return GD_DR_NOT_TAKEN;
-    if (g.accumulate || g.C16 || (g.splits > 1 && epi != GD_EPI_SLAB)) return GD_DR_NOT_TAKEN;  // (slabs: dr_kn_kernel sets its own split count)
+    if (g.accumulate || g.C16 || (g.splits > 1 && epi != GD_EPI_SLAB)) return GD_DR_NOT_TAKEN;  // (slabs: the kernels set their own split count)
     if (layA == GD_LAY_MC && layB == GD_LAY_MC) {
         if (epi == GD_EPI_ADAMW) return gd_gemm_dr_adamw_multi(&g, 1, s);  // the one-element case
         if (epi == GD_EPI_STORE) return gd_dr_tn_launch(g, s);
@@ -39,6 +44,7 @@ int gd_gemm_dr_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) {
         if (epi == GD_EPI_SLAB) return gd_dr_kn_launch(g, s);
     } else if (layA == GD_LAY_KC && layB == GD_LAY_KC) {
         if (epi == GD_EPI_LOSS || epi == GD_EPI_POST) return gd_dr_fat_launch(epi, g, s);
+        if (epi == GD_EPI_SLAB) return gd_dr_fat_slab_launch(g, s);
     }
     return GD_DR_NOT_TAKEN;
 }

@@ -1,5 +1,6 @@
-// dr_fat_kernel of gemm_dr.h -- the output layer with a fused row-loss / posterior epilogue as one fat tile per wave -- with its
-// launcher and its entry point gd_dr_fat_launch.
+// dr_fat_kernel of gemm_dr.h -- the output layer with a fused row-loss / posterior epilogue as one fat tile per wave, and the same loop
+// over a K range per task for the first-layer forward as split-K slabs -- with its launcher and its entry points gd_dr_fat_launch and
+// gd_dr_fat_slab_launch (plan: gd_dr_fat_slab_plan).
 #include <stdlib.h>
 
 #include "gemm_dr.h"
@@ -51,12 +52,17 @@ namespace {
 //     so their ds_reads have retired.  The last chunk's parked loads (range-checked: no fetch, zeros) still WRITE their image:
 //     a vmcnt(0) after the loop retires them before the epilogue stages rows in the same LDS, and the fill of the NEXT tile waits
 //     lgkmcnt(0) for the epilogue's last reads of that staging.
+//
+// EPI = GD_EPI_SLAB (GDMCF_DR_FAT_SLAB): the first-layer forward xin W1^T, a [batch x hidden] output over a LONG K.  A task is
+// (split, tile): the same chunk bodies over the chunks [c_lo, c_hi) of one split, the partial tile stored into slab `split` for
+// gd_splitk_reduce.  Everything slab-specific is behind `SLAB` and folds to the fused epilogues' constants otherwise.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int NB, int EPI, int DMA>
 __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
-    static_assert(EPI == GD_EPI_LOSS || EPI == GD_EPI_POST, "output layer with a fused epilogue");
+    static_assert(EPI == GD_EPI_LOSS || EPI == GD_EPI_POST || EPI == GD_EPI_SLAB, "output layer with a fused epilogue, or split-K slabs");
     static_assert(NB >= 4 && NB <= 12, "5 x NB accumulator blocks must fit 256 registers");
     static_assert(DMA == 0 || DMA == 1, "B through staging registers, or straight into LDS");
+    constexpr bool SLAB = EPI == GD_EPI_SLAB;
     typedef __attribute__((address_space(3))) void* lds_vp;
     constexpr int WAIT_VM0 = 0x0F70, WAIT_LGKM0 = 0xC07F;  // s_waitcnt vmcnt(0) / lgkmcnt(0), the other counters left alone
     constexpr int TMB = 5;
@@ -75,12 +81,20 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
     const __amdgpu_buffer_rsrc_t srdB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0, (int)(((int64_t)(g.N - 1) * g.ldb + g.K) * 4), 0x00020000);
     const int NCH = d.ksp;       // chunks of 16 k per tile: ceil(K / 16) -- the loop runs them in pairs, an odd last one alone
     const int c_mask = g.K >> 4;  // first chunk that reaches past K
+    const int ntasks = SLAB ? ntiles * g.splits : ntiles;  // slabs: a task is (split, tile), the tiles of one split on consecutive waves
     // LDS float offsets: write -- piece p = rows 16 p + (lane >> 2), slot lane & 3; read -- block b = rows 16 b + r, slot q
     // (DMA: the write lands lane-linear, row lane >> 2, slot lane & 3; the lane fetches the global slot g_slot that belongs there)
     const int w_off = (lane >> 2) * 16 + (((lane & 3) ^ ((((lane >> 2) >> 2) & 1) << 1)) << 2);
     const int g_slot = DMA ? ((lane & 3) ^ ((((lane >> 2) >> 2) & 1) << 1)) : (lane & 3);
     const int r_off = r * 16 + ((q ^ (((r >> 2) & 1) << 1)) << 2);
-    for (int tile = wl; tile < ntiles; tile += n_waves) {
+    for (int task = wl; task < ntasks; task += n_waves) {
+        // slabs: this task's chunks [c_lo, c_hi) of the reduction, the whole ones [c_lo, c_in); a chunk that reaches past K is the
+        // last split's last (c_hi > c_in).  The fused epilogues: one tile per task, every chunk.
+        const int split = SLAB ? task / ntiles : 0;
+        const int tile = SLAB ? task - split * ntiles : task;
+        const int c_lo = SLAB ? split * (g.kchunk >> 4) : 0;
+        const int c_hi = SLAB ? min(c_lo + (g.kchunk >> 4), NCH) : NCH;
+        const int c_in = SLAB ? min(c_hi, c_mask) : c_mask;
         const int tm = tile % d.tiles_m, tn = tile / d.tiles_m;
         const int m0 = tm * (16 * TMB), n0 = tn * (16 * NB);
         uint32_t offA[TMB], offB[NB];
@@ -96,13 +110,14 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
         f32x4 xa[2][TMB], G[DMA ? 1 : NB], FB[NB];
         // ---- fill: chunk 0 of A into xa[0], chunk 0 of B through LDS image 0 (DMA: into the registers and the image of parity hp,
         // see the loop) ----
-        const int hp = DMA ? (c_mask & 1) : 0;
+        const int hp = DMA ? ((c_in - c_lo) & 1) : 0;  // (slabs: the parity of this task's whole-chunk count)
+        const int k_lo = SLAB ? c_lo * 64 : 0;         // scalar byte offset of the task's first chunk
         if (hp) {
 #pragma unroll
-            for (int i = 0; i < TMB; ++i) xa[1][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdA, offA[i], 0, 0));
+            for (int i = 0; i < TMB; ++i) xa[1][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdA, offA[i], k_lo, 0));
         } else {
 #pragma unroll
-            for (int i = 0; i < TMB; ++i) xa[0][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdA, offA[i], 0, 0));
+            for (int i = 0; i < TMB; ++i) xa[0][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdA, offA[i], k_lo, 0));
         }
         if constexpr (DMA) {
             // (the previous tile's epilogue has read its row staging out of this LDS: those reads retire before a piece may land)
@@ -110,10 +125,10 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
             __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int p = 0; p < NB; ++p) __builtin_amdgcn_raw_ptr_buffer_load_lds(srdB, (lds_vp)(lds + hp * (NB * 256) + p * 256), 16, (int)offB[p], 0, 0, 0);
+            for (int p = 0; p < NB; ++p) __builtin_amdgcn_raw_ptr_buffer_load_lds(srdB, (lds_vp)(lds + hp * (NB * 256) + p * 256), 16, (int)offB[p], k_lo, 0, 0);
         } else {
 #pragma unroll
-            for (int p = 0; p < NB; ++p) G[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdB, offB[p], 0, 0));
+            for (int p = 0; p < NB; ++p) G[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdB, offB[p], k_lo, 0));
 #pragma unroll
             for (int p = 0; p < NB; ++p) *reinterpret_cast<f32x4*>(lds + p * 256 + w_off) = G[p];
         }
@@ -123,8 +138,8 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
         // retires everything the previous chunk issued -- the pieces of ITS image first of all -- before the first fragment read)
 #define GD_FAT_CHUNK(PAR, c, MSK)                                                                                         \
         {                                                                                                             \
-            /* scalar offset of the next chunk; past the last chunk it parks the loads outside both matrices (0, no fetch) */ \
-            const uint32_t kn = ((c) + 1 < NCH) ? (uint32_t)((c) + 1) * 64u : 0x80000000u;                            \
+            /* scalar offset of the next chunk; past the task's last chunk it parks the loads outside both matrices (0, no fetch) */ \
+            const uint32_t kn = ((c) + 1 < c_hi) ? (uint32_t)((c) + 1) * 64u : 0x80000000u;                           \
             if constexpr (DMA) {                                                                                      \
                 __builtin_amdgcn_sched_barrier(0);                                                                    \
                 __builtin_amdgcn_s_waitcnt(WAIT_VM0);                                                                 \
@@ -186,13 +201,16 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
         // at parity 0, behind a pair loop that runs only chunks inside K.  The parities are labels (which registers, which image),
         // so an odd number of inside chunks is evened out in FRONT: chunk 0 then runs alone at parity 1, which is where the fill put
         // it (hp).  Same chunks, same k order, same MFMAs as DMA = 0.
-        const int c_pairs = DMA ? c_mask : NCH;                                           // the pair loop runs chunks [hp, c_pairs & ~1 | hp)
+        // Slabs: the same four bodies over the task's range [c_lo, c_hi) -- chunk c_lo alone at parity 1 when the count of whole chunks
+        // is odd, the pairs up to c_in, then the masked chunk if this task has it (the last split only; it may be the task's only chunk:
+        // hp is then 0 and the fill has put it at parity 0, where the masked body reads).
+        const int c_pairs = DMA ? c_in : c_hi;                                            // the pair loop runs chunks [c_lo + hp, c_pairs)
         const int c_pfl = (DMA && c_pf >= 0) ? min(c_pf | hp, c_pairs - 2) : c_pf;         // (the touches ride on a pair of the loop)
-        int c = 0;
+        int c = c_lo;
         if constexpr (DMA) {
             if (hp) {
-                GD_FAT_CHUNK(1, 0, false);
-                c = 1;
+                GD_FAT_CHUNK(1, c_lo, false);
+                c = c_lo + 1;
             }
         }
         for (; c + 1 < c_pairs; c += 2) {
@@ -223,9 +241,9 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
         // an odd number of chunks (K = 1 000: 63, the last one half masked): the last chunk alone, not a pair with an all-zero
         // partner (1.6 % of the product's matrix instructions at K = 1 000)
         if constexpr (DMA) {
-            if (c < NCH) GD_FAT_CHUNK(0, c, true);  // (c == c_mask here)
+            if (c < c_hi) GD_FAT_CHUNK(0, c, true);  // (c == c_mask here)
         } else {
-            if (NCH & 1) GD_FAT_CHUNK(0, NCH - 1, NCH - 1 >= c_mask);
+            if ((c_hi - c_lo) & 1) GD_FAT_CHUNK(0, c_hi - 1, c_hi - 1 >= c_mask);
         }
 #undef GD_FAT_CHUNK
         if constexpr (DMA) {
@@ -233,6 +251,41 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_waitcnt(WAIT_VM0);
             __builtin_amdgcn_sched_barrier(0);
+        }
+
+        if constexpr (SLAB) {
+            // ---- slab epilogue: the partial tile into slab `split`, staged in rows as below -- no bias, no global reads.  The slab's
+            // rows are ldc = round4(N) floats and 16-byte aligned: whole groups leave as 16-byte stores, the group that holds column
+            // N - 1 element by element (a store past N would land in the next row), rows >= M not at all ----
+            constexpr int LDS_S = 16 * NB + 4, NJ_S = (4 * NB + 15) / 16;
+            float* const slab = g.C + (int64_t)split * g.slab_stride;
+#pragma unroll
+            for (int i = 0; i < TMB; ++i) {
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) lds[(4 * q + t) * LDS_S + 16 * b + r] = acc[i][b][t];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int p4 = 0; p4 < 4; ++p4) {
+                    const int m = m0 + 16 * i + 4 * p4 + q;
+#pragma unroll
+                    for (int j = 0; j < NJ_S; ++j) {
+                        const int c4 = r + 16 * j;
+                        const int n = n0 + 4 * c4;
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(lds + (4 * p4 + q) * LDS_S + 4 * min(c4, 4 * NB - 1));
+                        if (c4 < 4 * NB && m < g.M) {
+                            if (n + 3 < g.N) {
+                                *reinterpret_cast<f32x4*>(slab + (int64_t)m * g.ldc + n) = v;
+                            } else {
+                                for (int e = 0; e < 4 && n + e < g.N; ++e) slab[(int64_t)m * g.ldc + n + e] = v[e];
+                            }
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);  // (the next block's staging writes stay behind this block's reads)
+            }
+            continue;  // (the fused epilogues below belong to the other instantiations)
         }
 
         // ---- epilogue: the tile goes through the wave's LDS (the chunk images are dead) one block of 16 rows at a time and leaves
@@ -379,10 +432,11 @@ __global__ __launch_bounds__(256, 1) void dr_fat_kernel(const DrArgs d) {
 template <int NB>
 int dr_fat_go(const DrArgs& d, int epi, int dma, int n_cu, hipStream_t s) {
     const size_t lds = (size_t)4 * 2 * NB * 256 * sizeof(float) + 4 * 64 * sizeof(float);  // chunk images + a scratch line per wave (x_t prefetch)
-    void (*kern)(const DrArgs) = dma ? (epi == GD_EPI_LOSS ? dr_fat_kernel<NB, GD_EPI_LOSS, 1> : dr_fat_kernel<NB, GD_EPI_POST, 1>)
-                                     : (epi == GD_EPI_LOSS ? dr_fat_kernel<NB, GD_EPI_LOSS, 0> : dr_fat_kernel<NB, GD_EPI_POST, 0>);
-    static bool attr_set[4] = {false, false, false, false};
-    const int ai = 2 * dma + (epi == GD_EPI_LOSS);
+    void (*kern)(const DrArgs) =
+        dma ? (epi == GD_EPI_SLAB ? dr_fat_kernel<NB, GD_EPI_SLAB, 1> : epi == GD_EPI_LOSS ? dr_fat_kernel<NB, GD_EPI_LOSS, 1> : dr_fat_kernel<NB, GD_EPI_POST, 1>)
+            : (epi == GD_EPI_SLAB ? dr_fat_kernel<NB, GD_EPI_SLAB, 0> : epi == GD_EPI_LOSS ? dr_fat_kernel<NB, GD_EPI_LOSS, 0> : dr_fat_kernel<NB, GD_EPI_POST, 0>);
+    static bool attr_set[6] = {false, false, false, false, false, false};
+    const int ai = epi == GD_EPI_SLAB ? 4 + dma : 2 * dma + (epi == GD_EPI_LOSS);
     if (!attr_set[ai] && lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
@@ -393,6 +447,13 @@ int dr_fat_go(const DrArgs& d, int epi, int dma, int n_cu, hipStream_t s) {
     }
     hipLaunchKernelGGL(kern, dim3(n_cu), dim3(256), lds, s, d);
     return GDMCF_OK;
+}
+
+// B's pieces straight into LDS (GDMCF_FAT_DMA=1; 0: through staging registers): 16 bytes per lane from a 16-byte-aligned source,
+// any other weight runs the register-staged loop
+int dr_fat_dma(const GdGemm& g) {
+    static const int dma_env = getenv("GDMCF_FAT_DMA") ? atoi(getenv("GDMCF_FAT_DMA")) : GD_FAT_DMA_DEFAULT;
+    return (dma_env > 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0 && (g.ldb & 3) == 0) ? 1 : 0;
 }
 
 }  // namespace
@@ -435,10 +496,7 @@ int gd_dr_fat_launch(int epi, GdGemm& g, hipStream_t s) {
         static const int pf = getenv("GDMCF_FAT_PF") ? atoi(getenv("GDMCF_FAT_PF")) : 10;
         d.stagger = pf;  // (DrArgs: the field doubles as this kernel's prefetch distance)
     }
-    // B's pieces straight into LDS (GDMCF_FAT_DMA=1; 0: through staging registers): 16 bytes per lane from a 16-byte-aligned source,
-    // any other weight runs the register-staged loop
-    static const int dma_env = getenv("GDMCF_FAT_DMA") ? atoi(getenv("GDMCF_FAT_DMA")) : GD_FAT_DMA_DEFAULT;
-    const int dma = (dma_env > 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0 && (g.ldb & 3) == 0) ? 1 : 0;
+    const int dma = dr_fat_dma(g);
     g.tiles_m = d.tiles_m;
     g.tiles_n = d.tiles_n;
     d.g = g;
@@ -457,4 +515,74 @@ int gd_dr_fat_launch(int epi, GdGemm& g, hipStream_t s) {
     if (rc != GDMCF_OK) return rc;
     t_gd_last_gemm = 4;
     return gd_launch_status("gemm_dr");
+}
+
+// Tile width, split count and chunks per split of the first-layer forward on dr_fat_kernel<NB, GD_EPI_SLAB, 1> (common.h).  One
+// (split, tile) task per wave slot, one round: for every width the splits that fill the slots (at least eight chunks each, at most
+// 64 slabs for the reducer to sum), and of the widths the one whose task costs the least matrix time, NB x chunks per split.
+int gd_dr_fat_slab_plan(int M, int N, int K, int* nb_out, int* cps_out) {
+    if (!dr_routes().fat_slab || M <= 0 || N < 128 || K < 4096) return 0;
+    const int n_cu = dr_cu_count();
+    const int tiles_m = gd_cdiv(M, 80);
+    if ((n_cu & 7) != 0 || (long)tiles_m * 80 * 100 > (long)M * 112) return 0;  // 80-row tiles: at most 12 % padding
+    const long slots = 4L * n_cu;
+    const int chunks = gd_cdiv(K, 16);
+    int nb = 0, cps = 0;
+    long best = 1L << 60;
+    for (int c = 8; c <= 12; ++c) {
+        const long tiles = (long)tiles_m * gd_cdiv(N, 16 * c);
+        if (tiles > slots) continue;
+        long sp = slots / tiles;
+        if (sp > chunks / 8) sp = chunks / 8;
+        if (sp > 64) sp = 64;
+        if (sp < 2) continue;
+        const int per = gd_cdiv(chunks, (int)sp);
+        if ((long)c * per < best) { best = (long)c * per; nb = c; cps = per; }
+    }
+    if (!nb) return 0;
+    if (nb_out) *nb_out = nb;
+    if (cps_out) *cps_out = cps;
+    return gd_cdiv(chunks, cps);  // (the real split count: the last split may be short, none is empty)
+}
+
+// The first-layer forward xin W1^T (both operands K-contiguous) as split-K slabs on the fat-tile loop (sets g.splits / kchunk / tiles_*
+// for the reducer), or GD_DR_NOT_TAKEN with g as it was.  A weight that is not 16-byte aligned (a contiguous nn.Linear weight with
+// an odd K) runs the register-staged loop on the same plan: same MFMAs, same k order, same slabs -- the layer's result does not
+// depend on where its weight's rows are seated (tests/test_gpu_dw_multi.py compares a seated weight with a contiguous one bit for bit).
+int gd_dr_fat_slab_launch(GdGemm& g, hipStream_t s) {
+    int nb = 0, cps = 0;
+    const int splits = gd_dr_fat_slab_plan(g.M, g.N, g.K, &nb, &cps);
+    if (!splits) return GD_DR_NOT_TAKEN;
+    const size_t need = (size_t)splits * g.M * g.ldc * sizeof(float);
+    const bool ok = gd_aligned16(g.C) && (g.ldc & 3) == 0 && g.ldc >= g.N &&
+                    g.ws_cap >= need && g.slab_stride >= (int64_t)g.M * g.ldc && (g.slab_stride & 3) == 0 &&
+                    (int64_t)g.M * g.lda * 4 < ((int64_t)1 << 31) && (int64_t)g.N * g.ldb * 4 < ((int64_t)1 << 32) && g.lda >= g.K && g.ldb >= g.K;
+    if (!ok) return GD_DR_NOT_TAKEN;
+    const int n_cu = dr_cu_count();
+    DrArgs d = {};
+    d.tiles_m = gd_cdiv(g.M, 80);
+    d.tiles_n = gd_cdiv(g.N, 16 * nb);
+    d.m_fastest = 1;
+    d.ksp = gd_cdiv(g.K, 16);  // chunks of 16 k in the whole reduction; a task runs g.kchunk / 16 of them
+    g.splits = splits;
+    g.kchunk = cps * 16;
+    g.tiles_m = d.tiles_m;
+    g.tiles_n = d.tiles_n;
+    d.g = g;
+    d.ctr = 0;
+    const int dma = dr_fat_dma(g);
+    int rc = GDMCF_OK;
+    {
+        GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
+        switch (nb) {
+            case 8: rc = dr_fat_go<8>(d, GD_EPI_SLAB, dma, n_cu, s); break;
+            case 9: rc = dr_fat_go<9>(d, GD_EPI_SLAB, dma, n_cu, s); break;
+            case 10: rc = dr_fat_go<10>(d, GD_EPI_SLAB, dma, n_cu, s); break;
+            case 11: rc = dr_fat_go<11>(d, GD_EPI_SLAB, dma, n_cu, s); break;
+            default: rc = dr_fat_go<12>(d, GD_EPI_SLAB, dma, n_cu, s); break;
+        }
+    }
+    if (rc != GDMCF_OK) return rc;
+    t_gd_last_gemm = 6;
+    return gd_launch_status("gemm_dr_fat_slab");
 }

@@ -147,9 +147,11 @@ size_t gdmcf_linear_ws_bytes(int M, int N, int K) {
     for (int prec = GDMCF_GEMM_F32; prec <= GDMCF_GEMM_F32X3; ++prec) {  // the caller may switch precision later
         const int cf = pick_class(M, N, false, prec), cb = pick_class(M, K, false, prec);
         size_t f = (size_t)pick_splits(M, N, K, cf, prec) * M * round4(N);
-        if (prec == GDMCF_GEMM_F32) {  // gdmcf_linear_fwd_wt_f32 on dr_kn_kernel
+        if (prec == GDMCF_GEMM_F32) {  // gdmcf_linear_fwd_wt_f32 on dr_kn_kernel, gdmcf_linear_fwd_f32 on the fat-tile slab loop
             const size_t fk = (size_t)gd_dr_kn_splits(M, N, K) * M * round4(N);
             f = f > fk ? f : fk;
+            const size_t ff = (size_t)gd_dr_fat_slab_plan(M, N, K, nullptr, nullptr) * M * round4(N);
+            f = f > ff ? f : ff;
         }
         size_t b = (size_t)pick_splits(M, K, N, cb, prec) * M * round4(K);
         if (prec == GDMCF_GEMM_F32) {  // the input gradient on dr_kn_kernel: one (split, tile) task per wave slot
@@ -160,6 +162,15 @@ size_t gdmcf_linear_ws_bytes(int M, int N, int K) {
         need = need > b ? need : b;
     }
     return need * sizeof(float) + 256;
+}
+
+int gdmcf_debug_fat_slab_plan(int M, int N, int K, int* nb, int* splits, int* cps) {
+    int nb_ = 0, cps_ = 0;
+    const int sp = (t_gemm_prec == GDMCF_GEMM_F32 && M > 0 && N > 0 && K > 0) ? gd_dr_fat_slab_plan(M, N, K, &nb_, &cps_) : 0;
+    if (nb) *nb = nb_;
+    if (splits) *splits = sp;
+    if (cps) *cps = cps_;
+    return sp > 0;
 }
 
 int gdmcf_loss_tiles(int N) { return gd_cdiv(N, 16); }  // partial row sums per output tile: the narrowest tile any kernel uses
@@ -189,6 +200,7 @@ int gdmcf_linear_fwd_f32(const float* A, int64_t lda, const float* W, int64_t ld
         return GDMCF_E_WORKSPACE;
     }
     g.splits = splits; g.C = (float*)ws; g.ldc = lds_; g.slab_stride = (int64_t)M * lds_;
+    g.ws_cap = ws_bytes;  // (the fat-tile slab loop splits further when the workspace allows: gdmcf_linear_ws_bytes sizes for it)
     attach_shadows(g, GD_LAY_KC, GD_LAY_KC);
     int rc = gd_gemm_launch(GD_LAY_KC, GD_LAY_KC, GD_EPI_SLAB, cls, g, s);
     if (rc) return rc;

@@ -42,9 +42,14 @@ int gdmcf_device_info(int* n_cu, int* wave_size, char* arch_host, int arch_len);
 /* Which kernel family the calling thread's LAST dense product was dispatched to (introspection for tests and
  * profiles -- "did the hand-written path run?"): 1 LDS-tiled f32 MFMA kernel, 2 register-streaming weight-gradient
  * kernel, 3 the same with the AdamW stream, 4 fat-tile output-layer kernel (one tile per wave), 5 register-streaming
- * input-gradient / cached-W^T forward kernel (dr_kn_kernel), 6 retired (never returned), 7 bf16-input kernels,
+ * input-gradient / cached-W^T forward kernel (dr_kn_kernel), 6 fat-tile kernel over split-K slabs (the first-layer forward), 7 bf16-input kernels,
  * 8 f32x3 kernels, 9 element-wise kernel for degenerate shapes; 0 none yet.                              */
 int gdmcf_debug_last_gemm(void);
+/* What the fat-tile slab route (family 6) plans for gdmcf_linear_fwd_f32's product C[M, N] = A[M, K] W[N, K]^T on the current device, in
+ * the calling thread's GEMM precision: returns 1 and the tile width *nb (x 16 columns), the split count *splits and the chunks of
+ * 16 k per split *cps, or 0 (all three 0) when the route does not take the shape.  The call itself may still decline: a workspace
+ * that is not 16-byte aligned or smaller than gdmcf_linear_ws_bytes.  Tests pick their shapes with it. */
+int gdmcf_debug_fat_slab_plan(int M, int N, int K, int* nb, int* splits, int* cps);
 
 /* Optional in-library timing with HIP events on the launch stream (bench.py's live roofline
  * measurement).  While enabled, every tagged kernel launch is bracketed by two hipEventRecord
