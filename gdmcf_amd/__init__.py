@@ -11,7 +11,7 @@ from .cat import DNNCat  # noqa: F401
 from .onehot_embedding import DNNOneHotEmbedding, nt_xent_loss_grad  # noqa: F401
 from .onehot_gcn import DNNOneHotEmbeddingGCN  # noqa: F401
 from . import checkpoint, data_utils, driver, parallel  # noqa: F401
-from .recommend import recommend, score_candidates  # noqa: F401  (the function shadows its module's name in the package: `gdmcf_amd.recommend(...)`)
+from .recommend import rank_targets, recommend, score_candidates  # noqa: F401  (the function shadows its module's name in the package: `gdmcf_amd.recommend(...)`)
 
 __all__ = ["DNN", "timestep_embedding", "GaussianDiffusion", "GaussianDiffusionDiscrete", "ModelMeanType", "FusedAdamW", "computeTopNAccuracy",
-           "computeTopNAccuracy_device", "masked_topk", "score_topk", "print_results", "LightGCN", "BPRTrainer", "DNNOneHot", "DNNCat", "DNNOneHotEmbedding", "DNNOneHotEmbeddingGCN", "nt_xent_loss_grad", "recommend", "score_candidates"]
+           "computeTopNAccuracy_device", "masked_topk", "score_topk", "print_results", "LightGCN", "BPRTrainer", "DNNOneHot", "DNNCat", "DNNOneHotEmbedding", "DNNOneHotEmbeddingGCN", "nt_xent_loss_grad", "recommend", "score_candidates", "rank_targets"]

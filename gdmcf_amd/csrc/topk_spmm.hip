@@ -3,32 +3,17 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "rank_order.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------
 // masked top-k: one 256-thread workgroup per row.
 //   1. history mask -> bitmap in LDS (I bits)
-//   2. 4-pass 8-bit radix select on order-preserving uint32 keys -> k-th largest key
+//   2. 4-pass 8-bit radix select on order-preserving uint32 keys -> k-th largest key (rank_order.h: order_key, masked_key)
 //   3. collect keys > threshold (any order) + the lowest-index ties == threshold
 //   4. bitonic sort of (key, ~index) pairs -> descending score, ascending index on ties
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t order_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_to_float(uint32_t k) {
-    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
-
-constexpr uint32_t NEG_INF_KEY = 0x007FFFFFu;  // order_key(-inf)
-
-__device__ __forceinline__ uint32_t masked_key(const float* __restrict__ row, const uint32_t* bitmap, int i) {
-    if (bitmap[i >> 5] & (1u << (i & 31))) return NEG_INF_KEY;
-    return order_key(row[i]);
-}
-
 // gdmcf_topk_masked_rows_f32: what the row-indirected instantiations take behind the plain kernels' arguments.  Both kernels
 // below end in a parameter pack EXT that is either empty -- gdmcf_topk_masked_f32: the parameter list, the kernel arguments and
 // the code are what they were without the pack -- or one TopkRowsArgs.
@@ -39,17 +24,6 @@ struct TopkRowsArgs {
     const float* scale;       // [B] factor of the returned values (nullptr: none)
 };
 __device__ __forceinline__ const TopkRowsArgs& rows_args(const TopkRowsArgs& e) { return e; }
-
-// bits of CSR row r into the LDS bitmap, as the plain kernels set their own row's (entries outside [0, I) skipped)
-template <int NT>
-__device__ __forceinline__ void mask_row_bits(uint32_t* bitmap, int I, const int64_t* __restrict__ indptr,
-                                              const int32_t* __restrict__ indices, int64_t r, int tid) {
-    const int64_t beg = indptr[r], end = indptr[r + 1];
-    for (int64_t j = beg + tid; j < end; j += NT) {
-        const int c = indices[j];
-        if (c >= 0 && c < I) atomicOr(&bitmap[c >> 5], 1u << (c & 31));
-    }
-}
 
 // NT threads per row: 1024 when the row is staged in LDS (the staged row allows one workgroup per CU anyway, and
 // the select is a chain of short LDS loops -- 16 waves hide their latency, 4 waves measured 2.4x slower)
@@ -631,6 +605,64 @@ __global__ __launch_bounds__(256) void topn_metrics_kernel(const int64_t* __rest
     }
 }
 
+// The same four terms from the RANKS of a user's ground-truth items (gdmcf_rank_targets_f32) instead of a list: one wave per user.
+// The hits below a cut-off are visited in ascending rank -- every round the 64 lanes find the smallest (rank, column) pair not
+// yet visited -- so dcg receives the gains topn_metrics_kernel adds, in its order; idcg runs over j < min(N, |GT|) in ascending
+// j as there; the same expressions in float64: the same bits.  Every lane carries the same sums, lane 0 stores them.  Nothing
+// is bounded by a list length: a cut-off past the last hit only closes the sums.
+__global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t* __restrict__ ranks, int64_t ldr, int U, int G,
+                                                           const TopNList tn, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= U) return;  // (the whole wave)
+    const int32_t* r = ranks + (int64_t)u * ldr;
+    int len = 0;
+    for (int j = lane; j < G; j += 64) len += r[j] >= 0 ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) len += __shfl_xor(len, o);
+    double* o = out + (int64_t)u * tn.n * 4;
+    if (len == 0) {
+        for (int k = lane; k < tn.n * 4; k += 64) o[k] = 0.0;
+        return;
+    }
+    constexpr unsigned long long NONE = ~0ull;
+    int hits = 0, next = 0, ji = 0;
+    double dcg = 0.0, idcg = 0.0, mrr = 0.0;
+    unsigned long long from = 0ull;  // pairs below it are visited
+    while (next < tn.n) {
+        unsigned long long best = NONE;
+        for (int j = lane; j < G; j += 64) {
+            const int32_t v = r[j];
+            if (v >= 0) {
+                const unsigned long long p = ((unsigned long long)(uint32_t)v << 32) | (uint32_t)j;
+                if (p >= from && p < best) best = p;
+            }
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            const unsigned long long t = __shfl_xor(best, s);
+            best = t < best ? t : best;
+        }
+        const int64_t rk = (int64_t)(best >> 32);  // (NONE: past every cut-off)
+        while (next < tn.n && (best == NONE || rk >= (int64_t)tn.v[next])) {  // the cut-offs that close before this hit
+            const int N = tn.v[next];
+            for (; ji < N && ji < len; ++ji) idcg += 1.0 / log2((double)(ji + 2));
+            if (lane == 0) {
+                o[next * 4 + 0] = (double)hits / (double)N;
+                o[next * 4 + 1] = (double)hits / (double)len;
+                o[next * 4 + 2] = idcg != 0.0 ? dcg / idcg : 0.0;
+                o[next * 4 + 3] = mrr;
+            }
+            ++next;
+        }
+        if (best == NONE) break;
+        dcg += 1.0 / log2((double)(rk + 2));
+        if (hits == 0) mrr = 1.0 / ((double)rk + 1.0);
+        ++hits;
+        from = best + 1ull;
+    }
+}
+
 // Both top-k entries: the fast path where it applies, then the radix-select kernel (alone, or for the rows the fast path marked).
 // EXT is the kernels' own pack: empty (gdmcf_topk_masked_f32) or one TopkRowsArgs, handed on behind the plain arguments.
 template <class... EXT>
@@ -793,6 +825,21 @@ int gdmcf_topn_metrics_f64(const int64_t* pred_idx, int64_t ldp, int U, const in
     hipLaunchKernelGGL(topn_metrics_kernel, dim3(gd_cdiv(U, 256)), dim3(256), 0, (hipStream_t)stream, pred_idx, ldp, U,
                        gt_indptr, gt_indices, tn, out);
     return gd_launch_status("topn_metrics");
+}
+
+int gdmcf_rank_metrics_f64(const int32_t* ranks, int64_t ldr, int U, int G, const int* topN_host, int n_topn, double* out,
+                           void* stream) {
+    GD_CHECK_SHAPE(U > 0 && G >= 1 && ldr >= G && n_topn >= 1 && n_topn <= TOPN_MAX,
+                   "gdmcf_rank_metrics_f64: bad shape (U > 0, G >= 1, ldr >= G, 1..8 cut-offs)");
+    GD_CHECK_ARG(ranks && topN_host && out, "gdmcf_rank_metrics_f64: null pointer");
+    TopNList tn;
+    tn.n = n_topn;
+    for (int i = 0; i < n_topn; ++i) {
+        tn.v[i] = topN_host[i];
+        GD_CHECK_ARG(tn.v[i] >= 1 && (i == 0 || tn.v[i] > tn.v[i - 1]), "gdmcf_rank_metrics_f64: cut-offs must be ascending and >= 1");
+    }
+    hipLaunchKernelGGL(rank_metrics_kernel, dim3(gd_cdiv(U, 4)), dim3(256), 0, (hipStream_t)stream, ranks, ldr, U, G, tn, out);
+    return gd_launch_status("gdmcf_rank_metrics_f64");
 }
 
 }  // extern "C"

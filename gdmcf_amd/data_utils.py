@@ -49,6 +49,7 @@ class DeviceCSR:
         csr = sp.csr_matrix(csr)
         csr.sum_duplicates()
         self.shape = csr.shape
+        self.max_row_len = int(np.diff(csr.indptr).max(initial=0))  # the longest row (host matrix: no device read)
         self.device = torch.device(device)
         self.indptr = torch.from_numpy(csr.indptr.astype(np.int64)).to(self.device)
         self.indices = torch.from_numpy(csr.indices.astype(np.int32)).to(self.device)

@@ -48,7 +48,7 @@ def train_one_epoch(diffusion, model, optimizer, train_csr, batch_size, device, 
 
 @torch.no_grad()
 def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps, sampling_noise, batch_size,
-             device, sparse=False, latent=False, recommend=False, candidates=None):
+             device, sparse=False, latent=False, recommend=False, candidates=None, ranks=False):
     """Precision / Recall / NDCG / MRR @topN exactly as reference main.py:267-310.
 
     data_csr: rows fed to p_sample (the reference feeds the training rows); data_te: ground-truth CSR;
@@ -61,9 +61,14 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
     per call, or passed through when it already is one -- so no batch slices a matrix on the host; `sparse` is then ignored and
     of `latent` only the value "extended" matters (recommend picks its own route, `diffusion.last_recommend_route`).
     candidates (with recommend=True only): [n_users, C], row u the items user u is ranked within (gdmcf_amd.recommend's
-    `candidates`: a retriever's output, an allow-list, the sampled-negatives protocol's one held-out item among sampled ones)."""
+    `candidates`: a retriever's output, an allow-list, the sampled-negatives protocol's one held-out item among sampled ones).
+    ranks=True (with recommend=True, without candidates): no lists at all -- gdmcf_amd.rank_targets gives the catalogue rank of
+    every ground-truth item and evaluate_utils.rank_metrics_device the metrics from them: the same return value, with topN no
+    longer bounded by the top-k's k."""
     if candidates is not None and not recommend:
         raise ValueError("driver.evaluate: candidates needs recommend=True")
+    if ranks and (not recommend or candidates is not None):
+        raise ValueError("driver.evaluate: ranks=True needs recommend=True and takes no candidates")
     model.eval()
     n = mask_his.shape[0]
     predict_items = []
@@ -71,6 +76,14 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
     if recommend:
         from .recommend import recommend as recommend_fn
         mask = mask_his if isinstance(mask_his, DeviceCSR) else DeviceCSR(mask_his, device)
+        if ranks:
+            from .recommend import rank_targets
+            gt = data_te.tocsr().astype(np.float32, copy=True)  # (the ground truth as computeTopNAccuracy_device reads it)
+            gt.eliminate_zeros()
+            got = rank_targets(diffusion, model, dcsr, np.arange(n), DeviceCSR(gt, device), mask=mask, sampling_steps=sampling_steps,
+                               sampling_noise=sampling_noise, batch_size=batch_size,
+                               **(dict(latent="extended") if isinstance(latent, str) and latent == "extended" else {}))
+            return evaluate_utils.rank_metrics_device(got, topN)
         lists = recommend_fn(diffusion, model, dcsr, np.arange(n), topN[-1], mask=mask, sampling_steps=sampling_steps,
                              sampling_noise=sampling_noise, batch_size=batch_size,  # (the same batches, made inside)
                              **(dict(latent="extended") if isinstance(latent, str) and latent == "extended" else {}),

@@ -158,6 +158,91 @@ def computeTopNAccuracy_device(ground_truth_csr, predicted_idx, topN):
     return res[0], res[1], res[2], res[3]
 
 
+def _check_topN(topN):
+    topN = [int(n) for n in topN]
+    if topN != sorted(set(topN)) or not topN or topN[0] < 1:
+        raise ValueError("topN must be ascending, non-empty and >= 1")
+    return topN
+
+
+def rank_metrics(ranks, topN):
+    """computeTopNAccuracy from RANKS instead of lists, in plain Python: ranks[u] holds the 0-based catalogue rank of each of
+    user u's ground-truth items (gdmcf_amd.rank_targets; negative entries = no item there).  |GT| is the number of non-negative
+    entries, a hit below N an entry < N; the hits are taken in ascending rank, so every sum receives the terms of the
+    reference's loop over the list the ranks came from, in its order: the same rounded results.  Cut-offs are bounded by no
+    list length; users without ground truth add nothing but count in the divisor."""
+    topN = _check_topN(topN)
+    precision, recall, NDCG, MRR = [], [], [], []
+    n_users = len(ranks)
+    for N in topN:
+        sum_p = sum_r = sum_n = sum_m = 0
+        for i in range(n_users):
+            gt = sorted(int(r) for r in ranks[i] if int(r) >= 0)
+            if len(gt) == 0:
+                continue
+            hits, dcg, idcg, mrr = 0, 0.0, 0.0, 0.0
+            for r in gt:
+                if r >= N:
+                    break
+                dcg += 1.0 / math.log2(r + 2)
+                if hits == 0:
+                    mrr = 1.0 / (r + 1.0)
+                hits += 1
+            for j in range(min(N, len(gt))):
+                idcg += 1.0 / math.log2(j + 2)
+            sum_p += hits / N
+            sum_r += hits / len(gt)
+            sum_n += (dcg / idcg) if idcg != 0 else 0
+            sum_m += mrr
+        precision.append(round(sum_p / n_users, 4))
+        recall.append(round(sum_r / n_users, 4))
+        NDCG.append(round(sum_n / n_users, 4))
+        MRR.append(round(sum_m / n_users, 4))
+    return precision, recall, NDCG, MRR
+
+
+RANK_METRICS_GROUP = 8  # cut-offs per gdmcf_rank_metrics_f64 call
+
+
+def rank_metrics_terms(ranks, topN):
+    """The per-user terms [U, len(topN), 4] (float64, on the device; precision / recall / NDCG / MRR) of gdmcf_rank_metrics_f64
+    for int32 device ranks [U, G], the cut-offs in groups of RANK_METRICS_GROUP."""
+    import ctypes
+    _lib.require_gpu(ranks, "ranks")
+    topN = _check_topN(topN)
+    if ranks.dim() != 2 or ranks.shape[1] < 1:
+        raise ValueError("ranks is [n_users, G >= 1]")
+    r = ranks if ranks.dtype == torch.int32 else ranks.to(torch.int32)
+    if r.stride(-1) != 1:
+        r = r.contiguous()
+    U, G = r.shape
+    out = torch.empty(U, len(topN), 4, dtype=torch.float64, device=r.device)
+    if U == 0:
+        return out
+    for lo in range(0, len(topN), RANK_METRICS_GROUP):
+        grp = topN[lo:lo + RANK_METRICS_GROUP]
+        part = out if len(grp) == len(topN) else torch.empty(U, len(grp), 4, dtype=torch.float64, device=r.device)
+        _lib.check(_lib.load().gdmcf_rank_metrics_f64(r.data_ptr(), r.stride(0), U, G, (ctypes.c_int * len(grp))(*grp), len(grp),
+                                                      part.data_ptr(), _lib.stream_ptr()))
+        if part is not out:
+            out[:, lo:lo + len(grp)] = part
+    return out
+
+
+def rank_metrics_device(ranks, topN):
+    """rank_metrics with the per-user work on the MI355X (gdmcf_rank_metrics_f64): `ranks` an int32 device tensor [U, G] as
+    gdmcf_amd.rank_targets returns it for the ground truth as targets.  The per-user terms carry the bits of
+    gdmcf_topn_metrics_f64 on the lists the ranks came from; they are added up in user order on the host and rounded exactly
+    as computeTopNAccuracy_device does, so the four lists equal its (and the reference's) -- for any cut-offs, also above the
+    item count."""
+    topN = _check_topN(topN)
+    terms = rank_metrics_terms(ranks, topN).cpu().numpy()
+    U = terms.shape[0]
+    sums = np.add.accumulate(terms, axis=0)[-1]  # sequential float64 additions in user order, as the reference's loop
+    res = [[round(float(sums[k, m]) / U, 4) for k in range(len(topN))] for m in range(4)]
+    return res[0], res[1], res[2], res[3]
+
+
 def print_results(loss, valid_result, test_result):
     """output the evaluation results."""
     if loss is not None:

@@ -5,7 +5,9 @@ layer's space, without the dense x_T, the posterior epilogue and x_0 itself: the
 c1[0], so the raw scores of the last product are ranked and only the k returned values are scaled.
 `score_candidates` / `recommend(candidates=)`: the same call for the items a caller names per user -- where the
 reverse loop ends at the operands of its last product and the lists are short, only the named rows of the output weight are
-read (gdmcf_cand_scores_f32); otherwise the named scores are picked out of the [B, I] ones (gdmcf_cand_pick_f32)."""
+read (gdmcf_cand_scores_f32); otherwise the named scores are picked out of the [B, I] ones (gdmcf_cand_pick_f32).
+`rank_targets`: the same call ending in the exact rank of every item a target matrix names per user, in that order,
+instead of a list (gdmcf_rank_targets_f32) -- the evaluation side: every metric that is a function of where the held-out items sit."""
 import types
 
 import numpy as np
@@ -272,3 +274,46 @@ def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_step
             scores.data_ptr(), scores.stride(0), B, I, *c.mask_ptrs, chunk.data_ptr(), _lib.ptr(scale), k,
             idx[lo:lo + B].data_ptr(), _lib.ptr(v), _lib.stream_ptr()))
     return (val, idx) if return_values else idx
+
+
+def rank_targets(diffusion, model, rows, user_ids, targets, *, mask="rows", sampling_steps=0, sampling_noise=False, batch_size=400,
+                 latent=True, noise0=None, sampled0=None, return_live=False):
+    """The exact catalogue ranks [n, G] (int32, on the device) of the items the DeviceCSR `targets` names per user -- an
+    evaluation's held-out items -- in the order `recommend` ranks by: ranks[r, j] is the number of items that precede the j-th
+    entry of row user_ids[r] of `targets` when the mask's items count as -inf, larger predictions come first and equal ones in
+    ascending item index; the 0-based place the item has in recommend(..., k = I)'s list (gdmcf_rank_targets_f32).  Every
+    quantity that is a function of where the held-out items sit follows from it without a [n, I] copy to the host: untruncated
+    MRR, mean rank, Recall@N for an N chosen afterwards, leave-one-out HR@N / NDCG@N (evaluate_utils.rank_metrics_device), and with
+    return_live percentiles and AUC.
+
+    targets: a DeviceCSR with `rows`' shape (its values are not read).  G = targets.max_row_len (at least 1); columns past the
+    length of a user's row hold -1.  A masked target is ranked inside the -inf tail by its index, as the top-k would list it.
+    return_live: (ranks, n_live [n] int32) -- the number of unmasked items per user.
+    Everything else is recommend's: the routes (`diffusion.last_recommend_route`; on the latent routes the raw scores of the
+    last product are ranked, which the positive scale does not reorder), masks, chunks of `batch_size`, `index`, the injected
+    draws noise0 / sampled0, the id checks.  Per chunk one launch follows the scores; no top-k runs and nothing synchronises.
+    Candidate lists are not taken: a rank inside a [n, C] list is two torch operations on score_candidates' output s,
+    (s > s.gather(1, pos)).sum(1) plus the equal scores at lower positions."""
+    if not isinstance(rows, DeviceCSR):
+        raise TypeError("gdmcf_amd.rank_targets: rows must be a gdmcf_amd.data_utils.DeviceCSR")
+    if not isinstance(targets, DeviceCSR):
+        raise TypeError("gdmcf_amd.rank_targets: targets must be a gdmcf_amd.data_utils.DeviceCSR")
+    if tuple(targets.shape) != tuple(rows.shape):
+        raise ValueError(f"gdmcf_amd.rank_targets: targets has shape {tuple(targets.shape)}, rows {tuple(rows.shape)}")
+    c = _setup(diffusion, model, rows, user_ids, mask, sampling_steps, sampling_noise, batch_size, latent)
+    _lib.require_gpu(targets.indptr, "targets")
+    dev, n, I = c.dev, c.n, c.I
+    G = max(int(targets.max_row_len), 1)
+    ranks = torch.empty(n, G, dtype=torch.int32, device=dev)
+    live = torch.empty(n, dtype=torch.int32, device=dev) if return_live else None
+    if n:
+        lib, eng = _lib.load(), model.engine
+        # (a matrix without any entry: an empty tensor has no pointer, and no indptr range covers the one index handed over instead)
+        tix = targets.indices if targets.indices.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+        for lo, chunk, B, product, scores in _reverse_chunks(diffusion, model, rows, c, noise0, sampled0):
+            scores, _ = _all_scores(eng, B, dev, product, scores)
+            _lib.check(lib.gdmcf_rank_targets_f32(
+                scores.data_ptr(), scores.stride(0), B, I, *c.mask_ptrs, targets.indptr.data_ptr(), tix.data_ptr(),
+                chunk.data_ptr(), G, ranks[lo:lo + B].data_ptr(), ranks.stride(0),
+                _lib.ptr(live[lo:lo + B]) if live is not None else None, _lib.stream_ptr()))
+    return (ranks, live) if return_live else ranks

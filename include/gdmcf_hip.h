@@ -510,6 +510,27 @@ int gdmcf_topk_masked_f32(const float* pred, int64_t ldp, int B, int I, const in
 int gdmcf_topk_masked_rows_f32(const float* pred, int64_t ldp, int B, int I, const int64_t* indptr, const int32_t* indices,
                                const int64_t* indptr2, const int32_t* indices2, const int64_t* rows, const float* scale, int k,
                                int64_t* idx_out, float* val_out, void* stream);
+/* The exact position of named items in that order (gdmcf_amd.rank_targets): rank_out[b, j], j < the length of row rows[b] of the
+ * target CSR (tgt_indptr int64 [n_users + 1], tgt_indices int32, a FULL CSR like the masks; required), is the number of items
+ * i in [0, I) that precede target j -- the 0-based place it would have in gdmcf_topk_masked_rows_f32(..., k = I)'s list for the
+ * same pred, masks and rows.  The order is the top-k's: an item's key is the order key of its score, or of -inf when the item
+ * occurs in row rows[b] of either mask CSR (indptr / indices, optional indptr2 / indices2 which needs the first; both NULL =
+ * no mask; rows unsorted, repeated or out of range as there); larger key first, equal keys in ascending item index; NaN, +-0
+ * and +-inf order by the same key map.  A masked target is ranked inside the -inf tail by its index, as the top-k would list
+ * it.  A target outside [0, I) gets -1; columns from the row's length up to G get -1; target entries past G are not ranked;
+ * columns from G up to ldr are not written.  Target rows may be unsorted and hold repeats: equal targets get equal ranks.
+ * rows int64 [B]: the row of EVERY CSR (masks and targets) per pred row, not checked on the device; NULL = rows 0..B-1.
+ * n_live_out (optional, int32 [B]): the number of unmasked items of the row, I minus the distinct in-range mask entries --
+ * what turns a rank into a percentile or an AUC.
+ * Limits: any B >= 1, I >= 1, G >= 1, ldp >= I, ldr >= G (GDMCF_E_SHAPE otherwise).  Targets are ranked in passes of up to 1024
+ * (the row is streamed once per pass; one pass for G <= 1024), fewer per pass where the mask bitmap of I bits leaves less
+ * room: the plan -- 12 bytes per target of a pass plus I / 8 bytes -- must fit 160 KiB of LDS with 32 targets a pass, so I up
+ * to about 1.3 million, the width gdmcf_topk_masked_rows_f32 takes; wider rows return GDMCF_E_UNSUPPORTED.
+ * The counts are integers added by LDS atomics: the same result in every run.  No global atomics, no workspace, no host
+ * synchronisation.                                                                                                      */
+int gdmcf_rank_targets_f32(const float* pred, int64_t ldp, int B, int I, const int64_t* indptr, const int32_t* indices,
+                           const int64_t* indptr2, const int32_t* indices2, const int64_t* tgt_indptr, const int32_t* tgt_indices,
+                           const int64_t* rows, int G, int32_t* rank_out, int64_t ldr, int32_t* n_live_out, void* stream);
 
 /* ---- candidate lists: score only the items a caller names (gdmcf_amd.score_candidates, recommend(candidates=)) -----------
  * The gathered product: out[b, c] = (dot(A[b, :K], W[cand[b, c], :K]) + bias[cand[b, c]]) * scale[b] for b < B, c < C -- the
@@ -558,6 +579,15 @@ int gdmcf_score_topk_f32(const float* user_emb, int64_t ldu, const int64_t* user
  * ground truth as CSR with sorted column indices.  The caller adds the terms up over users and divides by U.        */
 int gdmcf_topn_metrics_f64(const int64_t* pred_idx, int64_t ldp, int U, const int64_t* gt_indptr, const int32_t* gt_indices,
                            const int* topN_host, int n_topn, double* out, void* stream);
+/* The same four terms from ranks instead of lists: ranks int32 [U, ldr >= G] as gdmcf_rank_targets_f32 writes them for the
+ * ground truth as targets (a negative entry = no item there), |GT| = the number of non-negative entries of the row, a hit
+ * below N = an entry < N.  The hits are taken in ascending rank and DCG is accumulated in that order, IDCG over
+ * j < min(N, |GT|) in ascending j: for ranks that came from a full order the float64 bits equal gdmcf_topn_metrics_f64's on
+ * that order's first N items.  A user without entries gets zeros.  topN_host ascending, any values >= 1, at most 8 per call
+ * (the host calls it in groups): no list bounds them, a cut-off past the item count counts every hit (recall 1).
+ * out[U][n_topn][4].  One wave per user, no atomics: deterministic.                                                     */
+int gdmcf_rank_metrics_f64(const int32_t* ranks, int64_t ldr, int U, int G, const int* topN_host, int n_topn, double* out,
+                           void* stream);
 
 /* ---- LightGCN propagation: CSR SpMM (lightGCN.py:184-189) --------------------------------
  * Y[r,:] = ( sum_j val[j]*X[col[j],:]  +  sum_k addend_k[r,:] ) * scale
