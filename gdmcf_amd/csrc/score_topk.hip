@@ -14,6 +14,7 @@
 // When there are too few row tiles to fill the chip the items are split into slabs: each (tile, slab) workgroup writes its k
 // best pairs to the workspace and score_merge_kernel sorts a row's slabs together.
 #include "common.h"
+#include "score_product.h"
 
 namespace {
 
@@ -28,22 +29,8 @@ __device__ __forceinline__ float st_key_to_float(uint32_t k) {
 constexpr uint32_t ST_NEG_INF_KEY = 0x007FFFFFu;  // st_order_key(-inf)
 constexpr int ST_BM_ITEMS = 2048;                  // items covered by one build of the history bitmap
 constexpr int ST_BM_WORDS = ST_BM_ITEMS / 32;
-constexpr int ST_STEP = 64;                        // items per workgroup step (4 waves x 16)
+constexpr int ST_STEP = SP_STEP;                   // items per workgroup step (4 waves x 16)
 typedef unsigned long long u64;
-
-// four consecutive floats of a table row, zero past d; `vec`: rows are 16-byte aligned and d % 4 == 0
-__device__ __forceinline__ f32x4 st_load4(const float* __restrict__ row, int k0, int d, bool vec) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (vec) {
-        if (k0 < d) v = *reinterpret_cast<const f32x4*>(row + k0);
-    } else {
-        if (k0 < d) v.x = row[k0];
-        if (k0 + 1 < d) v.y = row[k0 + 1];
-        if (k0 + 2 < d) v.z = row[k0 + 2];
-        if (k0 + 3 < d) v.w = row[k0 + 3];
-    }
-    return v;
-}
 
 // all lists of the tile: pad to CAP with 0 (below every real pair), bitonic sort descending, cut to k, raise the bounds
 __device__ void st_compact(u64* cand, uint32_t* cnt, u64* thr, int R, int CAP, int k, int tid) {
@@ -110,12 +97,10 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
         const int r = row0 + min(rb * 16 + lc, rows_here - 1);
         arow[rb] = U + (uid ? uid[r] : (int64_t)r) * ldu;
     }
-    f32x4 areg[AREG ? RB : 1][4];
-    if (AREG) {
+    f32x4 areg[RB][4];  // (the product step -- fragments, k order -- is score_product.h's, shared with score_rank.hip)
+    if constexpr (AREG) {
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) areg[rb][j] = st_load4(arow[rb], 16 * j + 4 * lg, d, vec != 0);
+        for (int rb = 0; rb < RB; ++rb) sp_load_frags(areg[rb], arow[rb], lg, d, vec != 0);
     }
     float thrf[RB][4];  // the bounds of this lane's rows as floats: -inf = everything passes, +inf (rows past the end) = nothing
 #pragma unroll
@@ -125,12 +110,7 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
 
     auto item_row = [&](int base) -> const float* { return V + (int64_t)min(base + 16 * wave + lc, n_items - 1) * ldi; };
     f32x4 bcur[4], bnext[4];
-    if (AREG) {
-        const float* p = item_row(i0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bcur[j] = st_load4(p, 16 * j + 4 * lg, d, vec != 0);
-    }
-    const int nkc = (d + 15) >> 4;
+    if constexpr (AREG) sp_load_frags(bcur, item_row(i0), lg, d, vec != 0);
 
     for (int cbase = i0; cbase < i1; cbase += ST_BM_ITEMS) {
         // ---- history bitmap of items cbase .. cbase + ST_BM_ITEMS - 1 ----
@@ -152,36 +132,14 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
             f32x4 acc[RB];
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (AREG) {
+            if constexpr (AREG) {
                 // the next step's items are requested before this step's products (addresses clamped to the table)
-                const float* pn = item_row(base + ST_STEP);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bnext[j] = st_load4(pn, 16 * j + 4 * lg, d, vec != 0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (16 * j < d) {
-#pragma unroll
-                        for (int s = 0; s < 4; ++s)
-#pragma unroll
-                            for (int rb = 0; rb < RB; ++rb)
-                                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[rb][j][s], bcur[j][s], acc[rb], 0, 0, 0);
-                    }
-                }
+                sp_load_frags(bnext, item_row(base + ST_STEP), lg, d, vec != 0);
+                sp_mfma_frags<RB>(acc, areg, bcur, d);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) bcur[j] = bnext[j];
             } else {
-                const float* p = item_row(base);
-                for (int j = 0; j < nkc; ++j) {
-                    const f32x4 b = st_load4(p, 16 * j + 4 * lg, d, vec != 0);
-                    f32x4 a[RB];
-#pragma unroll
-                    for (int rb = 0; rb < RB; ++rb) a[rb] = st_load4(arow[rb], 16 * j + 4 * lg, d, vec != 0);
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-#pragma unroll
-                        for (int rb = 0; rb < RB; ++rb)
-                            acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb][s], b[s], acc[rb], 0, 0, 0);
-                }
+                sp_mfma_reread<RB>(acc, arow, item_row(base), lg, d, vec != 0);
             }
             // ---- selection: acc[rb][q] = score(row rb*16 + 4*lg + q, item base + 16*wave + lc) ----
             bool pass = false;

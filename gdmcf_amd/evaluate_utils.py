@@ -84,6 +84,71 @@ def score_topk(user_emb, item_emb, k, mask_indptr=None, mask_indices=None, user_
     return (val, idx) if return_values else idx
 
 
+def score_rank(user_emb, item_emb, tgt_indptr, tgt_indices, mask_indptr=None, mask_indices=None, user_ids=None, G=None,
+               return_live=False, check_ids=True):
+    """The exact catalogue rank of named items per ranked row, without the score matrix: the counterpart of score_topk for
+    held-out targets (gdmcf_score_rank_f32: the same fused product, counting instead of selecting).  ranks[r, j] is the number
+    of items that precede target j of row r in score_topk's order (descending score, equal scores in ascending item index,
+    masked items as -inf at the end by index) -- the place the item has in score_topk(..., k = n_items)'s list, for any
+    catalogue size.  -1 for a target outside [0, n_items) and for the columns past a row's length.
+
+    Tensors as score_topk's; the target CSR (`tgt_indptr` int64 [n_rows + 1], `tgt_indices` int32, required) and the mask CSR
+    have one row per RANKED row; rows may be unsorted and hold repeats.  `G`: the number of columns; target entries past G are
+    not ranked.  G=None takes the longest target row (at least 1), which costs ONE DEVICE-TO-HOST READ of `tgt_indptr`: callers
+    that know G pass it.  Returns int32 [n_rows, G] on the device, and with `return_live` also n_live int32 [n_rows], the
+    number of unmasked items of each row.  `check_ids` as in score_topk."""
+    if tgt_indptr is None or tgt_indices is None:
+        raise ValueError("score_rank: tgt_indptr and tgt_indices are required")
+    if (mask_indptr is None) != (mask_indices is None):
+        raise ValueError("score_rank: mask_indptr and mask_indices go together")
+    _lib.require_gpu(user_emb, "user embeddings")
+    _lib.require_gpu(item_emb, "item embeddings")
+    for t, what in ((tgt_indptr, "tgt_indptr"), (tgt_indices, "tgt_indices"), (mask_indptr, "mask_indptr"),
+                    (mask_indices, "mask_indices"), (user_ids, "user_ids")):
+        if t is not None:
+            _lib.require_gpu(t, what)
+    lib = _lib.load()
+    prep = lambda t: t if (t.dtype == torch.float32 and t.stride(-1) == 1) else t.float().contiguous()
+    ue, ie = prep(user_emb.detach()), prep(item_emb.detach())
+    assert ue.dim() == 2 and ie.dim() == 2 and ue.shape[1] == ie.shape[1], "user_emb [U, d] and item_emb [I, d] must share d"
+    dev = ue.device
+    I, d = ie.shape
+    ids = None
+    if user_ids is not None:
+        ids = user_ids.to(device=dev, dtype=torch.int64).contiguous()
+        if check_ids and ids.numel():
+            lo, hi = torch.aminmax(ids)  # (one synchronising copy)
+            lo, hi = torch.stack((lo, hi)).tolist()
+            if not (0 <= lo and hi < ue.shape[0]):
+                raise IndexError("score_rank: user_ids out of range")
+    n_rows = ids.numel() if ids is not None else ue.shape[0]
+    tp = tgt_indptr.to(device=dev, dtype=torch.int64).contiguous()
+    tx = tgt_indices.to(device=dev, dtype=torch.int32).contiguous()
+    assert tp.numel() == n_rows + 1, "tgt_indptr must have one entry per ranked row plus one"
+    ip = ix = None
+    if mask_indptr is not None:
+        ip = mask_indptr.to(device=dev, dtype=torch.int64).contiguous()
+        ix = mask_indices.to(device=dev, dtype=torch.int32).contiguous()
+        assert ip.numel() == n_rows + 1, "mask_indptr must have one entry per ranked row plus one"
+    if G is None:
+        G = max(int((tp[1:] - tp[:-1]).max()), 1) if n_rows else 1  # (the one host read)
+    G = int(G)
+    if G < 1:
+        raise AssertionError("score_rank: G must be at least 1")
+    ranks = torch.empty(n_rows, G, dtype=torch.int32, device=dev)
+    live = torch.empty(n_rows, dtype=torch.int32, device=dev) if return_live else None
+    if n_rows == 0:
+        return (ranks, live) if return_live else ranks
+    if tx.numel() == 0:
+        tx = torch.zeros(1, dtype=torch.int32, device=dev)  # (a pointer for the entry; no row reads it)
+    nbytes = int(lib.gdmcf_score_rank_ws_bytes(n_rows, I, d, G))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.gdmcf_score_rank_f32(ue.data_ptr(), ue.stride(0), _lib.ptr(ids), n_rows, ie.data_ptr(), ie.stride(0), I, d,
+                                        _lib.ptr(ip), _lib.ptr(ix), tp.data_ptr(), tx.data_ptr(), G, ranks.data_ptr(),
+                                        ranks.stride(0), _lib.ptr(live), ws.data_ptr(), nbytes, _lib.stream_ptr()))
+    return (ranks, live) if return_live else ranks
+
+
 def csr_rows_to_device(csr, rows, device):
     """(indptr int64, indices int32) device tensors for `csr[rows]` (a scipy CSR history matrix)."""
     sub = csr[rows]

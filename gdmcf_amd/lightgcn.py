@@ -546,6 +546,29 @@ class LightGCN(nn.Module):
         ip, ix = _history_rows(history, ids)
         return score_topk(fu, fi, k, ip, ix, user_ids=ids, check_ids=False)
 
+    @torch.no_grad()
+    def rank_targets(self, users, targets, history=None, return_live=False):
+        """The exact catalogue rank of every target item of `users` (int64 ids, any device / array) by the propagated
+        embeddings: int32 [len(users), G] on the GPU, G = the longest target row of the asked users (at least 1; one host read),
+        ranks[b, j] = the place target j of user users[b] has in recommend(users, k = n_items, history)'s list, -1 past the
+        row's length.  `targets` and `history` (optional): scipy CSR or data_utils.DeviceCSR with one row per user of the MODEL;
+        the history of the asked users counts as -inf, as in recommend.  With `return_live` also the number of unmasked items
+        per user (int32 [len(users)]).  One propagation + evaluate_utils.score_rank: no [users, items] score matrix, no k."""
+        from .evaluate_utils import score_rank
+        if targets is None:
+            raise ValueError("rank_targets: targets (scipy CSR or DeviceCSR, one row per user) are required")
+        for m, what in ((targets, "targets"), (history, "history")):
+            if m is not None and tuple(m.shape) != (self.n_users, self.n_items):
+                raise ValueError(f"rank_targets: {what} has shape {tuple(m.shape)}, the model has {(self.n_users, self.n_items)}")
+        ids = torch.as_tensor(np.asarray(users.cpu() if torch.is_tensor(users) else users), dtype=torch.int64)
+        if ids.numel() and not (0 <= int(ids.min()) and int(ids.max()) < self.n_users):  # (on the host: no device sync)
+            raise IndexError("rank_targets: user ids out of range")
+        fu, fi, _, _ = self.propagate_through_layers()
+        ids = ids.to(fu.device)
+        ip, ix = _history_rows(history, ids)
+        tp, tx = _history_rows(targets, ids)
+        return score_rank(fu, fi, tp, tx, ip, ix, user_ids=ids, return_live=return_live, check_ids=False)
+
 
 def _history_rows(history, ids):
     """(indptr int64, indices int32) on ids' device: the rows `ids` of `history` (scipy CSR or DeviceCSR), or (None, None)."""
@@ -610,6 +633,53 @@ def get_metrics(user_emb, item_emb, n_users, n_items, train_csr, test_csr, K):
     pos = torch.searchsorted(gkeys, pkeys.reshape(-1)).clamp_(max=gkeys.numel() - 1)
     hit = (gkeys[pos] == pkeys.reshape(-1)).reshape(pkeys.shape)
     return tuple(float(t.mean()) for t in ranking_terms(hit, n_gt))
+
+
+def hits_from_ranks(ranks, K):
+    """The hit matrix [U, K] (bool) get_metrics forms from its lists, from RANKS instead: `ranks` integer [U, G] (any device), the
+    0-based catalogue rank of each test item of the user, negative = no item there; hit[u, r] = True for every rank r < K.  (The
+    r-th recommendation is a test item exactly when some test item has rank r.)"""
+    ok = (ranks >= 0) & (ranks < K)
+    hit = torch.zeros(ranks.shape[0], int(K), dtype=torch.bool, device=ranks.device)
+    rows = torch.arange(ranks.shape[0], device=ranks.device)[:, None].expand_as(ranks)
+    hit[rows[ok], ranks[ok].to(torch.int64)] = True
+    return hit
+
+
+def _check_Ks(Ks):
+    Ks = [int(K) for K in Ks]
+    if not Ks or Ks != sorted(set(Ks)) or Ks[0] < 1:
+        raise ValueError("get_metrics_at: Ks must be ascending, non-empty and >= 1")
+    return Ks
+
+
+def get_metrics_at(user_emb, item_emb, n_users, n_items, train_csr, test_csr, Ks):
+    """get_metrics at every cut-off of `Ks` (ascending) from ONE ranking pass: {K: (recall, precision, ndcg, map)}.  The users
+    with test interactions are ranked once by the fused gdmcf_score_rank_f32 (evaluate_utils.score_rank: the exact rank of every
+    test item, no score matrix, no list), and each K's hit matrix is read off the ranks (hits_from_ranks) and goes through
+    ranking_terms as get_metrics' does: for K <= 1024 each tuple equals get_metrics(..., K) exactly.  No list bounds K here: any
+    K >= 1, also above 1024 and above n_items."""
+    from .evaluate_utils import score_rank
+    Ks = _check_Ks(Ks)
+    _lib.require_gpu(user_emb, "user embeddings")
+    _lib.require_gpu(item_emb, "item embeddings")
+    dev = user_emb.device
+    test = sp.csr_matrix(test_csr).astype(np.float32)
+    test.sum_duplicates()
+    test.sort_indices()
+    assert test.shape == (n_users, n_items) and user_emb.shape[0] == n_users and item_emb.shape[0] == n_items
+    users = np.nonzero(np.diff(test.indptr) > 0)[0].astype(np.int64)
+    if len(users) == 0:
+        raise ValueError("get_metrics_at: no user has a test interaction")
+    ids = torch.from_numpy(users).to(dev)
+    ip, ix = _history_rows(train_csr, ids)
+    gt = test[users]
+    lens = np.diff(gt.indptr)
+    n_gt = torch.from_numpy(lens.astype(np.int64)).to(dev)
+    tp = torch.from_numpy(gt.indptr.astype(np.int64)).to(dev)
+    tx = torch.from_numpy(gt.indices.astype(np.int32)).to(dev)
+    ranks = score_rank(user_emb, item_emb, tp, tx, ip, ix, user_ids=ids, G=int(lens.max()), check_ids=False)  # [U_test, G]
+    return {K: tuple(float(t.mean()) for t in ranking_terms(hits_from_ranks(ranks, K), n_gt)) for K in Ks}
 
 
 class _PropagateMean(torch.autograd.Function):

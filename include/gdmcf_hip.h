@@ -56,8 +56,8 @@ int gdmcf_debug_fat_slab_plan(int M, int N, int K, int* nb, int* splits, int* cp
  * calls; gdmcf_prof_collect synchronises them and returns (tag, milliseconds, work) triples,
  * where work = algorithmic FLOPs (GEMM tags) or bytes (HBM-bound tags) of that launch.
  * Tags: 1 linear_fwd gemm, 2 loss_fwd gemm, 3 posterior gemm, 4 bwd_input gemm, 5 bwd_weight gemm,
- * 6 adamw (also normalize_rows_bwd_adamw / scatter_rows_adamw), 7 prep_input, 8 spmm, 9 topk, 12 score_topk (work = the
- * 2 n_rows n_items d FLOPs of the score product).
+ * 6 adamw (also normalize_rows_bwd_adamw / scatter_rows_adamw), 7 prep_input, 8 spmm, 9 topk, 12 score_topk and score_rank (work = the
+ * 2 n_rows n_items d FLOPs of the score product, per pass).
  * on: 1 = record, 2 = pause (stop recording, keep the records), 0 = off and discard.           */
 int gdmcf_prof_enable(int on);
 int gdmcf_prof_collect(int cap, int* tags_host, float* ms_host, double* work_host);
@@ -571,6 +571,35 @@ size_t gdmcf_score_topk_ws_bytes(int n_rows, int n_items, int d, int k);
 int gdmcf_score_topk_f32(const float* user_emb, int64_t ldu, const int64_t* user_ids, int n_rows, const float* item_emb,
                          int64_t ldi, int n_items, int d, const int64_t* mask_indptr, const int32_t* mask_indices, int k,
                          int64_t* out_idx, float* out_val, void* ws, size_t ws_bytes, void* stream);
+
+/* The exact ranks of named items from the same fused product (evaluate_utils.score_rank, LightGCN.rank_targets,
+ * lightgcn.get_metrics_at): gdmcf_score_topk_f32's product with the selection replaced by gdmcf_rank_targets_f32's counting, so
+ * neither the [n_rows, n_items] score matrix nor a k bounds it.  user_emb / user_ids / item_emb / d and the mask CSR are
+ * gdmcf_score_topk_f32's; both CSRs hold one row per ranked row of the CALL (mask_indptr, tgt_indptr int64 [n_rows + 1]; indices
+ * int32; the mask optional, the targets required).  Everything else is gdmcf_rank_targets_f32's, so that either entry can stand in
+ * for the other: rank_out[r, j] is the number of items that precede target j of row r -- larger key first, equal keys in ascending
+ * item index, a masked item carries the key of -inf, a masked target is ranked inside the -inf tail by its index; NaN, +-0 and
+ * +-inf order by the same key map.  A target outside [0, n_items) gets -1; columns from the row's length up to G get -1; target
+ * entries past G are not ranked; columns from G up to ldr are not written.  Target rows may be unsorted and hold repeats (equal
+ * targets get equal ranks); mask rows may be unsorted and hold repeats and out-of-range entries, which are skipped.  n_live_out
+ * (optional, int32 [n_rows]): n_items minus the distinct in-range mask entries of the row.
+ * A target's own score is formed by the MFMA chain, in the k order, that forms the streamed score of that item (one small launch,
+ * one wave per row and 16 targets), so rank_out[r, j] is exactly the place of the item in gdmcf_score_topk_f32's list for the
+ * same tables wherever that list reaches.
+ * Limits: any n_rows >= 1, n_items >= 1, G >= 1, 1 <= d <= 4096, ldu / ldi >= d, ldr >= G (GDMCF_E_SHAPE; d > 4096 and null or
+ * half-given pointers GDMCF_E_ARG; a short, missing or not 16-byte aligned workspace GDMCF_E_WORKSPACE / GDMCF_E_ARG).  Row tiles
+ * by G: 64 rows to G = 128, 32 to 256, 16 above, where the targets are ranked in passes of 512 that stream the items again.
+ * ws: gdmcf_score_rank_ws_bytes bytes, always needed: 8 bytes per row and target column (G rounded up to 16), 4 bytes per row,
+ * pass, item slab and gap (targets of a pass + 1), 4 bytes per row and slab -- it grows with n_rows * G (times the slab count, at
+ * most 16 and only when few rows are asked for), never with n_rows * n_items.  Integer sums only: the same bits in every run.
+ * gdmcf_debug_score_rank_plan: the plan for a shape (tests pick their G with it): returns 1 and the rows of a tile, the targets
+ * of a pass, the passes and the item slabs, or 0 (all four 0) for a shape the entry refuses.                              */
+int gdmcf_debug_score_rank_plan(int n_rows, int n_items, int G, int* tile_rows, int* pass_targets, int* passes, int* slabs);
+size_t gdmcf_score_rank_ws_bytes(int n_rows, int n_items, int d, int G);
+int gdmcf_score_rank_f32(const float* user_emb, int64_t ldu, const int64_t* user_ids, int n_rows, const float* item_emb,
+                         int64_t ldi, int n_items, int d, const int64_t* mask_indptr, const int32_t* mask_indices,
+                         const int64_t* tgt_indptr, const int32_t* tgt_indices, int G, int32_t* rank_out, int64_t ldr,
+                         int32_t* n_live_out, void* ws, size_t ws_bytes, void* stream);
 
 /* Ranking metrics of reference evaluate_utils.py:6-52 (computeTopNAccuracy) on the device: per user and per cut-off
  * N of topN_host (ascending, at most 8) the four terms precision = hits/N, recall = hits/|GT|, NDCG = dcg/idcg,
