@@ -191,6 +191,7 @@ int gdmcf_graph_state_bind(const void* state_dev) {
 
 int gdmcf_graph_state_init(void* state_host, uint64_t prep_offset, uint64_t ts_offset, int64_t adam_step, int64_t table_first,
                            int64_t table_len, const void* hyper_table_dev) {
+    GD_CHECK_OFFSET(prep_offset | ts_offset, "graph_state_init");
     GD_CHECK_ARG(state_host && hyper_table_dev && table_len > 0, "graph_state_init: null pointer / empty table");
     GdStepState* st = static_cast<GdStepState*>(state_host);
     st->prep_offset = prep_offset; st->ts_offset = ts_offset; st->adam_step = adam_step; st->table_first = table_first;

@@ -287,6 +287,7 @@ extern "C" {
 int gdmcf_bpr_sample_f32(const int64_t* indptr, const int32_t* indices, const int64_t* users, int B, int n_users, int n_items,
                          uint64_t seed, uint64_t offset, int64_t* pos, int64_t* neg, int32_t* flag, void* stream) {
     GD_CHECK_SHAPE(B > 0 && n_users > 0 && n_items > 0, "bpr_sample: bad shape");
+    GD_CHECK_OFFSET(offset, "bpr_sample");
     GD_CHECK_ARG(indptr && indices && users && pos && neg, "bpr_sample: null pointer");
     hipLaunchKernelGGL(bpr_sample_kernel, dim3(gd_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, indptr, indices, users, B,
                        n_users, n_items, seed, offset, pos, neg, flag);

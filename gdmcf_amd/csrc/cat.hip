@@ -407,6 +407,7 @@ int gdmcf_cat_prep_input_f32(const float* x, int64_t ldx, const float* xU, int64
     GD_CHECK_SHAPE(ldxin >= (int64_t)I + E && (ldxin % 4) == 0 && gd_aligned16(xin), "cat_prep_input: xin must be 16B aligned, ld%4==0, ld >= I+E");
     GD_CHECK_SHAPE(ldxt >= I && (ldxt % 4) == 0 && gd_aligned16(xt_out), "cat_prep_input: x_t must be 16B aligned, ld%4==0, ld >= I");
     GD_CHECK_SHAPE(ldx >= I && ldu >= 2 * (int64_t)I, "cat_prep_input: ldx < I or ldu < 2I");
+    GD_CHECK_OFFSET(offset, "cat_prep_input");
     GD_CHECK_ARG(x && xU && xin && xt_out && cat_w && cat_b && ts && emb_w && emb_b, "cat_prep_input: null pointer");
     GD_CHECK_ARG((ca == nullptr) == (cb == nullptr), "cat_prep_input: ca/cb must both be set or both NULL");
     GD_CHECK_ARG(noise_mode >= 0 && noise_mode <= 2 && drop_mode >= 0 && drop_mode <= 2, "cat_prep_input: bad mode");
@@ -444,6 +445,7 @@ int gdmcf_cat_prep_input_csr_f32(const int64_t* indptr, const int32_t* indices, 
     GD_CHECK_SHAPE(ldxin >= (int64_t)I + E && (ldxin % 4) == 0 && gd_aligned16(xin), "cat_prep_input_csr: xin must be 16B aligned, ld%4==0, ld >= I+E");
     GD_CHECK_SHAPE(ldxt >= I && (ldxt % 4) == 0 && gd_aligned16(xt_out), "cat_prep_input_csr: x_t must be 16B aligned, ld%4==0, ld >= I");
     GD_CHECK_SHAPE(ldx0bits >= (I + 31) / 32 && ldclsbits >= (I + 31) / 32, "cat_prep_input_csr: ldx0bits / ldclsbits < ceil(I/32)");
+    GD_CHECK_OFFSET(offset_noise | offset_prep, "cat_prep_input_csr");
     GD_CHECK_ARG(indptr && indices && rows, "cat_prep_input_csr: CSR arrays / row ids missing");
     GD_CHECK_ARG(xin && xt_out && x0bits_out && clsbits_out && cat_w && cat_b && ts && emb_w && emb_b, "cat_prep_input_csr: null pointer");
     GD_CHECK_ARG(sampled ? lds >= I : ts_U != nullptr, "cat_prep_input_csr: classes / ts_U missing or lds < I");
@@ -481,6 +483,7 @@ int gdmcf_cat_grad_f32(const float* dxin, int64_t lddx, const float* xt, int64_t
                        const uint8_t* keep, int64_t ldkeep, float drop_p, uint64_t seed, uint64_t offset, int B, int I, void* ws,
                        size_t ws_bytes, float* grad_w, float* grad_b, void* stream) {
     GD_CHECK_SHAPE(B > 0 && I > 0 && I <= 0x3FFFFFFF && lddx >= I && ldxt >= I && ldu >= 2 * (int64_t)I, "cat_grad: bad shape");
+    GD_CHECK_OFFSET(offset, "cat_grad");
     GD_CHECK_ARG(dxin && xt && xU && grad_w && grad_b, "cat_grad: null pointer");
     GD_CHECK_ARG(drop_mode >= 0 && drop_mode <= 2 && (drop_mode != 1 || (keep && ldkeep >= I)), "cat_grad: bad mode / keep-mask missing");
     GD_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "cat_grad: dropout p out of range");
@@ -510,6 +513,7 @@ int gdmcf_cat_grad_bits_f32(const float* dxin, int64_t lddx, const float* xt, in
                             float* grad_b, void* stream) {
     GD_CHECK_SHAPE(B > 0 && I > 0 && I <= 0x3FFFFFFF && lddx >= I && ldxt >= I, "cat_grad_bits: bad shape");
     GD_CHECK_SHAPE(ldx0bits >= (I + 31) / 32 && ldclsbits >= (I + 31) / 32, "cat_grad_bits: ldx0bits / ldclsbits < ceil(I/32)");
+    GD_CHECK_OFFSET(offset, "cat_grad_bits");
     GD_CHECK_ARG(dxin && xt && x0bits && clsbits && grad_w && grad_b, "cat_grad_bits: null pointer");
     GD_CHECK_ARG(drop_mode >= 0 && drop_mode <= 2 && (drop_mode != 1 || (keep && ldkeep >= I)), "cat_grad_bits: bad mode / keep-mask missing");
     GD_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "cat_grad_bits: dropout p out of range");

@@ -27,6 +27,9 @@ void gdmcf_set_error(const char* fmt, ...);
         }                                    \
     } while (0)
 
+// A Philox offset has 56 bits: 32 in counter word w, 24 above the stream id in word z (draws.h: gd_counter).
+#define GD_CHECK_OFFSET(offset, who) GD_CHECK_SHAPE(((uint64_t)(offset) >> 56) == 0, who ": Philox offset must be below 2^56")
+
 static inline int gd_launch_status(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -10,7 +10,10 @@
 #include "common.h"
 
 // ---- streams: counter word z of Philox4x32-10 (common.h), one id per kind of draw --------------------------------------------
-// counter = (position along the row, row, STREAM, offset); the key is the seed.
+// counter = (position along the row, row, STREAM | (offset >> 32) << 8, (uint32)offset); the key is the seed.  Stream ids stay
+// below 256 and offsets below 2^56 (GD_CHECK_OFFSET, common.h): the offset's bits 32..55 ride in word z above the stream id, so
+// callers may keep disjoint draw regions apart by the offset's high bits (gaussian_diffusion.py: 1 << 40, 1 << 41, 1 << 42) and
+// every draw at an offset below 2^32 has the counter (position, row, stream, offset) it always had.
 enum : uint32_t {
     GD_STREAM_NOISE = 0,         // q_sample's N(0,1): prep_input.hip (xt4), cat.hip (cat_prep_kernel), randn_kernel with stream_id 0
     GD_STREAM_DROPOUT = 1,       // keep-masks: prep_input.hip, cat.hip (builder and gradient)
@@ -30,7 +33,7 @@ constexpr int PREP_G = 4;
 __device__ __forceinline__ uint2 gd_philox_key(uint64_t seed) { return make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)); }
 // the counter of the block of four words at position x of row b, and the block
 __device__ __forceinline__ uint4 gd_counter(uint32_t x, int b, uint32_t stream, uint64_t offset) {
-    return make_uint4(x, (uint32_t)b, stream, (uint32_t)offset);
+    return make_uint4(x, (uint32_t)b, stream | ((uint32_t)(offset >> 32) << 8), (uint32_t)offset);
 }
 __device__ __forceinline__ uint4 gd_philox_block(uint32_t x, int b, uint32_t stream, uint64_t offset, uint2 key) {
     return philox4x32_10(gd_counter(x, b, stream, offset), key);

@@ -220,6 +220,7 @@ int gdmcf_sample_timesteps(const double* Lt_history, const int64_t* Lt_count, in
                            double uniform_prob, uint64_t seed, uint64_t offset, int64_t* ts, double* pt, double* p_out,
                            void* stream) {
     GD_CHECK_SHAPE(B > 0 && T > 0 && H > 0, "sample_timesteps: bad shape");
+    GD_CHECK_OFFSET(offset, "sample_timesteps");
     GD_CHECK_ARG(T <= 4096, "sample_timesteps: T > 4096 unsupported");
     hipLaunchKernelGGL(sample_timesteps_kernel, dim3(1), dim3(256), (size_t)T * 16, (hipStream_t)stream, Lt_history,
                        Lt_count, T, H, B, uniform_prob, seed, offset, ts, pt, p_out, t_gd_step_state);

@@ -184,6 +184,7 @@ int gdmcf_onehot_noise_f32(const float* x0, int64_t ldx, const int64_t* ts, int 
                            const uint8_t* sampled, int64_t lds, uint64_t seed, uint64_t offset, float* xU, int64_t ldu,
                            uint8_t* sampled_out, int64_t ldso, void* stream) {
     GD_CHECK_SHAPE(B > 0 && I > 0 && ldx >= I && ldu >= 2 * (int64_t)I, "onehot_noise: bad shape");
+    GD_CHECK_OFFSET(offset, "onehot_noise");
     GD_CHECK_ARG(x0 && xU && (sampled ? lds >= I : ts != nullptr) && (!sampled_out || ldso >= I),
                  "onehot_noise: null pointer / bad leading dimension");
     {
@@ -197,6 +198,7 @@ int gdmcf_onehot_noise_f32(const float* x0, int64_t ldx, const int64_t* ts, int 
 
 int gdmcf_randn_f32(float* out, int64_t ld, int rows, int cols, int stream_id, uint64_t seed, uint64_t offset, void* stream) {
     GD_CHECK_SHAPE(rows > 0 && cols > 0 && ld >= cols, "randn: bad shape");
+    GD_CHECK_OFFSET(offset, "randn");
     GD_CHECK_ARG(out && stream_id >= 0 && stream_id < 256, "randn: null pointer / bad stream id");
     {
         GdProfScope prof(11, (double)rows * cols * 4.0, (hipStream_t)stream);  // algorithmic bytes: the store
@@ -222,6 +224,7 @@ int gdmcf_graph_guided_step_u8(uint8_t* graph, int64_t ldg, const int64_t* ts, i
                                int user_guided, uint64_t seed, uint64_t offset, uint8_t* sampled_out, int64_t ldso,
                                uint8_t* pick_out, void* stream) {
     GD_CHECK_SHAPE(B > 0 && I > 0 && ldg >= I, "graph_guided_step: bad shape");
+    GD_CHECK_OFFSET(offset, "graph_guided_step");
     GD_CHECK_ARG(graph && (sampled_in ? lds >= I : ts != nullptr) && (!sampled_out || ldso >= I),
                  "graph_guided_step: null pointer / bad leading dimension");
     GD_CHECK_ARG(!user_guided || pick_in || degree_prob, "graph_guided_step: user_guided needs pick_in or degree_prob");

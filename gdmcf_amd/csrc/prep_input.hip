@@ -396,6 +396,7 @@ int gdmcf_dnn_prep_input_f32(const float* x, int64_t ldx, const int64_t* ts, con
     GD_CHECK_SHAPE(B > 0 && I > 0 && E >= 0, "prep_input: empty batch");
     GD_CHECK_SHAPE(ldxin >= I + E && (ldxin % 4) == 0 && gd_aligned16(xin), "prep_input: xin must be 16B aligned, ld%4==0");
     GD_CHECK_SHAPE(ldx >= I, "prep_input: ldx < I");
+    GD_CHECK_OFFSET(offset, "prep_input");
     PrepArgs a;
     const int rc = prep_args_common(a, "prep_input", ts, ca, cb, noise_mode, noise, ldn, drop_mode, keep, ldkeep, drop_p, seed,
                                     offset, emb_w, emb_b, E, B, I, xin, ldxin, temb_out);
@@ -425,6 +426,7 @@ int gdmcf_dnn_prep_input_csr_f32(const int64_t* indptr, const int32_t* indices, 
                                  int64_t ldxin, float* temb_out, uint32_t* bits_out, int64_t ldbits, void* stream) {
     GD_CHECK_SHAPE(B > 0 && I > 0 && E >= 0, "prep_input_csr: empty batch");
     GD_CHECK_SHAPE(ldxin >= I + E && (ldxin % 4) == 0 && gd_aligned16(xin), "prep_input_csr: xin must be 16B aligned, ld%4==0");
+    GD_CHECK_OFFSET(offset, "prep_input_csr");
     GD_CHECK_ARG(indptr && indices && rows, "prep_input_csr: CSR arrays / row ids missing");
     GD_CHECK_ARG(!bits_out || ldbits >= (I + 31) / 32, "prep_input_csr: ldbits < ceil(I/32)");
     PrepArgs a;
@@ -453,6 +455,7 @@ int gdmcf_onehot_prep_input_csr_f32(const int64_t* indptr, const int32_t* indice
     const int I2 = 2 * I;
     GD_CHECK_SHAPE(ldxin >= (int64_t)I2 + E && (ldxin % 4) == 0 && gd_aligned16(xin),
                    "onehot_prep_input_csr: xin must be 16B aligned, ld%4==0, ld >= 2I+E");
+    GD_CHECK_OFFSET(offset_noise | offset_prep, "onehot_prep_input_csr");
     GD_CHECK_ARG(indptr && indices && rows, "onehot_prep_input_csr: CSR arrays / row ids missing");
     GD_CHECK_ARG(!bits_out || ldbits >= (I + 31) / 32, "onehot_prep_input_csr: ldbits < ceil(I/32)");
     GD_CHECK_ARG((sampled ? lds >= I : ts_U != nullptr) && (!sampled_out || ldso >= I),

@@ -18,6 +18,13 @@
  *   - no function allocates device memory; scratch is passed in as `ws`/`ws_bytes`
  *     (query the size with the matching *_ws_bytes function) so everything is
  *     hipGraph-capturable.
+ *   - random draws: every in-kernel draw is a function of words of ONE Philox4x32-10 block, named below by its counter
+ *     (position, row, stream, offset) and the key `seed` (low word, high word).  The four counter words are
+ *         (position, row, stream | (offset >> 32) << 8, offset & 0xFFFFFFFF):
+ *     stream ids are below 256 and a Philox `offset` is below 2^56 (GDMCF_E_SHAPE otherwise, from every entry that takes
+ *     one) -- its bits 32..55 sit above the stream id, so offsets that differ only in their high bits draw different
+ *     numbers, and an offset below 2^32 gives the counter (position, row, stream, offset) itself.  Checkpoints persist
+ *     (seed, offset): the mapping is a stored format.
  */
 #ifndef GDMCF_HIP_H
 #define GDMCF_HIP_H
@@ -159,8 +166,8 @@ int gdmcf_onehot_prep_input_csr_f32(const int64_t* indptr, const int32_t* indice
  * replaces `noise = th.randn_like(x_start)` where the noise itself is needed in memory: the eps TARGET of
  * training_losses (gaussian_diffusion.py:328-331, :844-846) and the reverse loop's `noise = th.randn_like(x_t)`
  * (:210-217, :696-703).  out[b, i] (float32 [rows, ld]) = normal (i & 3) of the Philox4x32-10 block with counter
- * (i >> 2, b, stream_id, (uint32)offset), key seed: Box-Muller on the block's (x, y) and (z, w) words, hardware log / sqrt /
- * sin / cos.  stream_id 0 is the stream gdmcf_dnn_prep_input(_csr)_f32 draws in place (noise_mode 2): a buffer filled here
+ * (i >> 2, b, stream_id, offset) (all 56 offset bits count: Conventions), key seed: Box-Muller on the block's (x, y) and
+ * (z, w) words, hardware log / sqrt / sin / cos.  stream_id 0 is the stream gdmcf_dnn_prep_input(_csr)_f32 draws in place (noise_mode 2): a buffer filled here
  * with the same (seed, offset) and handed to it as given noise (noise_mode 1) yields the same x_t bit for bit.  Stream ids
  * 1-3, 5, 6 belong to dropout / timestep / one-hot / graph draws; 4 and 7 are free for callers (eps target, step noise).  */
 int gdmcf_randn_f32(float* out, int64_t ld, int rows, int cols, int stream_id, uint64_t seed, uint64_t offset, void* stream);
@@ -701,7 +708,7 @@ int gdmcf_scale_f32(const float* acc, int64_t n, float scale, float* out, void* 
  * gdmcf_bpr_sample_f32 replaces the reference's per-user `random.choice(x)` / `sample_neg(x)` (lightGCN.py:225-229,
  * :244-246): for each users[j] one interacted and one non-interacted item of the training CSR (indptr int64 [n_users+1],
  * indices int32, every row sorted and free of duplicates), one thread per triple, Philox4x32-10 with counter
- * (j, 0, 7, (uint32)offset) and key seed -- stream id 7.  pos[j] is uniform over the row; neg[j] is uniform over the
+ * (j, 0, 7, offset) and key seed -- stream id 7.  pos[j] is uniform over the row; neg[j] is uniform over the
  * n_items - deg items NOT in the row, drawn exactly (no rejection loop): r uniform in [0, n_items - deg), i = the smallest
  * index with row[i] - i > r (binary search; i = deg when there is none), neg = r + i -- the distribution of sample_neg.
  * Integers come from 32-bit words by multiply-high, floor(w n / 2^32): the bias of any outcome is at most n / 2^32.

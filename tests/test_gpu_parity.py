@@ -639,7 +639,8 @@ def test_lt_history_kernel_matches_serial_fifo():
     from gdmcf_amd import _lib
     lib = _lib.load()
     g = torch.Generator().manual_seed(0)
-    for T, H, B in [(3, 4, 50), (5, 10, 400), (40, 10, 16), (7, 3, 1), (2, 10, 257)]:
+    # (1000, 10, 300): the production schedule length -- 88 KB of dynamic LDS, above the 48 KiB default limit
+    for T, H, B in [(3, 4, 50), (5, 10, 400), (40, 10, 16), (7, 3, 1), (2, 10, 257), (1000, 10, 300)]:
         od = O.GaussianDiffusion(O.ModelMeanType.START_X, "linear", 0.1, 0.001, 0.01, T, history_num_per_term=H)
         hist = torch.zeros(T, H, dtype=torch.float64, device=DEV)
         cnt = torch.zeros(T, dtype=torch.int64, device=DEV)
