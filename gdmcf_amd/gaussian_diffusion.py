@@ -95,13 +95,23 @@ class GaussianDiffusion(nn.Module):
     def SNR(self, t):
         return self.alphas_cumprod[t] / (1 - self.alphas_cumprod[t])
 
+    _draw_seed = None  # the key a loaded checkpoint carried (checkpoint.load_diffusion_state); None: torch's seed, see draw_seed
+
+    def draw_seed(self):
+        """The Philox key of every draw this object makes (timesteps, the eps target's and the reverse loop's normals, q_sample's
+        noise, the one-hot noise, the degree-guided graph picks): the one a checkpoint loaded, if any -- a resumed run continues
+        the streams it was saved in, however its process is seeded -- otherwise torch.initial_seed(), read at every call."""
+        if self._draw_seed is not None:
+            return self._draw_seed
+        return int(torch.initial_seed()) & (2 ** 63 - 1)
+
     def _draw_noise(self, like, eps_mode=False, stream_id=4):
         """`th.randn_like(x)` of the reference (:328-331 the eps target, :210-217 / :696-703 the reverse loop's noise) as a device
-        draw: gdmcf_randn_f32 (Philox4x32-10 keyed by torch.initial_seed(), one offset per call) unless rng == "torch"."""
+        draw: gdmcf_randn_f32 (Philox4x32-10 keyed by draw_seed(), one offset per call) unless rng == "torch"."""
         if self.rng == "torch":
             return torch.randn(like.shape, dtype=torch.float32, device=like.device)
         self._randn_calls = getattr(self, "_randn_calls", 0) + 1
-        return _lib.philox_randn(like.shape, like.device, int(torch.initial_seed()) & (2 ** 63 - 1), self._randn_calls, stream_id)
+        return _lib.philox_randn(like.shape, like.device, self.draw_seed(), self._randn_calls, stream_id)
 
     def _extract_into_tensor(self, arr, timesteps, broadcast_shape):
         res = arr.to(timesteps.device)[timesteps].float()
@@ -129,7 +139,7 @@ class GaussianDiffusion(nn.Module):
             self._ts_calls = getattr(self, "_ts_calls", 0) + 1
             _lib.check(_lib.load().gdmcf_sample_timesteps(
                 self.Lt_history.data_ptr(), self.Lt_count.data_ptr(), self.steps, self.history_num_per_term,
-                batch_size, float(uniform_prob), int(torch.initial_seed()) & (2 ** 63 - 1), self._ts_calls,
+                batch_size, float(uniform_prob), self.draw_seed(), self._ts_calls,
                 t.data_ptr(), pt.data_ptr(), None, _lib.stream_ptr()))
             return t, pt
         elif method == "uniform":
@@ -152,7 +162,7 @@ class GaussianDiffusion(nn.Module):
         self._q_calls = getattr(self, "_q_calls", 0) + 1
         # the input builder without dropout, normalisation and embedding columns (E = 0)
         prep_input(_lib.load(), x, I, t, self._t32["sqrt_ab"], self._t32["sqrt_1mab"], nz, None, 0.0, False,
-                   int(torch.initial_seed()) & (2 ** 63 - 1), (1 << 40) + self._q_calls, False, None, 0, out, None, None, None,
+                   self.draw_seed(), (1 << 40) + self._q_calls, False, None, 0, out, None, None, None,
                    _lib.stream_ptr())
         return out[:, :I]
 
@@ -429,7 +439,7 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         self._noise_calls = getattr(self, "_noise_calls", 0) + 1
         _lib.check(_lib.load().gdmcf_onehot_noise_f32(
             x0.data_ptr(), x0.stride(0), ts.data_ptr(), B, I, float(self.discrete), None, 0,
-            int(torch.initial_seed()) & (2 ** 63 - 1), (1 << 41) + self._noise_calls, scratch.data_ptr(), scratch.stride(0),
+            self.draw_seed(), (1 << 41) + self._noise_calls, scratch.data_ptr(), scratch.stride(0),
             sampled.data_ptr(), sampled.stride(0), _lib.stream_ptr()))
         return torch.nn.functional.one_hot(sampled.long(), num_classes=2)
 
@@ -637,7 +647,7 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         _lib.check(_lib.load().gdmcf_graph_guided_step_u8(
             graph.data_ptr(), graph.stride(0), t.data_ptr(), B, I, float(self.discrete), _lib.ptr(sampled),
             sampled.stride(0) if sampled is not None else 0, _lib.ptr(pick), _lib.ptr(degp), int(self.user_guided),
-            int(torch.initial_seed()) & (2 ** 63 - 1), (1 << 42) + self._noise_calls, _lib.ptr(sampled_out),
+            self.draw_seed(), (1 << 42) + self._noise_calls, _lib.ptr(sampled_out),
             sampled_out.stride(0) if sampled_out is not None else 0, _lib.ptr(pick_out), _lib.stream_ptr()))
         return graph
 
