@@ -5,7 +5,8 @@ from .DNN import DNN, timestep_embedding  # noqa: F401
 from .gaussian_diffusion import GaussianDiffusion, GaussianDiffusionDiscrete, ModelMeanType  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
 from .evaluate_utils import computeTopNAccuracy, computeTopNAccuracy_device, masked_topk, print_results, score_rank, score_topk  # noqa: F401
-from .lightgcn import BPRTrainer, LightGCN  # noqa: F401
+from .bpr import BPRTrainer  # noqa: F401
+from .lightgcn import LightGCN  # noqa: F401
 from .onehot import DNNOneHot  # noqa: F401
 from .cat import DNNCat  # noqa: F401
 from .onehot_embedding import DNNOneHotEmbedding, nt_xent_loss_grad  # noqa: F401

@@ -1,4 +1,4 @@
-// The order every ranking kernel shares (topk_spmm.hip: the masked top-k; rank.hip: the ranks of named items): an item's key is
+// The order every ranking kernel shares (topk.hip: the masked top-k; rank.hip: the ranks of named items): an item's key is
 // the order-preserving image of its score, or of -inf when the item is masked; larger key first, equal keys in ascending item
 // index -- as one 64-bit pair (key, ~index), larger pair first.  NaN, +-0 and +-inf order by their bits under this one map.
 #pragma once

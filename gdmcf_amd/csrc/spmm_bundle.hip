@@ -1,8 +1,8 @@
 // LightGCN propagation, second-generation CSR SpMM (reference lightGCN.py:184-189): ONE launch per layer over a
-// host-built, statically balanced schedule (gdmcf_amd/lightgcn.py:spmm_bundle_plan).
+// host-built, statically balanced schedule (gdmcf_amd/spmm_schedule.py:spmm_bundle_plan).
 //
 // Why: with the gathered table confined to 0.5 MB (every gather an L2 hit) the first-generation kernels
-// (topk_spmm.hip: short rows / long pieces / combine, three launches) still took 43 us per Yelp-shape layer
+// (spmm_csr.hip: short rows / long pieces / combine, three launches) still took 43 us per Yelp-shape layer
 // (tools/spmm_ceiling.py) -- the time was in the kernels' shape, not in the cache misses: four rows of unrelated
 // length shared a wave (the wave runs for the longest), every wave lived for four rows, three launches ramped up and
 // drained one after the other.  Here
@@ -17,17 +17,10 @@
 // Accumulation order is fixed by the schedule -> bit-identical run to run; rows cut into several pieces write
 // float partials that spmm_combine adds in slot order (no atomics).
 #include "common.h"
+#include "spmm.h"
 #include <stdlib.h>
 
 namespace {
-
-constexpr int SPMM_MAX_ADD = 8;
-struct SpmmAdd {
-    const float* p[SPMM_MAX_ADD];
-    int n;
-    int64_t ld;
-    float scale;
-};
 
 struct SpmmBundlePlan {
     const int32_t* wdesc;  // [n_waves][4] = first/last+1 piece, first/last+1 bundle of the wave
@@ -158,6 +151,7 @@ __global__ __launch_bounds__(256) void spmm_bundle_kernel(const SpmmBundlePlan p
                 if (slot_st >= 0) {
                     *reinterpret_cast<f32x4*>(partial + (int64_t)slot_st * d + gl * 4) = acc;
                 } else {
+                    // spmm_store_row, written out: through the helper the WIDE instantiations at LPR = 4 take two more VGPRs
                     for (int k = 0; k < add.n; ++k) acc += *reinterpret_cast<const f32x4*>(add.p[k] + (int64_t)row_st * add.ld + gl * 4);
                     *reinterpret_cast<f32x4*>(Y + (int64_t)row_st * ldy + gl * 4) = acc * add.scale;
                 }
@@ -223,10 +217,7 @@ __global__ __launch_bounds__(256) void spmm_bundle_kernel(const SpmmBundlePlan p
         cA = cB; wA = wB;
         // pin the rotated values here: the compiler otherwise sinks the moves / selects below the store
         asm volatile("" : "+v"(begA), "+v"(lenA), "+v"(rowA), "+v"(mxA), "+v"(begB), "+v"(lenB), "+v"(rowB), "+v"(mxB), "+v"(cA), "+v"(wA));
-        if (row_st >= 0) {
-            for (int k = 0; k < add.n; ++k) acc += *reinterpret_cast<const f32x4*>(add.p[k] + (int64_t)row_st * add.ld + gl * 4);
-            *reinterpret_cast<f32x4*>(Y + (int64_t)row_st * ldy + gl * 4) = acc * add.scale;
-        }
+        if (row_st >= 0) spmm_store_row(acc, add, Y, ldy, row_st, gl);
     }
 #undef GD_DESC
 #undef GD_BATCH
@@ -234,7 +225,7 @@ __global__ __launch_bounds__(256) void spmm_bundle_kernel(const SpmmBundlePlan p
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Third generation: the wave streams its nonzeros.  The schedule is the one above, but the host also re-orders the
-// (col, val) pairs into the order the waves gather them (gdmcf_amd/lightgcn.py:spmm_stream_pack): a wave reads ONE
+// (col, val) pairs into the order the waves gather them (gdmcf_amd/spmm_schedule.py:spmm_stream_pack): a wave reads ONE
 // contiguous run, 64 entries (= LPR steps of G gathers) per load, whatever rows they belong to, and a unit (a piece or a
 // bundle) is just "so many steps, then write these rows".  Why: vmcnt retires in order, so a load that goes to HBM (the
 // col/val of the next row, a descriptor) holds back every younger L2-hit gather behind it -- a wave that chases row
@@ -341,15 +332,13 @@ __global__ __launch_bounds__(256) void spmm_stream_kernel(const SpmmStreamPlan p
                 if (s_st >= 0) {
                     __builtin_nontemporal_store(acc, reinterpret_cast<f32x4*>(partial + (int64_t)s_st * d + gl * 4));
                 } else {
-                    for (int k = 0; k < add.n; ++k) acc += *reinterpret_cast<const f32x4*>(add.p[k] + (int64_t)a_st * add.ld + gl * 4);
-                    __builtin_nontemporal_store(acc * add.scale, reinterpret_cast<f32x4*>(Y + (int64_t)a_st * ldy + gl * 4));
+                    spmm_store_row<true>(acc, add, Y, ldy, a_st, gl);
                 }
             }
         } else if (a_st >= 0) {  // bundle: lane group g owns row a_st (bit 30: the row is empty, discard what was gathered)
             const int r = a_st & 0x3FFFFFFF;
             if (a_st & 0x40000000) acc = f32x4{0.f, 0.f, 0.f, 0.f};
-            for (int k = 0; k < add.n; ++k) acc += *reinterpret_cast<const f32x4*>(add.p[k] + (int64_t)r * add.ld + gl * 4);
-            __builtin_nontemporal_store(acc * add.scale, reinterpret_cast<f32x4*>(Y + (int64_t)r * ldy + gl * 4));
+            spmm_store_row<true>(acc, add, Y, ldy, r, gl);
         }
     }
     asm volatile("" ::"v"(t0), "v"(t1), "v"(t2), "v"(t3));  // the touches are only waited for here
@@ -390,10 +379,7 @@ __global__ __launch_bounds__(256) void spmm_bundle_combine_kernel(const int32_t*
         s.z += __shfl_xor(s.z, o);
         s.w += __shfl_xor(s.w, o);
     }
-    if (g == 0) {
-        for (int q = 0; q < add.n; ++q) s += *reinterpret_cast<const f32x4*>(add.p[q] + (int64_t)r * add.ld + gl * 4);
-        *reinterpret_cast<f32x4*>(Y + (int64_t)r * ldy + gl * 4) = s * add.scale;
-    }
+    if (g == 0) spmm_store_row(s, add, Y, ldy, r, gl);
 }
 
 template <int LPR>
@@ -433,16 +419,9 @@ extern "C" int gdmcf_spmm_bundled_f32(const int32_t* wdesc, int n_waves, const i
     GD_CHECK_ARG(n_cut == 0 || (crow && cptr && partial_ws), "spmm_bundled: cut rows need crow/cptr/partial_ws");
     GD_CHECK_ARG(n_add >= 0 && n_add <= SPMM_MAX_ADD && (n_add == 0 || (addends_host && ld_add >= d)), "spmm_bundled: bad addends");
     const int lpr = d / 4;
-    bool ok = (d % 4 == 0) && (lpr == 2 || lpr == 4 || lpr == 8 || lpr == 16 || lpr == 32 || lpr == 64) && (ldx % 4 == 0) &&
-              (ldy % 4 == 0) && gd_aligned16(X) && gd_aligned16(Y) && (partial_ws == nullptr || gd_aligned16(partial_ws));
-    SpmmAdd add = {};
-    add.n = n_add;
-    add.ld = ld_add;
-    add.scale = scale;
-    for (int k = 0; k < n_add; ++k) {
-        add.p[k] = addends_host[k];
-        ok = ok && gd_aligned16(add.p[k]) && (ld_add % 4 == 0);
-    }
+    SpmmAdd add;
+    const bool ok = spmm_fill_add(add, addends_host, n_add, ld_add, scale) && (d % 4 == 0) && spmm_lpr_ok(lpr) && (ldx % 4 == 0) &&
+                    (ldy % 4 == 0) && gd_aligned16(X) && gd_aligned16(Y) && (partial_ws == nullptr || gd_aligned16(partial_ws));
     if (!ok) {
         gdmcf_set_error("spmm_bundled: needs d in {8,16,32,64,128,256} and 16-byte aligned rows (use gdmcf_spmm_csr_f32 otherwise)");
         return GDMCF_E_UNSUPPORTED;
@@ -453,12 +432,7 @@ extern "C" int gdmcf_spmm_bundled_f32(const int32_t* wdesc, int n_waves, const i
     {
         GdProfScope prof(8, alg_bytes, s);
 #define GD_GO(L) launch_bundle<L>(n_blocks, s, pl, col, val, nnz, X, ldx, n_x_rows, Y, ldy, partial_ws, d, add, crow, cptr, n_cut)
-        if (lpr == 16) GD_GO(16);
-        else if (lpr == 8) GD_GO(8);
-        else if (lpr == 32) GD_GO(32);
-        else if (lpr == 64) GD_GO(64);
-        else if (lpr == 4) GD_GO(4);
-        else GD_GO(2);
+        GD_SPMM_FOR_LPR(lpr, GD_GO);
 #undef GD_GO
     }
     return gd_launch_status("spmm_bundled");
@@ -497,17 +471,10 @@ extern "C" int gdmcf_spmm_stream_f32(const int32_t* wdesc, int n_waves, const in
     GD_CHECK_ARG(n_cut == 0 || (crow && cptr && partial_ws), "spmm_stream: cut rows need crow/cptr/partial_ws");
     GD_CHECK_ARG(n_add >= 0 && n_add <= SPMM_MAX_ADD && (n_add == 0 || (addends_host && ld_add >= d)), "spmm_stream: bad addends");
     const int lpr = d / 4;
-    bool ok = (d % 4 == 0) && (lpr == 2 || lpr == 4 || lpr == 8 || lpr == 16 || lpr == 32 || lpr == 64) && (ldx % 4 == 0) &&
-              (ldy % 4 == 0) && gd_aligned16(X) && gd_aligned16(Y) && (partial_ws == nullptr || gd_aligned16(partial_ws)) &&
-              ((reinterpret_cast<uintptr_t>(cw) & 7u) == 0);
-    SpmmAdd add = {};
-    add.n = n_add;
-    add.ld = ld_add;
-    add.scale = scale;
-    for (int k = 0; k < n_add; ++k) {
-        add.p[k] = addends_host[k];
-        ok = ok && gd_aligned16(add.p[k]) && (ld_add % 4 == 0);
-    }
+    SpmmAdd add;
+    const bool ok = spmm_fill_add(add, addends_host, n_add, ld_add, scale) && (d % 4 == 0) && spmm_lpr_ok(lpr) && (ldx % 4 == 0) &&
+                    (ldy % 4 == 0) && gd_aligned16(X) && gd_aligned16(Y) && (partial_ws == nullptr || gd_aligned16(partial_ws)) &&
+                    ((reinterpret_cast<uintptr_t>(cw) & 7u) == 0);
     if (!ok) {
         gdmcf_set_error("spmm_stream: needs d in {8,16,32,64,128,256} and 16-byte aligned rows (use gdmcf_spmm_csr_f32 otherwise)");
         return GDMCF_E_UNSUPPORTED;
@@ -527,12 +494,7 @@ extern "C" int gdmcf_spmm_stream_f32(const int32_t* wdesc, int n_waves, const in
             hipLaunchKernelGGL(spmm_bundle_combine_kernel<L>, dim3(gd_cdiv(n_cut, 4)), dim3(256), 0, s, crow, cptr, n_cut, partial_ws,  \
                                d, Y, ldy, add);                                                                                         \
     } while (0)
-        if (lpr == 16) GD_GO(16);
-        else if (lpr == 8) GD_GO(8);
-        else if (lpr == 32) GD_GO(32);
-        else if (lpr == 64) GD_GO(64);
-        else if (lpr == 4) GD_GO(4);
-        else GD_GO(2);
+        GD_SPMM_FOR_LPR(lpr, GD_GO);
 #undef GD_GO
     }
     return gd_launch_status("spmm_stream");

@@ -1,5 +1,4 @@
-// Evaluation-side kernels: masked per-row top-k (reference main.py:296-301) and the LightGCN CSR
-// SpMM (reference lightGCN.py:184-189).  Both are HBM / cache-bandwidth bound.
+// Masked per-row top-k (reference main.py:296-301).  Bound by HBM / cache bandwidth.
 #include <stdlib.h>
 
 #include "common.h"
@@ -364,305 +363,6 @@ __global__ __launch_bounds__(NT, 8) void topk_fast_kernel(const float* __restric
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// CSR SpMM  Y = (A X + sum_k addend_k) * scale,  one wave per VIRTUAL row.
-// Degree skew is the problem (a hub item has 1e4+ neighbours, the median row ~20): the host splits
-// every row into virtual rows of <= chunk nonzeros (plan arrays below), so hub rows spread over many
-// waves; a row that was split writes float partials that a second tiny kernel adds in slot order
-// (deterministic, no atomics).  LPR lanes cover one embedding row with 16-byte loads, so a wave
-// gathers 64/LPR neighbour rows per instruction (d = 64: 4 x 256 B) and keeps 4 such instructions
-// in flight.  The LightGCN layer mean is fused through `addends`/`scale` in the last layer.
-// ---------------------------------------------------------------------------------------------
-constexpr int SPMM_MAX_ADD = 8;
-struct SpmmAdd {
-    const float* p[SPMM_MAX_ADD];
-    int n;
-    int64_t ld;
-    float scale;
-};
-
-template <int LPR>
-__global__ __launch_bounds__(256) void spmm_vec_kernel(const int64_t* __restrict__ vbeg, const int64_t* __restrict__ vend,
-                                                       const int32_t* __restrict__ vrow,
-                                                       const int32_t* __restrict__ vslot, int n_virtual,
-                                                       const int32_t* __restrict__ col,
-                                                       const float* __restrict__ val, const float* __restrict__ X,
-                                                       int64_t ldx, float* __restrict__ Y, int64_t ldy,
-                                                       float* __restrict__ partial, int d, const SpmmAdd add) {
-    constexpr int NPAR = 64 / LPR;
-    const int lane = threadIdx.x & 63;
-    const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (v >= n_virtual) return;
-    const int sub = lane / LPR, cl = lane % LPR;
-    const int64_t beg = vbeg[v], end = vend[v];
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    int64_t j = beg + sub;
-    for (; j + 3 * NPAR < end; j += 4 * NPAR) {
-        const int c0 = col[j], c1 = col[j + NPAR], c2 = col[j + 2 * NPAR], c3 = col[j + 3 * NPAR];
-        const float w0 = val[j], w1 = val[j + NPAR], w2 = val[j + 2 * NPAR], w3 = val[j + 3 * NPAR];
-        const f32x4 x0 = *reinterpret_cast<const f32x4*>(X + (int64_t)c0 * ldx + cl * 4);
-        const f32x4 x1 = *reinterpret_cast<const f32x4*>(X + (int64_t)c1 * ldx + cl * 4);
-        const f32x4 x2 = *reinterpret_cast<const f32x4*>(X + (int64_t)c2 * ldx + cl * 4);
-        const f32x4 x3 = *reinterpret_cast<const f32x4*>(X + (int64_t)c3 * ldx + cl * 4);
-        s0 += w0 * x0;
-        s1 += w1 * x1;
-        s2 += w2 * x2;
-        s3 += w3 * x3;
-    }
-    for (; j < end; j += NPAR) {
-        const int c0 = col[j];
-        const float w0 = val[j];
-        s0 += w0 * *reinterpret_cast<const f32x4*>(X + (int64_t)c0 * ldx + cl * 4);
-    }
-    f32x4 s = (s0 + s1) + (s2 + s3);
-#pragma unroll
-    for (int o = LPR; o < 64; o <<= 1) {
-        s.x += __shfl_xor(s.x, o);
-        s.y += __shfl_xor(s.y, o);
-        s.z += __shfl_xor(s.z, o);
-        s.w += __shfl_xor(s.w, o);
-    }
-    if (sub == 0) {
-        const int slot = vslot[v];
-        if (slot >= 0) {
-            *reinterpret_cast<f32x4*>(partial + (int64_t)slot * d + cl * 4) = s;
-        } else {
-            const int r = vrow[v];
-            for (int k = 0; k < add.n; ++k) s += *reinterpret_cast<const f32x4*>(add.p[k] + (int64_t)r * add.ld + cl * 4);
-            *reinterpret_cast<f32x4*>(Y + (int64_t)r * ldy + cl * 4) = s * add.scale;
-        }
-    }
-}
-
-// Short rows (the bulk of a user-item graph: median degree ~ 20): LPR lanes own one whole row, so a wave
-// works on 64/LPR rows at once.  With one row per wave the kernel is bound by the dependent chain
-// vptr -> col/val -> gather -> store of 50 k+ tiny waves (measured 39 us for the user half of the Yelp graph);
-// here each lane group fetches up to LPR (col, val) pairs with one coalesced load, broadcasts them with
-// group-local shuffles and keeps 4 gathers in flight.  Accumulation is in CSR order (deterministic).
-template <int LPR>
-__global__ __launch_bounds__(256) void spmm_short_kernel(const int64_t* __restrict__ vbeg, const int64_t* __restrict__ vend,
-                                                         const int32_t* __restrict__ vrow, int n_short,
-                                                         const int32_t* __restrict__ col,
-                                                         const float* __restrict__ val, const float* __restrict__ X,
-                                                         int64_t ldx, float* __restrict__ Y, int64_t ldy,
-                                                         const SpmmAdd add) {
-    constexpr int G = 64 / LPR;
-    const int lane = threadIdx.x & 63;
-    const int grp = lane / LPR, gl = lane % LPR;
-    const int v = (blockIdx.x * 4 + (threadIdx.x >> 6)) * G + grp;
-    if (v >= n_short) return;  // whole lane group leaves together
-    const int64_t beg = vbeg[v], end = vend[v];
-    const int r = vrow[v];
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t base = beg; base < end; base += LPR) {
-        const bool have = base + gl < end;
-        const int my_c = have ? col[base + gl] : 0;
-        const float my_w = have ? val[base + gl] : 0.f;
-        const int n = (int)min((int64_t)LPR, end - base);
-        int j = 0;
-        for (; j + 3 < n; j += 4) {
-            const int c0 = __shfl(my_c, j, LPR), c1 = __shfl(my_c, j + 1, LPR), c2 = __shfl(my_c, j + 2, LPR),
-                      c3 = __shfl(my_c, j + 3, LPR);
-            const float w0 = __shfl(my_w, j, LPR), w1 = __shfl(my_w, j + 1, LPR), w2 = __shfl(my_w, j + 2, LPR),
-                        w3 = __shfl(my_w, j + 3, LPR);
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(X + (int64_t)c0 * ldx + gl * 4);
-            const f32x4 x1 = *reinterpret_cast<const f32x4*>(X + (int64_t)c1 * ldx + gl * 4);
-            const f32x4 x2 = *reinterpret_cast<const f32x4*>(X + (int64_t)c2 * ldx + gl * 4);
-            const f32x4 x3 = *reinterpret_cast<const f32x4*>(X + (int64_t)c3 * ldx + gl * 4);
-            s += w0 * x0;
-            s += w1 * x1;
-            s += w2 * x2;
-            s += w3 * x3;
-        }
-        for (; j < n; ++j) {
-            const int c0 = __shfl(my_c, j, LPR);
-            const float w0 = __shfl(my_w, j, LPR);
-            s += w0 * *reinterpret_cast<const f32x4*>(X + (int64_t)c0 * ldx + gl * 4);
-        }
-    }
-    for (int k = 0; k < add.n; ++k) s += *reinterpret_cast<const f32x4*>(add.p[k] + (int64_t)r * add.ld + gl * 4);
-    *reinterpret_cast<f32x4*>(Y + (int64_t)r * ldy + gl * 4) = s * add.scale;
-}
-
-// generic fallback (any d): one neighbour at a time, lanes stride over columns
-__global__ __launch_bounds__(256) void spmm_generic_kernel(const int64_t* __restrict__ vbeg, const int64_t* __restrict__ vend,
-                                                           const int32_t* __restrict__ vrow,
-                                                           const int32_t* __restrict__ vslot, int n_virtual,
-                                                           const int32_t* __restrict__ col,
-                                                           const float* __restrict__ val, const float* __restrict__ X,
-                                                           int64_t ldx, float* __restrict__ Y, int64_t ldy,
-                                                           float* __restrict__ partial, int d, const SpmmAdd add) {
-    const int lane = threadIdx.x & 63;
-    const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (v >= n_virtual) return;
-    const int64_t beg = vbeg[v], end = vend[v];
-    const int slot = vslot[v], r = vrow[v];
-    for (int c0 = lane; c0 < d; c0 += 64) {
-        float s = 0.f;
-        for (int64_t j = beg; j < end; ++j) s += val[j] * X[(int64_t)col[j] * ldx + c0];
-        if (slot >= 0) {
-            partial[(int64_t)slot * d + c0] = s;
-        } else {
-            for (int k = 0; k < add.n; ++k) s += add.p[k][(int64_t)r * add.ld + c0];
-            Y[(int64_t)r * ldy + c0] = s * add.scale;
-        }
-    }
-}
-
-// rows that were split: Y[r] = (sum of their partial slots + addends) * scale.  One workgroup per split
-// row: wave w adds slots w, w+4, ... (independent loads, 4 in flight), the four partial sums are added in
-// wave order -> fixed summation order, no atomics.
-__global__ __launch_bounds__(256) void spmm_combine_kernel(const int32_t* __restrict__ lrow,
-                                                           const int32_t* __restrict__ lptr, int n_long,
-                                                           const float* __restrict__ partial, int d,
-                                                           float* __restrict__ Y, int64_t ldy, const SpmmAdd add) {
-    extern __shared__ float comb[];  // [4][d]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l = blockIdx.x;
-    const int r = lrow[l];
-    const int beg = lptr[l], end = lptr[l + 1];
-    for (int c0 = lane; c0 < d; c0 += 64) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int k = beg + wave;
-        for (; k + 12 < end; k += 16) {
-            s0 += partial[(int64_t)k * d + c0];
-            s1 += partial[(int64_t)(k + 4) * d + c0];
-            s2 += partial[(int64_t)(k + 8) * d + c0];
-            s3 += partial[(int64_t)(k + 12) * d + c0];
-        }
-        for (; k < end; k += 4) s0 += partial[(int64_t)k * d + c0];
-        comb[wave * d + c0] = (s0 + s1) + (s2 + s3);
-    }
-    __syncthreads();
-    if (wave == 0) {
-        for (int c0 = lane; c0 < d; c0 += 64) {
-            float s = ((comb[c0] + comb[d + c0]) + comb[2 * d + c0]) + comb[3 * d + c0];
-            for (int k = 0; k < add.n; ++k) s += add.p[k][(int64_t)r * add.ld + c0];
-            Y[(int64_t)r * ldy + c0] = s * add.scale;
-        }
-    }
-}
-
-// ---- ranking metrics (reference evaluate_utils.py:6-52) -----------------------------------------------------------
-// One thread per user walks its K predicted items once, in rank order, exactly as the reference's inner loop does
-// for every N (hits, dcg += 1/log2(j+2), ideal dcg over min(|GT|, N) ranks, reciprocal rank of the first hit), and
-// emits the four per-user terms whenever j+1 reaches one of the requested cut-offs.  float64 throughout, additions
-// in the reference's order: the per-user terms are bit-identical to the Python loop; the host adds them up in user
-// order.  Ground-truth rows must have sorted column indices (binary search).
-constexpr int TOPN_MAX = 8;
-struct TopNList {
-    int n;
-    int v[TOPN_MAX];
-};
-
-__global__ __launch_bounds__(256) void topn_metrics_kernel(const int64_t* __restrict__ pred, int64_t ldp, int U,
-                                                           const int64_t* __restrict__ gt_indptr,
-                                                           const int32_t* __restrict__ gt_idx, const TopNList tn,
-                                                           double* __restrict__ out) {
-    const int u = blockIdx.x * 256 + threadIdx.x;
-    if (u >= U) return;
-    const int64_t beg = gt_indptr[u], end = gt_indptr[u + 1];
-    const int64_t len = end - beg;
-    double* o = out + (int64_t)u * tn.n * 4;
-    if (len == 0) {
-        for (int k = 0; k < tn.n * 4; ++k) o[k] = 0.0;
-        return;
-    }
-    int hits = 0, next = 0;
-    int64_t left = len;
-    double dcg = 0.0, idcg = 0.0, mrr = 0.0;
-    bool first = true;
-    const int K = tn.v[tn.n - 1];
-    for (int j = 0; j < K; ++j) {
-        const int64_t item = pred[(int64_t)u * ldp + j];
-        int64_t lo = beg, hi = end;  // lower bound of `item` in the sorted row
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)gt_idx[mid] < item) lo = mid + 1;
-            else hi = mid;
-        }
-        const double gain = 1.0 / log2((double)(j + 2));
-        if (lo < end && (int64_t)gt_idx[lo] == item) {
-            dcg += gain;
-            if (first) {
-                mrr = 1.0 / ((double)j + 1.0);
-                first = false;
-            }
-            ++hits;
-        }
-        if (left > 0) {
-            idcg += gain;
-            --left;
-        }
-        if (j + 1 == tn.v[next]) {
-            const double N = (double)tn.v[next];
-            o[next * 4 + 0] = (double)hits / N;
-            o[next * 4 + 1] = (double)hits / (double)len;
-            o[next * 4 + 2] = idcg != 0.0 ? dcg / idcg : 0.0;
-            o[next * 4 + 3] = mrr;
-            ++next;
-        }
-    }
-}
-
-// The same four terms from the RANKS of a user's ground-truth items (gdmcf_rank_targets_f32) instead of a list: one wave per user.
-// The hits below a cut-off are visited in ascending rank -- every round the 64 lanes find the smallest (rank, column) pair not
-// yet visited -- so dcg receives the gains topn_metrics_kernel adds, in its order; idcg runs over j < min(N, |GT|) in ascending
-// j as there; the same expressions in float64: the same bits.  Every lane carries the same sums, lane 0 stores them.  Nothing
-// is bounded by a list length: a cut-off past the last hit only closes the sums.
-__global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t* __restrict__ ranks, int64_t ldr, int U, int G,
-                                                           const TopNList tn, double* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (u >= U) return;  // (the whole wave)
-    const int32_t* r = ranks + (int64_t)u * ldr;
-    int len = 0;
-    for (int j = lane; j < G; j += 64) len += r[j] >= 0 ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) len += __shfl_xor(len, o);
-    double* o = out + (int64_t)u * tn.n * 4;
-    if (len == 0) {
-        for (int k = lane; k < tn.n * 4; k += 64) o[k] = 0.0;
-        return;
-    }
-    constexpr unsigned long long NONE = ~0ull;
-    int hits = 0, next = 0, ji = 0;
-    double dcg = 0.0, idcg = 0.0, mrr = 0.0;
-    unsigned long long from = 0ull;  // pairs below it are visited
-    while (next < tn.n) {
-        unsigned long long best = NONE;
-        for (int j = lane; j < G; j += 64) {
-            const int32_t v = r[j];
-            if (v >= 0) {
-                const unsigned long long p = ((unsigned long long)(uint32_t)v << 32) | (uint32_t)j;
-                if (p >= from && p < best) best = p;
-            }
-        }
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) {
-            const unsigned long long t = __shfl_xor(best, s);
-            best = t < best ? t : best;
-        }
-        const int64_t rk = (int64_t)(best >> 32);  // (NONE: past every cut-off)
-        while (next < tn.n && (best == NONE || rk >= (int64_t)tn.v[next])) {  // the cut-offs that close before this hit
-            const int N = tn.v[next];
-            for (; ji < N && ji < len; ++ji) idcg += 1.0 / log2((double)(ji + 2));
-            if (lane == 0) {
-                o[next * 4 + 0] = (double)hits / (double)N;
-                o[next * 4 + 1] = (double)hits / (double)len;
-                o[next * 4 + 2] = idcg != 0.0 ? dcg / idcg : 0.0;
-                o[next * 4 + 3] = mrr;
-            }
-            ++next;
-        }
-        if (best == NONE) break;
-        dcg += 1.0 / log2((double)(rk + 2));
-        if (hits == 0) mrr = 1.0 / ((double)rk + 1.0);
-        ++hits;
-        from = best + 1ull;
-    }
-}
-
 // Both top-k entries: the fast path where it applies, then the radix-select kernel (alone, or for the rows the fast path marked).
 // EXT is the kernels' own pack: empty (gdmcf_topk_masked_f32) or one TopkRowsArgs, handed on behind the plain arguments.
 template <class... EXT>
@@ -747,99 +447,6 @@ int gdmcf_topk_masked_rows_f32(const float* pred, int64_t ldp, int B, int I, con
     const TopkRowsArgs ext = {indptr2, indices2, rows, scale};
     return topk_launch("gdmcf_topk_masked_rows_f32", pred, ldp, B, I, indptr, indices, k, idx_out, val_out, (hipStream_t)stream,
                        ext);
-}
-
-int gdmcf_spmm_csr_f32(const int64_t* vbeg, const int64_t* vend, const int32_t* vrow, const int32_t* vslot, int n_virtual, int n_short,
-                       const int32_t* lrow, const int32_t* lptr, int n_long, const int32_t* col, const float* val,
-                       int n_rows, const float* X, int64_t ldx, int d, float* Y, int64_t ldy, float* partial_ws,
-                       const float* const* addends_host, int n_add, int64_t ld_add, float scale, double alg_bytes,
-                       void* stream) {
-    GD_CHECK_SHAPE(n_rows > 0 && n_virtual > 0 && d > 0 && ldx >= d && ldy >= d, "spmm: bad shape");
-    GD_CHECK_ARG(n_add >= 0 && n_add <= SPMM_MAX_ADD && (n_add == 0 || (addends_host && ld_add >= d)), "spmm: bad addends");
-    GD_CHECK_ARG(n_long == 0 || (lrow && lptr && partial_ws), "spmm: split rows need lrow/lptr/partial_ws");
-    hipStream_t s = (hipStream_t)stream;
-    SpmmAdd add = {};
-    add.n = n_add; add.ld = ld_add; add.scale = scale;
-    bool add_al = true;
-    for (int k = 0; k < n_add; ++k) {
-        add.p[k] = addends_host[k];
-        add_al = add_al && gd_aligned16(add.p[k]);
-    }
-    GD_CHECK_ARG(n_short >= 0 && n_short <= n_virtual, "spmm: n_short out of range");
-    const dim3 block(256);
-    const bool vec = (d % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && gd_aligned16(X) && gd_aligned16(Y) &&
-                     (n_add == 0 || ((ld_add % 4 == 0) && add_al)) && (partial_ws == nullptr || gd_aligned16(partial_ws));
-    const int lpr = d / 4;
-    const bool pow2 = vec && (lpr == 2 || lpr == 4 || lpr == 8 || lpr == 16 || lpr == 32 || lpr == 64);
-    if (!pow2 && n_short > 0) {
-        gdmcf_set_error("spmm: the short-row path needs d in {8,16,32,64,128,256}; build the plan with n_short = 0");
-        return GDMCF_E_ARG;
-    }
-    {
-        GdProfScope prof(8, alg_bytes, s);
-        if (n_short > 0) {
-#define GD_SPMM_SHORT(L) hipLaunchKernelGGL(spmm_short_kernel<L>, dim3(gd_cdiv(n_short, 4 * (64 / L))), block, 0, s, vbeg, vend, vrow, n_short, col, val, X, ldx, Y, ldy, add)
-            if (lpr == 16) GD_SPMM_SHORT(16);
-            else if (lpr == 8) GD_SPMM_SHORT(8);
-            else if (lpr == 32) GD_SPMM_SHORT(32);
-            else if (lpr == 64) GD_SPMM_SHORT(64);
-            else if (lpr == 4) GD_SPMM_SHORT(4);
-            else GD_SPMM_SHORT(2);
-#undef GD_SPMM_SHORT
-        }
-        const int n_rest = n_virtual - n_short;
-        const dim3 grid(gd_cdiv(n_rest > 0 ? n_rest : 1, 4));
-        const int64_t* vbeg_r = vbeg + n_short;
-        const int64_t* vend_r = vend + n_short;
-        const int32_t* vrow_r = vrow + n_short;
-        const int32_t* vslot_r = vslot + n_short;
-#define GD_SPMM_LAUNCH(K) hipLaunchKernelGGL(K, grid, block, 0, s, vbeg_r, vend_r, vrow_r, vslot_r, n_rest, col, val, X, ldx, Y, ldy, partial_ws, d, add)
-        if (n_rest > 0) {
-            if (vec && lpr == 16) GD_SPMM_LAUNCH(spmm_vec_kernel<16>);
-            else if (vec && lpr == 8) GD_SPMM_LAUNCH(spmm_vec_kernel<8>);
-            else if (vec && lpr == 32) GD_SPMM_LAUNCH(spmm_vec_kernel<32>);
-            else if (vec && lpr == 64) GD_SPMM_LAUNCH(spmm_vec_kernel<64>);
-            else if (vec && lpr == 4) GD_SPMM_LAUNCH(spmm_vec_kernel<4>);
-            else if (vec && lpr == 2) GD_SPMM_LAUNCH(spmm_vec_kernel<2>);
-            else GD_SPMM_LAUNCH(spmm_generic_kernel);
-        }
-#undef GD_SPMM_LAUNCH
-        if (n_long > 0)
-            hipLaunchKernelGGL(spmm_combine_kernel, dim3(n_long), block, (size_t)4 * d * sizeof(float), s, lrow, lptr,
-                               n_long, partial_ws, d, Y, ldy, add);
-    }
-    return gd_launch_status("spmm_csr");
-}
-
-int gdmcf_topn_metrics_f64(const int64_t* pred_idx, int64_t ldp, int U, const int64_t* gt_indptr, const int32_t* gt_indices,
-                           const int* topN_host, int n_topn, double* out, void* stream) {
-    GD_CHECK_SHAPE(U > 0 && n_topn >= 1 && n_topn <= TOPN_MAX, "topn_metrics: bad shape (1..8 cut-offs)");
-    GD_CHECK_ARG(pred_idx && gt_indptr && gt_indices && topN_host && out, "topn_metrics: null pointer");
-    TopNList tn;
-    tn.n = n_topn;
-    for (int i = 0; i < n_topn; ++i) {
-        tn.v[i] = topN_host[i];
-        GD_CHECK_ARG(tn.v[i] >= 1 && (i == 0 || tn.v[i] > tn.v[i - 1]), "topn_metrics: cut-offs must be ascending and >= 1");
-    }
-    GD_CHECK_SHAPE(ldp >= tn.v[n_topn - 1], "topn_metrics: fewer predicted items per user than the largest cut-off");
-    hipLaunchKernelGGL(topn_metrics_kernel, dim3(gd_cdiv(U, 256)), dim3(256), 0, (hipStream_t)stream, pred_idx, ldp, U,
-                       gt_indptr, gt_indices, tn, out);
-    return gd_launch_status("topn_metrics");
-}
-
-int gdmcf_rank_metrics_f64(const int32_t* ranks, int64_t ldr, int U, int G, const int* topN_host, int n_topn, double* out,
-                           void* stream) {
-    GD_CHECK_SHAPE(U > 0 && G >= 1 && ldr >= G && n_topn >= 1 && n_topn <= TOPN_MAX,
-                   "gdmcf_rank_metrics_f64: bad shape (U > 0, G >= 1, ldr >= G, 1..8 cut-offs)");
-    GD_CHECK_ARG(ranks && topN_host && out, "gdmcf_rank_metrics_f64: null pointer");
-    TopNList tn;
-    tn.n = n_topn;
-    for (int i = 0; i < n_topn; ++i) {
-        tn.v[i] = topN_host[i];
-        GD_CHECK_ARG(tn.v[i] >= 1 && (i == 0 || tn.v[i] > tn.v[i - 1]), "gdmcf_rank_metrics_f64: cut-offs must be ascending and >= 1");
-    }
-    hipLaunchKernelGGL(rank_metrics_kernel, dim3(gd_cdiv(U, 4)), dim3(256), 0, (hipStream_t)stream, ranks, ldr, U, G, tn, out);
-    return gd_launch_status("gdmcf_rank_metrics_f64");
 }
 
 }  // extern "C"

@@ -35,6 +35,36 @@ def masked_topk(prediction, k, mask_indptr=None, mask_indices=None, return_value
     return (val, idx) if return_values else idx
 
 
+def _score_operands(what, user_emb, item_emb, mask_indptr, mask_indices, user_ids, check_ids, also_gpu=()):
+    """The operands score_topk and score_rank (`what`: the caller, for the error texts) share, as their entries take them:
+    (ue, ie, ids, n_rows, ip, ix) -- both tables float32 with unit column stride, `user_ids` int64 (range-checked against ue
+    when `check_ids`: one synchronising copy) or None, the number of ranked rows, the mask CSR int64 / int32 or (None, None).
+    Everything must be on the GPU, the (tensor, name) pairs of `also_gpu` included."""
+    _lib.require_gpu(user_emb, "user embeddings")
+    _lib.require_gpu(item_emb, "item embeddings")
+    for t, name in (*also_gpu, (mask_indptr, "mask_indptr"), (mask_indices, "mask_indices"), (user_ids, "user_ids")):
+        if t is not None:
+            _lib.require_gpu(t, name)
+    prep = lambda t: t if (t.dtype == torch.float32 and t.stride(-1) == 1) else t.float().contiguous()
+    ue, ie = prep(user_emb.detach()), prep(item_emb.detach())
+    assert ue.dim() == 2 and ie.dim() == 2 and ue.shape[1] == ie.shape[1], "user_emb [U, d] and item_emb [I, d] must share d"
+    dev = ue.device
+    ids = None
+    if user_ids is not None:
+        ids = user_ids.to(device=dev, dtype=torch.int64).contiguous()
+        if check_ids and ids.numel():
+            lo, hi = torch.aminmax(ids)  # (one synchronising copy)
+            lo, hi = torch.stack((lo, hi)).tolist()
+            if not (0 <= lo and hi < ue.shape[0]):
+                raise IndexError(f"{what}: user_ids out of range")
+    n_rows = ids.numel() if ids is not None else ue.shape[0]
+    ip = ix = None
+    if mask_indptr is not None:
+        ip = mask_indptr.to(device=dev, dtype=torch.int64).contiguous()
+        ix = mask_indices.to(device=dev, dtype=torch.int32).contiguous()
+    return ue, ie, ids, n_rows, ip, ix
+
+
 def score_topk(user_emb, item_emb, k, mask_indptr=None, mask_indices=None, user_ids=None, return_values=False, check_ids=True):
     """masked_topk(user_emb[user_ids] @ item_emb.T, k, mask_indptr, mask_indices) without the score matrix (reference
     lightGCN.py:75-90: the product, the dense -inf mask of the training interactions and torch.topk): one fused kernel,
@@ -45,33 +75,13 @@ def score_topk(user_emb, item_emb, k, mask_indptr=None, mask_indices=None, user_
     int32 item ids).  Same return convention, tie rule (lowest item index first) and degenerate-row convention (masked
     items count as -inf) as masked_topk.  `check_ids=False` skips the range check of `user_ids` (a device-to-host
     synchronisation): for callers that built the ids on the host and know them to lie in [0, U)."""
-    _lib.require_gpu(user_emb, "user embeddings")
-    _lib.require_gpu(item_emb, "item embeddings")
-    for t, what in ((mask_indptr, "mask_indptr"), (mask_indices, "mask_indices"), (user_ids, "user_ids")):
-        if t is not None:
-            _lib.require_gpu(t, what)
+    ue, ie, ids, n_rows, ip, ix = _score_operands("score_topk", user_emb, item_emb, mask_indptr, mask_indices, user_ids, check_ids)
     lib = _lib.load()
-    prep = lambda t: t if (t.dtype == torch.float32 and t.stride(-1) == 1) else t.float().contiguous()
-    ue, ie = prep(user_emb.detach()), prep(item_emb.detach())
-    assert ue.dim() == 2 and ie.dim() == 2 and ue.shape[1] == ie.shape[1], "user_emb [U, d] and item_emb [I, d] must share d"
     dev = ue.device
     I, d = ie.shape
-    ids = None
-    if user_ids is not None:
-        ids = user_ids.to(device=dev, dtype=torch.int64).contiguous()
-        if check_ids and ids.numel():
-            lo, hi = torch.aminmax(ids)  # (one synchronising copy)
-            lo, hi = torch.stack((lo, hi)).tolist()
-            if not (0 <= lo and hi < ue.shape[0]):
-                raise IndexError("score_topk: user_ids out of range")
-    n_rows = ids.numel() if ids is not None else ue.shape[0]
     if not 1 <= k <= I:
         raise AssertionError("selected index k out of range")
-    ip = ix = None
-    if mask_indptr is not None:
-        ip = mask_indptr.to(device=dev, dtype=torch.int64).contiguous()
-        ix = mask_indices.to(device=dev, dtype=torch.int32).contiguous()
-        assert ip.numel() == n_rows + 1, "mask_indptr must have one entry per ranked row plus one"
+    assert ip is None or ip.numel() == n_rows + 1, "mask_indptr must have one entry per ranked row plus one"
     idx = torch.empty(n_rows, k, dtype=torch.int64, device=dev)
     val = torch.empty(n_rows, k, dtype=torch.float32, device=dev) if return_values else None
     if n_rows == 0:
@@ -101,35 +111,15 @@ def score_rank(user_emb, item_emb, tgt_indptr, tgt_indices, mask_indptr=None, ma
         raise ValueError("score_rank: tgt_indptr and tgt_indices are required")
     if (mask_indptr is None) != (mask_indices is None):
         raise ValueError("score_rank: mask_indptr and mask_indices go together")
-    _lib.require_gpu(user_emb, "user embeddings")
-    _lib.require_gpu(item_emb, "item embeddings")
-    for t, what in ((tgt_indptr, "tgt_indptr"), (tgt_indices, "tgt_indices"), (mask_indptr, "mask_indptr"),
-                    (mask_indices, "mask_indices"), (user_ids, "user_ids")):
-        if t is not None:
-            _lib.require_gpu(t, what)
+    ue, ie, ids, n_rows, ip, ix = _score_operands("score_rank", user_emb, item_emb, mask_indptr, mask_indices, user_ids, check_ids,
+                                                  also_gpu=((tgt_indptr, "tgt_indptr"), (tgt_indices, "tgt_indices")))
     lib = _lib.load()
-    prep = lambda t: t if (t.dtype == torch.float32 and t.stride(-1) == 1) else t.float().contiguous()
-    ue, ie = prep(user_emb.detach()), prep(item_emb.detach())
-    assert ue.dim() == 2 and ie.dim() == 2 and ue.shape[1] == ie.shape[1], "user_emb [U, d] and item_emb [I, d] must share d"
     dev = ue.device
     I, d = ie.shape
-    ids = None
-    if user_ids is not None:
-        ids = user_ids.to(device=dev, dtype=torch.int64).contiguous()
-        if check_ids and ids.numel():
-            lo, hi = torch.aminmax(ids)  # (one synchronising copy)
-            lo, hi = torch.stack((lo, hi)).tolist()
-            if not (0 <= lo and hi < ue.shape[0]):
-                raise IndexError("score_rank: user_ids out of range")
-    n_rows = ids.numel() if ids is not None else ue.shape[0]
     tp = tgt_indptr.to(device=dev, dtype=torch.int64).contiguous()
     tx = tgt_indices.to(device=dev, dtype=torch.int32).contiguous()
     assert tp.numel() == n_rows + 1, "tgt_indptr must have one entry per ranked row plus one"
-    ip = ix = None
-    if mask_indptr is not None:
-        ip = mask_indptr.to(device=dev, dtype=torch.int64).contiguous()
-        ix = mask_indices.to(device=dev, dtype=torch.int32).contiguous()
-        assert ip.numel() == n_rows + 1, "mask_indptr must have one entry per ranked row plus one"
+    assert ip is None or ip.numel() == n_rows + 1, "mask_indptr must have one entry per ranked row plus one"
     if G is None:
         G = max(int((tp[1:] - tp[:-1]).max()), 1) if n_rows else 1  # (the one host read)
     G = int(G)

@@ -628,7 +628,7 @@ int gdmcf_rank_metrics_f64(const int32_t* ranks, int64_t ldr, int U, int G, cons
 /* ---- LightGCN propagation: CSR SpMM (lightGCN.py:184-189) --------------------------------
  * Y[r,:] = ( sum_j val[j]*X[col[j],:]  +  sum_k addend_k[r,:] ) * scale
  * The adjacency is plain CSR (col int32, val float32) plus a host-built execution plan of "virtual rows"
- * (gdmcf_amd/lightgcn.py:spmm_plan):
+ * (gdmcf_amd/spmm_schedule.py:spmm_plan):
  *   vbeg, vend int64 [n_virtual]  nonzero range of each virtual row
  *   vrow  int32 [n_virtual]       the real row it belongs to
  *   vslot int32 [n_virtual]       -1: the row is whole, write Y directly; >= 0: slot in partial_ws
@@ -647,7 +647,7 @@ int gdmcf_spmm_csr_f32(const int64_t* vbeg, const int64_t* vend, const int32_t* 
                        int64_t ldy, float* partial_ws, const float* const* addends_host, int n_add,
                        int64_t ld_add, float scale, double alg_bytes, void* stream);
 /* Second-generation schedule of the same product (one launch per layer; csrc/spmm_bundle.hip), for d in
- * {8,16,32,64,128,256} with 16-byte aligned rows.  The host plan (gdmcf_amd/lightgcn.py:spmm_bundle_plan) sorts the rows
+ * {8,16,32,64,128,256} with 16-byte aligned rows.  The host plan (gdmcf_amd/spmm_schedule.py:spmm_bundle_plan) sorts the rows
  * of at most s_max nonzeros by length and bundles them G = 64/(d/4) to a wave-step, cuts longer rows into pieces, and
  * gives every one of n_waves waves (a multiple of 32; block b = 4 waves serves class b % 8 = one XCD) a contiguous run
  * of pieces and bundles of equal cost:
@@ -665,7 +665,7 @@ int gdmcf_spmm_bundled_f32(const int32_t* wdesc, int n_waves, const int64_t* lbe
                            int64_t ldx, int d, float* Y, int64_t ldy, float* partial_ws, const float* const* addends_host, int n_add, int64_t ld_add,
                            float scale, double alg_bytes, void* stream);
 /* Third generation: the schedule of gdmcf_spmm_bundled_f32 with the nonzeros re-ordered into the order the waves gather
- * them (gdmcf_amd/lightgcn.py:spmm_stream_pack), so that a wave reads one contiguous run of (col, val) pairs instead of
+ * them (gdmcf_amd/spmm_schedule.py:spmm_stream_pack), so that a wave reads one contiguous run of (col, val) pairs instead of
  * chasing row pointers:
  *   wdesc int32 [n_waves][4]     first 64-entry batch of the wave's run, its batches, first / last+1 unit
  *   cw    int32 [n_entries][2]   (column, float bits of the value); n_entries % 64 == 0; 8-byte aligned

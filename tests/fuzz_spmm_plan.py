@@ -1,4 +1,4 @@
-"""One-off fuzz of the SpMM schedule builders (gdmcf_amd/lightgcn.py: spmm_bundle_plan + spmm_stream_pack) on the CPU: random CSR
+"""One-off fuzz of the SpMM schedule builders (gdmcf_amd/spmm_schedule.py: spmm_bundle_plan + spmm_stream_pack) on the CPU: random CSR
 matrices with degenerate degree patterns (all rows empty / full, hubs, tiny), random widths and limits; the packed stream is
 walked in numpy the way the kernel walks it and must reproduce A @ X with every row written exactly once.
     python tests/fuzz_spmm_plan.py"""

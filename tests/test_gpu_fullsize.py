@@ -58,7 +58,7 @@ def _float64_mean_of_layers(users, items, U, It, E0, L):
     ("stress", False, 1_200_000, 39_000_000),
 ])
 def test_propagation_at_the_selected_kernels_graph_size(shape, expect_streamed, min_nodes, min_nnz, monkeypatch):
-    monkeypatch.delenv("GDMCF_SPMM_GEN", raising=False)  # the product's own choice (lightgcn.py: SPMM_SLICE_MB)
+    monkeypatch.delenv("GDMCF_SPMM_GEN", raising=False)  # the product's own choice (spmm_schedule.py: pick_generation, SPMM_SLICE_MB)
     users, items, U, It = _graph(shape)
     assert U + It >= min_nodes
     rng = np.random.default_rng(7)

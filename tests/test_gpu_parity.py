@@ -525,7 +525,7 @@ def test_lightgcn_propagation_matches_reference(case, gen, monkeypatch):
 @pytest.mark.parametrize("gen", ["1", "2", "3"])
 def test_spmm_hub_rows_are_split_and_exact(gen, monkeypatch):
     """A hub item with thousands of neighbours goes through the split + combine path of every kernel generation
-    (1: virtual rows, 2: bundled schedule, 3: streamed schedule -- gdmcf_amd/lightgcn.py picks by table size)."""
+    (1: virtual rows, 2: bundled schedule, 3: streamed schedule -- spmm_schedule.pick_generation picks by table size)."""
     monkeypatch.setenv("GDMCF_SPMM_GEN", gen)
     rng = np.random.default_rng(0)
     U, It, d = 3000, 50, 64

@@ -250,7 +250,7 @@ def test_bf16_shadow_registry_and_gemm_precision_are_host_side_state():
 
 @pytest.mark.parametrize("d", [64, 20])
 def test_spmm_plan_covers_every_nonzero_once(d):
-    """Host-built execution plan of gdmcf_spmm_csr_f32 (gdmcf_amd/lightgcn.py:spmm_plan): emulate in numpy exactly
+    """Host-built execution plan of gdmcf_spmm_csr_f32 (gdmcf_amd/spmm_schedule.py:spmm_plan): emulate in numpy exactly
     what the kernels do with it -- whole short rows, pieces of long rows, slot-ordered combination of cut rows --
     and compare with the CSR product; also the invariants the kernels rely on.  Includes empty rows, a hub row cut
     into many pieces, a row of exactly `chunk` nonzeros, and a width without the short-row path (d = 20)."""
@@ -297,7 +297,7 @@ def test_spmm_plan_covers_every_nonzero_once(d):
 @pytest.mark.parametrize("d,n_waves,split_at", [(64, 32, None), (64, 64, None), (16, 32, None), (256, 32, None), (8, 32, None),
                                                 (64, 32, 100), (16, 64, 100)])
 def test_spmm_bundle_plan_is_a_partition_of_the_work(d, n_waves, split_at):
-    """Static schedule of gdmcf_spmm_bundled_f32 (gdmcf_amd/lightgcn.py:spmm_bundle_plan), emulated in numpy wave by wave
+    """Static schedule of gdmcf_spmm_bundled_f32 (gdmcf_amd/spmm_schedule.py:spmm_bundle_plan), emulated in numpy wave by wave
     exactly as csrc/spmm_bundle.hip walks it: every nonzero is gathered exactly once, every row is written exactly once
     (whole rows by their wave, cut rows from their partial slots in slot order), bundles hold rows of the same class
     sorted by length, the waves of a class own contiguous runs, empty rows still get written."""
@@ -380,7 +380,7 @@ def test_spmm_bundle_plan_is_a_partition_of_the_work(d, n_waves, split_at):
 
 @pytest.mark.parametrize("d,n_waves", [(64, 32), (64, 64), (16, 32), (256, 32), (8, 32)])
 def test_spmm_stream_pack_reproduces_the_product(d, n_waves):
-    """gdmcf_spmm_stream_f32's input (gdmcf_amd/lightgcn.py:spmm_stream_pack), walked in numpy exactly as the kernel does
+    """gdmcf_spmm_stream_f32's input (gdmcf_amd/spmm_schedule.py:spmm_stream_pack), walked in numpy exactly as the kernel does
     (csrc/spmm_bundle.hip: spmm_stream_kernel): wave by wave, batch by batch, UN steps at a time, lane group g taking entry
     step*G + g; pieces are summed over the lane groups and go to their slot or row, bundles write one row per lane group.
     The result must be A @ X, every real nonzero must appear exactly once with its value, padding must have weight 0."""
