@@ -4,7 +4,9 @@
 propagation, a host sampler.  `BPRTrainer` is the fused step (csrc/bpr.hip): triples drawn on the device
 (gdmcf_bpr_sample_f32), loss and per-triple derivative in one kernel (gdmcf_bpr_loss_f32), the cotangent scattered without
 atomics (gdmcf_bpr_grad_f32), the same propagation run on it, FusedAdamW -- no autograd graph, no host synchronisation.
-`sample_bpr_items`, `bpr_loss_grad` and `bpr_reg_grad_` are its functional pieces.
+`sample_bpr_items`, `bpr_loss_grad` and `bpr_reg_grad_` are its functional pieces; `sample_bpr_negatives`
+(gdmcf_bpr_sample_pool_f32) draws several negatives per positive, each the best-scored of a pool of candidates, for the
+trainer's `n_negs` / `neg_pool` knobs.
 """
 import numpy as np
 import torch
@@ -50,6 +52,15 @@ def _bpr_sample(lib, indptr, indices, users, n_users, n_items, seed, offset, pos
     _lib.check(lib.gdmcf_bpr_sample_f32(indptr.data_ptr(), indices.data_ptr(), users.data_ptr(), users.numel(), n_users, n_items,
                                         int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), pos.data_ptr(), neg.data_ptr(),
                                         _lib.ptr(flag), st))
+
+
+def _bpr_sample_pool(lib, indptr, indices, users, n_negs, pool, n_users, n_items, M, seed, offset, pos, neg, flag, st):
+    """pos [B], neg [B * n_negs] (slot k of triple j at j * n_negs + k); M: the propagated table, read only when pool > 1"""
+    scored = pool > 1
+    _lib.check(lib.gdmcf_bpr_sample_pool_f32(indptr.data_ptr(), indices.data_ptr(), users.data_ptr(), users.numel(), n_negs, pool,
+                                             n_users, n_items, M.data_ptr() if scored else None, M.stride(0) if scored else 0,
+                                             M.shape[1] if scored else 0, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                             pos.data_ptr(), neg.data_ptr(), _lib.ptr(flag), st))
 
 
 def _bpr_loss(lib, M, E0, users, pos, neg, n_users, n_items, coef, ws, out2, flag, st):
@@ -104,6 +115,38 @@ def sample_bpr_items(indptr, indices, users, n_items, seed, offset):
     flag = torch.zeros(1, dtype=torch.int32, device=users.device)
     _bpr_sample(lib, indptr.contiguous(), indices.contiguous(), users, indptr.numel() - 1, int(n_items), seed, offset, pos, neg,
                 flag, _lib.stream_ptr())
+    return pos, neg, flag
+
+
+@torch.no_grad()
+def sample_bpr_negatives(indptr, indices, users, n_items, seed, offset, n_negs=1, pool=1, M=None):
+    """(pos [B], neg [B, n_negs], flag) for the given users by gdmcf_bpr_sample_pool_f32 (include/gdmcf_hip.h): operands as
+    `sample_bpr_items`.  pos[j] is that function's positive.  neg[j, k] is the best of `pool` candidates drawn uniformly (and
+    independently: repeats are possible) from the items outside users[j]'s row, by the float32 score <M[users[j]], M[n_users +
+    i]> -- the earliest drawn among equals; M: the propagated table, float32 [n_users + n_items, d] on the device, needed (and
+    read) only when pool > 1.  n_negs = pool = 1 gives `sample_bpr_items`'s pos and neg bit for bit.  Candidate q = k * pool + c
+    of triple j takes word y, z, w of the Philox block with counter (j, 0, 7, offset) for q < 3 and word (q - 3) % 4 of block
+    (j, 1 + (q - 3) / 4, 7, offset) after that."""
+    lib = _lib.load()
+    for t, what in ((indptr, "CSR indptr"), (indices, "CSR indices"), (users, "users")):
+        _lib.require_gpu(t, f"sample_bpr_negatives: {what}")
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or users.dtype != torch.int64:
+        raise ValueError("sample_bpr_negatives: indptr int64, indices int32, users int64 expected")
+    n_negs, pool, n_users = int(n_negs), int(pool), indptr.numel() - 1
+    if n_negs < 1 or pool < 1:
+        raise ValueError("sample_bpr_negatives: n_negs >= 1 and pool >= 1 expected")
+    if pool > 1:
+        if M is None:
+            raise ValueError("sample_bpr_negatives: pool > 1 scores the candidates and needs the propagated table M")
+        _lib.require_gpu(M, "sample_bpr_negatives: the propagated embeddings")
+        if M.dim() != 2 or M.dtype != torch.float32 or M.stride(1) != 1 or M.shape[0] != n_users + int(n_items):
+            raise ValueError("sample_bpr_negatives: M must be float32 [n_users + n_items, d] with unit column stride")
+    users = users.contiguous()
+    pos = torch.empty_like(users)
+    neg = torch.empty(users.numel(), n_negs, dtype=torch.int64, device=users.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=users.device)
+    _bpr_sample_pool(lib, indptr.contiguous(), indices.contiguous(), users, n_negs, pool, n_users, int(n_items), M, seed, offset,
+                     pos, neg, flag, _lib.stream_ptr())
     return pos, neg, flag
 
 
@@ -163,9 +206,17 @@ class BPRTrainer:
     a device torch.Generator (sorted; without replacement when at least batch_size are eligible, as lightGCN.py:231-238), items
     by gdmcf_bpr_sample_f32 with the count of draws as Philox offset.  `flag` (int32 [1] on the device; reading it
     synchronises) turns 1 when a step met an id out of range in device tensors handed to step() -- host arrays are
-    range-checked before anything is enqueued."""
+    range-checked before anything is enqueued.
 
-    def __init__(self, model, train_csr, batch_size=1024, lr=0.005, decay=1e-4, seed=0):
+    n_negs negatives per positive, neg_pool candidates per negative (`sample_bpr_negatives`; both 1: the step above, launch for
+    launch).  batch_size stays the number of drawn (user, positive) pairs; a step then works on batch_size * n_negs triples --
+    users and pos repeated n_negs times each (users stay sorted), neg flattened -- through the same loss, sort, scatter,
+    regulariser and optimiser entries: mf is the mean of softplus over all of them and reg is `bpr_loss`'s with
+    len(users) = batch_size * n_negs.  With neg_pool > 1 every negative is the candidate the current propagated table scores
+    highest (dynamic negative sampling): step() propagates first and hands that one table to the sampler and to the loss.
+    Both are construction arguments like batch_size: they are not in state_dict(), a resumed run passes the same ones."""
+
+    def __init__(self, model, train_csr, batch_size=1024, lr=0.005, decay=1e-4, seed=0, n_negs=1, neg_pool=1):
         from .data_utils import DeviceCSR
         from .optim import FusedAdamW
         if model._world > 1:
@@ -174,12 +225,15 @@ class BPRTrainer:
         _lib.require_gpu(E0, "BPRTrainer: the model's E0")
         if batch_size < 1 or not decay >= 0:
             raise ValueError("BPRTrainer: batch_size >= 1 and decay >= 0 expected")
+        if n_negs < 1 or neg_pool < 1:
+            raise ValueError("BPRTrainer: n_negs >= 1 and neg_pool >= 1 expected")
         self.lib = _lib.load()
         dev = E0.device
         csr = train_csr if isinstance(train_csr, DeviceCSR) else DeviceCSR(train_csr, dev)
         if tuple(csr.shape) != (model.n_users, model.n_items):
             raise ValueError("BPRTrainer: train_csr must be [n_users, n_items] of the model")
         self.model, self.batch_size, self.decay, self.seed = model, int(batch_size), float(decay), int(seed)
+        self.n_negs, self.neg_pool = int(n_negs), int(neg_pool)
         self.indptr, self.indices = csr.indptr.to(dev), csr.indices.to(dev)
         deg = self.indptr[1:] - self.indptr[:-1]
         self.eligible = torch.nonzero((deg > 0) & (deg < model.n_items)).reshape(-1)
@@ -196,8 +250,10 @@ class BPRTrainer:
         self._memset_G = False
 
     @torch.no_grad()
-    def sample(self):
-        """(users, pos, neg): int64 [batch_size] on the device, users sorted."""
+    def sample(self, M=None):
+        """(users, pos, neg): int64 [batch_size * n_negs] on the device, users sorted; triple j * n_negs + k is drawn pair j with
+        its k-th negative.  M: the propagated table the candidates of a pool are scored by (neg_pool > 1 only; propagated here
+        when not given)."""
         B, n = self.batch_size, self.eligible.numel()
         dev = self.eligible.device
         if n >= B:
@@ -205,10 +261,21 @@ class BPRTrainer:
         else:
             pick = torch.randint(0, n, (B,), generator=self.generator, device=dev)
         users = torch.sort(self.eligible[pick]).values
-        pos, neg = torch.empty_like(users), torch.empty_like(users)
-        _bpr_sample(self.lib, self.indptr, self.indices, users, self.model.n_users, self.model.n_items, self.seed, self.draws,
-                    pos, neg, self.flag, _lib.stream_ptr())
+        pos = torch.empty_like(users)
+        if self.n_negs == 1 and self.neg_pool == 1:
+            neg = torch.empty_like(users)
+            _bpr_sample(self.lib, self.indptr, self.indices, users, self.model.n_users, self.model.n_items, self.seed, self.draws,
+                        pos, neg, self.flag, _lib.stream_ptr())
+            self.draws += 1
+            return users, pos, neg
+        if self.neg_pool > 1 and M is None:
+            M = self.model._propagate(self.model.E0.weight.detach())[0]
+        neg = torch.empty(B * self.n_negs, dtype=torch.int64, device=dev)
+        _bpr_sample_pool(self.lib, self.indptr, self.indices, users, self.n_negs, self.neg_pool, self.model.n_users,
+                         self.model.n_items, M, self.seed, self.draws, pos, neg, self.flag, _lib.stream_ptr())
         self.draws += 1
+        if self.n_negs > 1:
+            users, pos = users.repeat_interleave(self.n_negs), pos.repeat_interleave(self.n_negs)
         return users, pos, neg
 
     def _ids(self, users, pos, neg):
@@ -228,20 +295,40 @@ class BPRTrainer:
 
     @torch.no_grad()
     def step(self, users=None, pos=None, neg=None):
-        """One optimiser step on the given triples (device tensors or host arrays), or on freshly sampled ones.  Returns
-        (mf, reg): 0-d float32 device tensors, the two losses of `bpr_loss` before the update."""
+        """One optimiser step on the given triples (device tensors or host arrays; n_negs and neg_pool play no part), or on
+        freshly sampled ones.  Returns (mf, reg): 0-d float32 device tensors, the two losses of `bpr_loss` before the update."""
+        out2 = self._step(users, pos, neg)
+        return out2[0], out2[1]
+
+    @torch.no_grad()
+    def train_epoch(self, n_steps):
+        """n_steps calls of step() on freshly sampled triples: the body of the reference's epoch loop (lightGCN.py:285-304)
+        without its .item() calls.  Returns (mean mf, mean reg) over the steps, 0-d float32 device tensors -- nothing
+        synchronises."""
+        if n_steps < 1:
+            raise ValueError("BPRTrainer.train_epoch: n_steps >= 1 expected")
+        mean = torch.stack([self._step() for _ in range(int(n_steps))]).mean(0)
+        return mean[0], mean[1]
+
+    @torch.no_grad()
+    def _step(self, users=None, pos=None, neg=None):
+        """step(), returning (mf, reg) as one float32 [2] device tensor"""
         m, lib = self.model, self.lib
+        E0 = m.E0.weight
+        M = None
         if users is None and pos is None and neg is None:
-            users, pos, neg = self.sample()
+            if self.neg_pool > 1:  # the sampler scores its candidates by the table the loss reads: one propagation for both
+                M = m._propagate(E0.detach())[0]
+            users, pos, neg = self.sample(M)
         else:
             users, pos, neg = self._ids(users, pos, neg)
-        E0 = m.E0.weight
         st = _lib.stream_ptr()
         B, U, It = users.numel(), m.n_users, m.n_items
         coef, ws = self._bufs.get(B) or self._bufs.setdefault(B, (torch.empty(B, dtype=torch.float32, device=E0.device),
                                                                    torch.empty(2 * B, dtype=torch.float32, device=E0.device)))
         out2 = torch.empty(2, dtype=torch.float32, device=E0.device)  # (fresh: the caller may keep the losses of many steps)
-        M = m._propagate(E0.detach())[0]
+        if M is None:
+            M = m._propagate(E0.detach())[0]
         _bpr_loss(lib, M, E0, users, pos, neg, U, It, coef, ws, out2, self.flag, st)
         order = _bpr_order(users, pos, neg, U)
         if self._memset_G:
@@ -258,7 +345,7 @@ class BPRTrainer:
         E0.grad = D
         self.opt.step()
         self.steps += 1
-        return out2[0], out2[1]
+        return out2
 
     def state_dict(self):
         """Everything but the model: with `model.state_dict()` a run resumes bit-exactly."""

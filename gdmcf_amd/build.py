@@ -16,12 +16,13 @@ SOURCES = ["capi.hip", "dp_exchange.hip", "gemm_f32.hip", "gemm_bf16.hip", "gemm
 HEADERS = ["common.h", "draws.h", "rank_order.h", "score_product.h", "spmm.h", "gemm_dr.h", "gemm_epilogue.h", os.path.join("..", "..", "include", "gdmcf_hip.h")]
 LIB = os.path.join(CSRC, "libgdmcf_hip.so")
 ASM_LINT = ("gemm_dr_tn.hip", "gemm_split.hip")  # disassembled and run through lint_vmcnt + lint_store_data at every build
-STORE_LINT = ("gemm_f32.hip", "gemm_bf16.hip", "gemm_dr_fat.hip", "gemm_dr_kn.hip", "score_topk.hip", "score_rank.hip", "latent_step.hip")  # disassembled for lint_store_data only
-NO_SPILL = ("gemm_f32.hip", "gemm_bf16.hip", "gemm_split.hip", "gemm_dr_tn.hip", "score_topk.hip", "score_rank.hip", "cat.hip", "gather_fwd.hip", "ntxent.hip", "latent_step.hip", "cand_scores.hip")  # kernels with uncounted asm loads (and score_topk.hip and score_rank.hip, whose
+STORE_LINT = ("gemm_f32.hip", "gemm_bf16.hip", "gemm_dr_fat.hip", "gemm_dr_kn.hip", "score_topk.hip", "score_rank.hip", "latent_step.hip", "bpr.hip")  # disassembled for lint_store_data only
+NO_SPILL = ("gemm_f32.hip", "gemm_bf16.hip", "gemm_split.hip", "gemm_dr_tn.hip", "score_topk.hip", "score_rank.hip", "cat.hip", "gather_fwd.hip", "ntxent.hip", "latent_step.hip", "cand_scores.hip", "bpr.hip")  # kernels with uncounted asm loads (and score_topk.hip and score_rank.hip, whose
 # register budget is the user fragments; cat.hip, whose two passes are meant to be bound by HBM alone; gather_fwd.hip, whose unrolled row
 # loads must stay in registers to be in flight together; ntxent.hip, whose gradient kernel keeps 16 operand loads and four accumulator
 # tiles in flight per step; latent_step.hip, whose operand loads of two chunks must be in flight beside four accumulator tiles; cand_scores.hip, whose
-# user row lives in registers beside four candidate rows in flight): a spill is a build error
+# user row lives in registers beside four candidate rows in flight; bpr.hip, whose pool sampler keeps the user row and the next candidate's
+# row in registers over each reduction): a spill is a build error
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -7,6 +7,11 @@
 // product is reduced inside the group by xor shuffles.  d % 4 != 0 (or unaligned rows) takes the same kernels with element-wise
 // loads and stores.
 //
+// gdmcf_bpr_sample_pool_f32 generalises the reference's per-user draw (lightGCN.py:225-246: one positive, one negative) to
+// n_negs negatives per positive, each the best-scored of `pool` uniform candidates under the current propagated table
+// (dynamic negative sampling); n_negs = pool = 1 is gdmcf_bpr_sample_f32's draw bit for bit.  It gathers B n_negs (1 + pool)
+// rows and is latency bound like the rest: a lane group per slot, the next candidate's row in flight over each reduction.
+//
 // Nothing here uses a float atomic: the loss is reduced from per-triple partials in one fixed order, and the scatter gives every
 // destination row ONE writer that adds the row's contributions in sorted order (gdmcf_bpr_grad_f32), so results are the same
 // bits in every run whatever ids repeat.
@@ -78,6 +83,109 @@ __global__ __launch_bounds__(256) void bpr_sample_kernel(const int64_t* __restri
         if (row[mid] - mid > r) hi = mid; else lo = mid + 1;
     }
     neg[j] = r + lo;
+}
+
+// ---------------------------------------------------------------------------------------------
+// (a') sampler with n_negs negatives per positive, each the best of a pool of candidates: one lane group per slot (j, k)
+// ---------------------------------------------------------------------------------------------
+// the word of candidate q of triple j (draws.h, GD_STREAM_BPR): q < 3 is word y, z, w of block 0 (word x draws the positive),
+// q >= 3 word (q - 3) % 4 of block 1 + (q - 3) / 4.  `first` receives word x of the block the candidate came from.
+__device__ __forceinline__ uint32_t bpr_candidate_word(int j, int q, uint64_t seed, uint64_t offset, uint32_t& first) {
+    const int blk = q < 3 ? 0 : 1 + ((q - 3) >> 2), word = q < 3 ? q + 1 : (q - 3) & 3;
+    const uint4 w = gd_philox_block((uint32_t)j, blk, GD_STREAM_BPR, offset, gd_philox_key(seed));
+    first = w.x;
+    return word == 0 ? w.x : word == 1 ? w.y : word == 2 ? w.z : w.w;
+}
+
+// the r-th item (from 0) that is NOT in the sorted row: bpr_sample_kernel's search
+__device__ __forceinline__ int bpr_nth_missing(const int32_t* __restrict__ row, int deg, int r) {
+    int lo = 0, hi = deg;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (row[mid] - mid > r) hi = mid; else lo = mid + 1;
+    }
+    return r + lo;
+}
+
+__device__ __forceinline__ float bpr_dot4(const f32x4& a, const f32x4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+// Slot s = j * n_negs + k.  Lane l of the group draws and searches candidates c = l, l + LG, ... of the slot's pool (number
+// q = k * pool + c of the triple), then the group walks LG candidates at a time by shuffle: one item row against the user row
+// (one float4 per lane, held in registers), the row of the next candidate loaded before the current one is reduced.  Every lane
+// holds the same score after the xor reduction, so all keep the same best; lane 0 stores.  pool == 1 is launched with LG = 1 and
+// M == nullptr: the one candidate is the negative and nothing is scored.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bpr_sample_pool_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                                               const int64_t* __restrict__ users, int B, int n_negs, int pool,
+                                                               int n_users, int n_items, const float* __restrict__ M, int64_t ldm,
+                                                               int d, int LG, uint64_t seed, uint64_t offset,
+                                                               int64_t* __restrict__ pos, int64_t* __restrict__ neg,
+                                                               int32_t* __restrict__ flag) {
+    const int tid = threadIdx.x;
+    const int g = tid / LG, l = tid - g * LG;
+    const int64_t s = (int64_t)blockIdx.x * (256 / LG) + g;
+    if (s >= (int64_t)B * n_negs) return;  // (whole groups leave: the shuffles below stay inside a group)
+    const int j = (int)(s / n_negs), k = (int)(s - (int64_t)j * n_negs);
+    const int64_t u = users[j];
+    int64_t beg = 0, deg64 = 0;
+    if (u >= 0 && u < n_users) {
+        beg = indptr[u];
+        deg64 = indptr[u + 1] - beg;
+    }
+    if (deg64 <= 0 || deg64 >= n_items) {  // nothing to draw a positive (or a negative) from
+        if (l == 0) {
+            if (k == 0) pos[j] = -1;
+            neg[s] = -1;
+            if (flag) *flag = 1;
+        }
+        return;
+    }
+    const int deg = (int)deg64;
+    const int32_t* __restrict__ row = indices + beg;
+    const bool score = M != nullptr && pool > 1;
+    const int ncc = (d + 4 * LG - 1) / (4 * LG);  // column passes (1 up to d = 256): the same count in every lane
+    const float* __restrict__ mu = score ? M + u * ldm : nullptr;
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f};
+    if (score) a0 = bpr_load4<VEC>(mu, 4 * l, d);  // the user row: once per slot
+    int best = 0;
+    float best_score = 0.f;
+    for (int cb = 0; cb < pool; cb += LG) {
+        const int c = cb + l;
+        int cand = 0;
+        if (c < pool) {
+            uint32_t first;
+            const uint32_t w = bpr_candidate_word(j, k * pool + c, seed, offset, first);
+            cand = bpr_nth_missing(row, deg, (int)bpr_mulhi(w, (uint32_t)(n_items - deg)));
+            if (k == 0 && c == 0) pos[j] = row[bpr_mulhi(first, (uint32_t)deg)];  // (candidate 0 of the triple lives in block 0)
+        }
+        if (!score) {  // pool == 1 (LG = 1): the candidate is the negative
+            best = cand;
+            break;
+        }
+        const int nv = min(LG, pool - cb);
+        int ci = __shfl(cand, 0, LG);
+        f32x4 b = bpr_load4<VEC>(M + ((int64_t)n_users + ci) * ldm, 4 * l, d);
+        for (int i = 0; i < nv; ++i) {
+            const int cn = __shfl(cand, min(i + 1, nv - 1), LG);
+            const float* __restrict__ mi = M + ((int64_t)n_users + ci) * ldm;
+            f32x4 bn = b;
+            if (i + 1 < nv) bn = bpr_load4<VEC>(M + ((int64_t)n_users + cn) * ldm, 4 * l, d);  // in flight over the reduction
+            float sc = bpr_dot4(a0, b);
+            for (int cc = 1; cc < ncc; ++cc) {
+                const int c0 = 4 * (l + cc * LG);
+                sc += bpr_dot4(bpr_load4<VEC>(mu, c0, d), bpr_load4<VEC>(mi, c0, d));
+            }
+            for (int m = LG >> 1; m > 0; m >>= 1) sc += __shfl_xor(sc, m);  // (groups are aligned: lane ^ m stays inside)
+            // the first candidate is kept; a later one replaces it only with a strictly greater score (never with a NaN)
+            if ((cb == 0 && i == 0) || sc > best_score) {
+                best = ci;
+                best_score = sc;
+            }
+            ci = cn;
+            b = bn;
+        }
+    }
+    if (l == 0) neg[s] = best;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -292,6 +400,31 @@ int gdmcf_bpr_sample_f32(const int64_t* indptr, const int32_t* indices, const in
     hipLaunchKernelGGL(bpr_sample_kernel, dim3(gd_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, indptr, indices, users, B,
                        n_users, n_items, seed, offset, pos, neg, flag);
     return gd_launch_status("bpr_sample");
+}
+
+int gdmcf_bpr_sample_pool_f32(const int64_t* indptr, const int32_t* indices, const int64_t* users, int B, int n_negs, int pool,
+                              int n_users, int n_items, const float* M, int64_t ldm, int d, uint64_t seed, uint64_t offset,
+                              int64_t* pos, int64_t* neg, int32_t* flag, void* stream) {
+    GD_CHECK_SHAPE(B > 0 && n_negs > 0 && pool > 0 && n_users > 0 && n_items > 0, "bpr_sample_pool: bad shape");
+    GD_CHECK_SHAPE((int64_t)n_negs * pool < (1 << 20), "bpr_sample_pool: n_negs * pool must stay below 2^20");
+    GD_CHECK_SHAPE(M == nullptr || (d >= 1 && ldm >= d), "bpr_sample_pool: bad table shape");
+    GD_CHECK_OFFSET(offset, "bpr_sample_pool");
+    GD_CHECK_ARG(indptr && indices && users && pos && neg, "bpr_sample_pool: null pointer");
+    GD_CHECK_ARG(M != nullptr || pool == 1, "bpr_sample_pool: a pool of candidates needs the propagated table");
+    const bool scored = pool > 1;
+    const int LG = scored ? bpr_lane_group(d) : 1;  // nothing to score: one thread per slot
+    GD_CHECK_SHAPE((int64_t)B * n_negs * LG < 2147483647LL && (int64_t)n_users + n_items < 2147483647LL,
+                   "bpr_sample_pool: batch or table too large");
+    const bool vec = scored && d % 4 == 0 && ldm % 4 == 0 && gd_aligned16(M);
+    const dim3 grid((unsigned)(((int64_t)B * n_negs + 256 / LG - 1) / (256 / LG)));
+    const float* table = scored ? M : nullptr;
+    if (vec)
+        hipLaunchKernelGGL(bpr_sample_pool_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, indptr, indices, users, B, n_negs,
+                           pool, n_users, n_items, table, ldm, d, LG, seed, offset, pos, neg, flag);
+    else
+        hipLaunchKernelGGL(bpr_sample_pool_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, indptr, indices, users, B, n_negs,
+                           pool, n_users, n_items, table, ldm, d, LG, seed, offset, pos, neg, flag);
+    return gd_launch_status("bpr_sample_pool");
 }
 
 int gdmcf_bpr_loss_f32(const float* M, int64_t ldm, const float* E0, int64_t lde, int d, const int64_t* users, const int64_t* pos,

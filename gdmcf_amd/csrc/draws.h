@@ -23,6 +23,10 @@ enum : uint32_t {
     GD_STREAM_GRAPH_CLASS = 5,   // noise.hip: graph_step_kernel, the edge classes
     GD_STREAM_GRAPH_PICK = 6,    // noise.hip: graph_step_kernel, one bit per user, counter (0xFFFFFFFF, b, 6, offset)
     GD_STREAM_BPR = 7,           // bpr.hip: the triple sampler, counter (j, 0, 7, offset); also the reverse loop's randn_kernel fills
+    // Triple j of the sampler owns the blocks (j, 0), (j, 1), ...: word x of block 0 draws the positive, and candidate number
+    // q = k * pool + c (negative slot k, pool position c) takes word y, z, w of block 0 for q = 0, 1, 2 and word (q - 3) % 4 of
+    // block (j, 1 + (q - 3) / 4) for q >= 3 (gdmcf_bpr_sample_pool_f32).  The one-negative draw of gdmcf_bpr_sample_f32 is
+    // q = 0 of this layout, not a second scheme.
 };
 
 // ---- launch geometry of the builders, of randn_kernel and of the cat kernels ---------------------------------------------------

@@ -17,8 +17,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .bpr import (BPRTrainer, _bpr_grad, _bpr_loss, _bpr_operands, _bpr_order, _bpr_sample, bpr_loss, bpr_loss_grad,  # noqa: F401
-                  bpr_reg_grad_, sample_bpr_batch, sample_bpr_items)
+from .bpr import (BPRTrainer, _bpr_grad, _bpr_loss, _bpr_operands, _bpr_order, _bpr_sample, _bpr_sample_pool, bpr_loss,  # noqa: F401
+                  bpr_loss_grad, bpr_reg_grad_, sample_bpr_batch, sample_bpr_items, sample_bpr_negatives)
 from .lightgcn_eval import _check_Ks, _history_rows, get_metrics, get_metrics_at, hits_from_ranks, ranking_terms  # noqa: F401
 from .spmm_schedule import (SPMM_CHUNK, SPMM_COST_PIECE, SPMM_COST_ROW, SPMM_HOT_MB, SPMM_MISS_W, SPMM_NT, SPMM_PIECE,  # noqa: F401
                             SPMM_SHORT, SPMM_SLICE_MB, SPMM_SMAX, SPMM_WAVES, SpmmSchedule, pick_generation, spmm_bundle_plan,

@@ -715,6 +715,23 @@ int gdmcf_scale_f32(const float* acc, int64_t n, float scale, float* out, void* 
  * A user outside [0, n_users), or with deg == 0 or deg == n_items, gets pos = neg = -1 and *flag (int32, optional) = 1.   */
 int gdmcf_bpr_sample_f32(const int64_t* indptr, const int32_t* indices, const int64_t* users, int B, int n_users, int n_items,
                          uint64_t seed, uint64_t offset, int64_t* pos, int64_t* neg, int32_t* flag, void* stream);
+/* gdmcf_bpr_sample_pool_f32 generalises that draw (lightGCN.py:225-246) to n_negs negatives per positive, each the
+ * best-scored of `pool` candidates under the propagated table M [n_users + n_items, ldm] (dynamic negative sampling).
+ * pos [B] as above: row[mulhi(x, deg)], x the first word of the block with counter (j, 0, 7, offset).  neg [B * n_negs],
+ * neg[j * n_negs + k] = the negative of slot k.  Candidate q = k * pool + c of triple j (pool position c) is the
+ * mulhi(w_q, n_items - deg)-th item missing from the row (the same binary search); w_q is word y, z, w of block 0 for
+ * q = 0, 1, 2 and word (q - 3) % 4 of the block with counter (j, 1 + (q - 3) / 4, 7, offset) for q >= 3, so
+ * n_negs = pool = 1 is gdmcf_bpr_sample_f32 bit for bit.  Candidates are independent: repeats inside a pool and between
+ * slots are allowed.  pool == 1: the candidate is the negative and M is not read (M may be NULL).  pool > 1: the score of
+ * candidate i is the float32 dot product <M[users[j]], M[n_users + i]>; the slot keeps its first candidate unless a later
+ * one scores strictly greater (equal scores keep the earliest drawn; a NaN score never replaces anything).  One lane group
+ * per slot (j, k) as gdmcf_bpr_loss_f32, one thread per slot at pool == 1; no atomics.  A user outside [0, n_users), or
+ * with deg == 0 or deg == n_items, gets pos = -1, all n_negs negatives -1 and *flag (int32, optional) = 1.
+ * E_SHAPE: B, n_negs or pool < 1, n_negs * pool >= 2^20, d < 1 or ldm < d with M given; E_ARG: a null pointer, M == NULL
+ * with pool > 1.                                                                                                         */
+int gdmcf_bpr_sample_pool_f32(const int64_t* indptr, const int32_t* indices, const int64_t* users, int B, int n_negs, int pool,
+                              int n_users, int n_items, const float* M, int64_t ldm, int d, uint64_t seed, uint64_t offset,
+                              int64_t* pos, int64_t* neg, int32_t* flag, void* stream);
 /* gdmcf_bpr_loss_f32 replaces the six row gathers of LightGCN.forward (lightGCN.py:200-201) and bpr_loss (:207-219):
  *   coef[j] = sigmoid(x_j) / B           the derivative of mean_j softplus(x_j) (torch's softplus: linear above 20)
  *   *mf     = mean_j softplus(x_j)

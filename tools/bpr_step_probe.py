@@ -1,6 +1,7 @@
 """One LightGCN BPR training step, the autograd route against the fused one, back to back in one process.
 
     python tools/bpr_step_probe.py [--steps 50] [--warmup 5] [--rounds 5] [--out profiles/bpr_step_probe_yelp.json]
+    python tools/bpr_step_probe.py --legs fused_device_sampler --n-negs 1,4,1,4 --neg-pool 1,1,8,8    # the sampler's knobs
 
 Yelp shape (54 574 users, 34 395 items, d = 64, 3 layers, batch 1024, decay 1e-4, lr 0.005).  After the same untimed clock
 pre-heat as bench.py, the legs alternate on ONE model for `rounds` rounds, each leg `warmup` untimed steps then `steps` timed
@@ -12,6 +13,9 @@ ones between two device synchronisations:
   fused_device_sampler  BPRTrainer.step(): users by a device generator, items by gdmcf_bpr_sample_f32
   fused_memset          fused_presampled with the cotangent table zeroed by a memset every step (BPRTrainer._memset_G) instead of the
                         regulariser pass clearing the rows the scatter wrote (the product path, the other fused legs)
+  fused_device_sampler_n<N>_p<P>   the same from a BPRTrainer(n_negs=N, neg_pool=P): one leg per pair of --n-negs / --neg-pool
+                        (comma-separated lists of equal length; the pair 1, 1 is fused_device_sampler itself).  Each such leg
+                        also reports the bytes its step gathers, B * n_negs * (1 + pool) * 4 d.
 ms per step = median over the rounds; *_legs_ms every round; *_spread_ms = max - min of the rounds, the noise a difference has
 to exceed; *_host_enqueue_ms: host time until the last step is enqueued.  --legs runs a subset (one leg alone: the program to
 put under rocprofv3 --kernel-trace --stats); --stats-csv FILE --stats-steps N condenses that run's kernel_stats.csv into
@@ -58,6 +62,8 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--preheat-seconds", type=float, default=1.5)
     ap.add_argument("--legs", default=",".join(LEGS))
+    ap.add_argument("--n-negs", default="1", help="negatives per positive, one value per configuration (comma-separated)")
+    ap.add_argument("--neg-pool", default="1", help="candidates per negative, one value per configuration (comma-separated)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--stats-csv", default=None, help="condense a rocprofv3 kernel_stats.csv (of --stats-steps steps) and exit")
     ap.add_argument("--stats-steps", type=int, default=0)
@@ -117,6 +123,20 @@ def main(argv=None):
                "fused_device_sampler": lambda i: trainers["rows"].step()[0],
                "fused_memset": lambda i: trainers["memset"].step(*batches[i % 4])[0]}
     legs_run = [leg for leg in args.legs.split(",") if leg]
+    knobs = list(zip([int(v) for v in args.n_negs.split(",")], [int(v) for v in args.neg_pool.split(",")]))
+    if len(args.n_negs.split(",")) != len(args.neg_pool.split(",")):
+        ap.error("--n-negs and --neg-pool take lists of one length")
+    gathered = {}
+    for n, p in (knobs if knobs != [(1, 1)] else []):
+        if (n, p) == (1, 1):
+            leg = "fused_device_sampler"
+        else:
+            leg = f"fused_device_sampler_n{n}_p{p}"
+            trainers[leg] = BPRTrainer(m, R, batch_size=B, lr=lr, decay=decay, n_negs=n, neg_pool=p)
+            step_of[leg] = lambda i, t=trainers[leg]: t.step()[0]
+        gathered[leg] = B * n * (1 + p) * 4 * d
+        if leg not in legs_run:
+            legs_run.append(leg)
     preheat = clock_preheat(lib, dev, args.preheat_seconds)
     legs, host, loss = {k: [] for k in legs_run}, {k: [] for k in legs_run}, {}
     for _ in range(args.rounds):
@@ -137,6 +157,8 @@ def main(argv=None):
         res[leg] = dict(ms_per_step=round(statistics.median(legs[leg]), 4), legs_ms=[round(v, 4) for v in legs[leg]],
                         spread_ms=round(max(legs[leg]) - min(legs[leg]), 4),
                         host_enqueue_ms_per_step=round(statistics.median(host[leg]), 4), last_mf=round(loss[leg], 6))
+        if leg in gathered:
+            res[leg]["gathered_bytes_per_step"] = gathered[leg]
     verdict = {}
     for new, old in (("fused_presampled", "autograd_presampled"), ("fused_device_sampler", "autograd_host_sampler"),
                      ("fused_presampled", "fused_memset")):
