@@ -399,7 +399,19 @@ class SpmmSchedule:
 
     def launch(self, X, n_rows, n_x_rows, out, addends, scale, alg_bytes, stream):
         """out[:n_rows] <- (A X + sum of `addends`) * scale, enqueued on `stream`.  X: float32 [n_x_rows, d]; `addends`: tensors
-        of one row stride whose row i goes with row i of the matrix; alg_bytes: the layer's compulsory HBM bytes (profiling)."""
+        of one row stride whose row i goes with row i of the matrix; alg_bytes: the layer's compulsory HBM bytes (profiling).
+        The C entry sees pointers and ONE addend stride only: what it cannot check is refused here with ValueError."""
+        for name, t in [("X", X), ("out", out)] + [(f"addend {k}", a) for k, a in enumerate(addends)]:
+            if t.dtype != torch.float32:
+                raise ValueError(f"SpmmSchedule.launch: {name} must be float32, not {t.dtype}")
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"SpmmSchedule.launch: {name} must be 2-D with unit inner stride (strides {tuple(t.stride())})")
+        if len({a.stride(0) for a in addends}) > 1:
+            raise ValueError(f"SpmmSchedule.launch: the addends must share one row stride, not {[a.stride(0) for a in addends]}")
+        if X.shape[0] < n_x_rows:
+            raise ValueError(f"SpmmSchedule.launch: X has {X.shape[0]} rows, the matrix gathers from {n_x_rows}")
+        if out.shape[0] < n_rows:
+            raise ValueError(f"SpmmSchedule.launch: out has {out.shape[0]} rows, the matrix has {n_rows}")
         lib, pl = _lib.load(), self.plan
         d = X.shape[1]
         arr = (ctypes.c_void_p * max(len(addends), 1))(*[a.data_ptr() for a in addends])
