@@ -193,6 +193,8 @@ int gdmcf_row_loss_finish_mean_f64(const float* rowsum, const float* rowdiv, con
                                    int64_t* Lt_count, int update_history, double* loss_unscaled, double* loss,
                                    float* gradcoef, double* loss_mean, float* rowscale_mean, void* stream) {
     GD_CHECK_SHAPE(B > 0 && T > 0 && H > 0, "row_loss_finish: bad shape");
+    GD_CHECK_ARG(rowsum && rowdiv && ts && weight_t && pt && loss_unscaled && loss, "row_loss_finish: null pointer");
+    GD_CHECK_ARG(!update_history || (Lt_history && Lt_count), "row_loss_finish: update_history without the history");
     GD_CHECK_ARG(!rowscale_mean || gradcoef, "row_loss_finish: rowscale_mean needs gradcoef");
     const size_t lds = lt_lds_bytes(T, H, B);
     GD_CHECK_ARG(lds <= 150 * 1024, "row_loss_finish: T*H and B too large for the LDS-resident FIFO update (150 KiB)");
@@ -207,6 +209,7 @@ int gdmcf_row_loss_finish_mean_f64(const float* rowsum, const float* rowdiv, con
 int gdmcf_lt_history_update(const int64_t* ts, const double* loss_unscaled, int B, int T, int H, double* Lt_history,
                             int64_t* Lt_count, void* stream) {
     GD_CHECK_SHAPE(B > 0 && T > 0 && H > 0, "lt_history_update: bad shape");
+    GD_CHECK_ARG(ts && loss_unscaled && Lt_history && Lt_count, "lt_history_update: null pointer");
     const size_t lds = lt_lds_bytes(T, H, B);
     GD_CHECK_ARG(lds <= 150 * 1024, "lt_history_update: T*H and B too large for the LDS-resident FIFO update (150 KiB)");
     static bool attr_set = false;

@@ -344,7 +344,8 @@ int gdmcf_scatter_rows_adamw_f32(const float* src, int64_t lds, const int64_t* i
 
 int gdmcf_emb_bwd_f32(const float* dZ1, int64_t lddz, const float* W1, int64_t ldw, int I, int E, const float* temb,
                       int M, int N, float* demb_ws, float* dWe, float* dbe, void* stream) {
-    GD_CHECK_SHAPE(M > 0 && N > 0 && E > 0 && ldw >= I + E && lddz >= N, "emb_bwd: bad shape");
+    GD_CHECK_SHAPE(M > 0 && N > 0 && E > 0 && I >= 0 && ldw >= I + E && lddz >= N, "emb_bwd: bad shape");
+    GD_CHECK_ARG(dZ1 && W1 && temb && demb_ws && dWe && dbe, "emb_bwd: null pointer");
     hipStream_t s = (hipStream_t)stream;
     float* W1e = demb_ws + (size_t)M * E;  // demb_ws holds [M*E] demb followed by [N*E] gathered weights
     hipLaunchKernelGGL(emb_gather_w_kernel, dim3(gd_cdiv(N * E, 256)), dim3(256), 0, s, W1, ldw, I, E, N, W1e);
@@ -356,6 +357,7 @@ int gdmcf_emb_bwd_f32(const float* dZ1, int64_t lddz, const float* W1, int64_t l
 int gdmcf_densify_rows_f32(const int64_t* indptr, const int32_t* indices, const float* values, const int64_t* row_ids,
                            int B, int I, float* out, int64_t ldo, void* stream) {
     GD_CHECK_SHAPE(B > 0 && I > 0 && ldo >= I, "densify_rows: bad shape");
+    GD_CHECK_ARG(indptr && indices && out, "densify_rows: null pointer");
     hipLaunchKernelGGL(densify_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, indptr, indices, values, row_ids,
                        I, out, ldo);
     return gd_launch_status("densify_rows");
@@ -363,6 +365,7 @@ int gdmcf_densify_rows_f32(const int64_t* indptr, const int32_t* indices, const 
 
 int gdmcf_scale_f32(const float* acc, int64_t n, float scale, float* out, void* stream) {
     GD_CHECK_SHAPE(n > 0, "scale: empty");
+    GD_CHECK_ARG(acc && out, "scale: null pointer");
     hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, acc, n,
                        scale, out);
     return gd_launch_status("scale");

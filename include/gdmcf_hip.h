@@ -87,7 +87,9 @@ int gdmcf_schedule_build(int kind, double noise_scale, double noise_min, double 
  * replaces DataDiffusion.__getitem__ + DataLoader collation + batch.to(device)
  * (data_utils.py:216-226, main.py:155,343): out[b, 0:I] = dense row row_ids[b] (row_ids NULL -> b).
  * indptr int64 [n_users+1], indices int32, values float32 or NULL (all ones); rows must hold each
- * column at most once (scipy's csr_matrix constructor has already summed duplicates).        */
+ * column at most once (scipy's csr_matrix constructor has already summed duplicates).  Columns
+ * outside [0, I) are skipped.  values and row_ids are optional; indptr, indices and out are
+ * required (GDMCF_E_ARG).                                                                    */
 int gdmcf_densify_rows_f32(const int64_t* indptr, const int32_t* indices, const float* values,
                            const int64_t* row_ids, int B, int I, float* out, int64_t ldo, void* stream);
 
@@ -431,7 +433,8 @@ int gdmcf_scatter_rows_adamw_f32(const float* src, int64_t lds, const int64_t* i
                                  void* stream);
 /* Gradients of the timestep-embedding branch (models/DNN.py:73-74,78):
  *   demb[m,e] = sum_n dZ1[m,n]*W1[n, I+e] ;  dWe = demb^T @ temb ;  dbe = sum_m demb
- * demb_ws: float32 scratch of (M + N) * E elements.                                         */
+ * demb_ws: float32 scratch of (M + N) * E elements.  dWe [E, E] and dbe [E] are overwritten, not
+ * accumulated into.  No pointer is optional (GDMCF_E_ARG for a NULL); I >= 0.                 */
 int gdmcf_emb_bwd_f32(const float* dZ1, int64_t lddz, const float* W1, int64_t ldw, int I, int E,
                       const float* temb, int M, int N, float* demb_ws, float* dWe, float* dbe,
                       void* stream);
@@ -443,7 +446,9 @@ int gdmcf_emb_bwd_f32(const float* dZ1, int64_t lddz, const float* W1, int64_t l
  * gradcoef[b] (optional) = d loss[b] / d out[b,n] / diff[b,n] = 2*alpha[b]*weight/(pt*rowdiv),
  * the per-row factor the backward multiplies `diff` by (alpha NULL -> 1).
  * update_history == 0 leaves the ring buffer untouched (data-parallel ranks call
- * gdmcf_lt_history_update on the gathered batch instead).                                  */
+ * gdmcf_lt_history_update on the gathered batch instead).
+ * Optional pointers (NULL allowed): alpha, gradcoef, and Lt_history / Lt_count when update_history == 0.  Every other
+ * pointer is required (GDMCF_E_ARG for a NULL).  ts must lie in [0, T): it is not checked.    */
 int gdmcf_row_loss_finish_f64(const float* rowsum, const float* rowdiv, const float* alpha,
                               const int64_t* ts, const double* weight_t, const double* pt, int B,
                               int T, int H, double* Lt_history, int64_t* Lt_count,
@@ -451,7 +456,9 @@ int gdmcf_row_loss_finish_f64(const float* rowsum, const float* rowdiv, const fl
                               float* gradcoef, void* stream);
 /* The same tail, additionally emitting what the reference's step computes next (main.py:348-350): loss_mean (optional,
  * float64 scalar) = mean_b loss[b], summed in a fixed order, and rowscale_mean[b] (optional, float32) = gradcoef[b] *
- * (float)(1/B) -- the per-row scale of the backward of that mean -- so that the step needs no reduction / scaling launch. */
+ * (float)(1/B) -- the per-row scale of the backward of that mean -- so that the step needs no reduction / scaling launch.
+ * loss_mean and rowscale_mean are optional like alpha and gradcoef above; rowscale_mean needs gradcoef (GDMCF_E_ARG without).
+ * gdmcf_lt_history_update has no optional pointer. */
 int gdmcf_row_loss_finish_mean_f64(const float* rowsum, const float* rowdiv, const float* alpha, const int64_t* ts,
                                    const double* weight_t, const double* pt, int B, int T, int H, double* Lt_history,
                                    int64_t* Lt_count, int update_history, double* loss_unscaled, double* loss,
@@ -697,7 +704,7 @@ int gdmcf_adam_hyper_fill(void* out_host, int n, float lr, float beta1, float be
                           int64_t first_step, float grad_scale);
 int gdmcf_graph_state_bind(const void* state_dev);
 int gdmcf_graph_state_tick(void* state_dev, void* stream);
-/* out = acc * scale */
+/* out = acc * scale, n > 0 elements; both pointers are required (GDMCF_E_ARG for a NULL) */
 int gdmcf_scale_f32(const float* acc, int64_t n, float scale, float* out, void* stream);
 
 /* ---- LightGCN BPR training step (lightGCN.py:207-251, :287-300; csrc/bpr.hip) -------------------------------------------
