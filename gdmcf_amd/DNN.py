@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from . import _lib
 from .engine import DenoiserEngine
+from .reverse_route import Carries
 
 
 def timestep_embedding(timesteps, dim, max_period=10000):
@@ -50,6 +51,7 @@ class _DNNForward(torch.autograd.Function):
 
 class DNN(nn.Module):
     """A deep neural network for the reverse diffusion process (drop-in for the reference DNN)."""
+    reverse_carries = Carries("base", True)
 
     def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, gemm_dtype="f32"):
         super().__init__()

@@ -33,6 +33,7 @@ from . import engine_core as core
 from .engine import DenoiserEngine
 from .engine_core import _Bufs, with_precision
 from .onehot import OneHotEngine
+from .reverse_route import Carries
 
 
 class CatEngine(DenoiserEngine):
@@ -253,6 +254,8 @@ class CatEngine(DenoiserEngine):
 class DNNCat(nn.Module):
     """Drop-in for the reference DNNCat (models/DNN.py:180-265)."""
 
+    # the latent loop under latent="extended" only; CSR rows on that route only, without a second-branch handle (xU0 = 1 - x, xU1 = x)
+    reverse_carries = Carries("extended", False, sparse_latent=True, second_handle=False)
     csr_rows = False  # training_losses densifies a CsrBatch for this backbone unless the instance was built with csr_rows=True
     fused_update_refusal = ("the input gradient of the first layer reads its weight, which a fused update would overwrite "
                             "first; use the separate AdamW pass")

@@ -85,11 +85,10 @@ class CsrBatch:
     else -- F.normalize, the eps target, values other than 1, torch-drawn noise -- is densified inside `training_losses`
     (`dense()`) and goes on as a dense batch, with the same results.
     The reverse loop (`p_sample`, `driver.evaluate(sparse=True)`) takes a CsrBatch as well.  With steps == 0 x_T is x_0 itself, so
-    in eval mode (binary rows, no F.normalize, float32 products; DNN, DNNOneHot, DNNOneHotEmbedding) the first reverse step's first
-    hidden layer is a sum of the rows' few dozen weight rows (gdmcf_gather_fwd_f32) instead of a [B, I] product, and the one-hot
-    backbones' second branch -- whose image is the same at every step -- is gathered once per batch; the dense x_t the posterior
-    needs is written by the CSR-fed builder.  Anything else (steps > 0, F.normalize, values other than 1, bf16 / f32x3, DNNCat, the
-    GCN backbone) is densified inside `p_sample` and gives the dense route's bits."""
+    where the rows stay sparse ("Routes") the first reverse step's first hidden layer is a sum of the rows' few dozen
+    weight rows (gdmcf_gather_fwd_f32) instead of a [B, I] product, and the one-hot backbones' second branch -- whose image is the
+    same at every step -- is gathered once per batch; the dense x_t the posterior needs is written by the CSR-fed builder.
+    Anything else is densified inside `p_sample` and gives the dense route's bits."""
 
     def __init__(self, csr, row_ids):
         self.csr = csr

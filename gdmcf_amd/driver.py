@@ -7,12 +7,12 @@ on top of the HIP path.  Host glue only: batches in, metrics out.
   The reference moves a dense [B, I] row block to the device per batch and masks with
   `prediction[his_data.nonzero()] = -inf`; here the history stays CSR and the mask is applied inside the
   top-k kernel.  `sparse=True` hands p_sample the rows as a CsrBatch as well: with sampling_steps == 0 the first layers of the
-  reverse loop then gather the rows' weight rows instead of multiplying a dense batch (GaussianDiffusion._sparse_reverse_ok).
+  reverse loop then gather the rows' weight rows instead of multiplying a dense batch (routes: DESIGN 4.9).
 """
 import numpy as np
 import torch
 
-from . import evaluate_utils
+from . import evaluate_utils, reverse_route
 from .data_utils import DeviceBatchLoader, DeviceCSR
 from .evaluate_utils import masked_topk
 from .parallel import DataParallelStep
@@ -54,9 +54,8 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
     data_csr: rows fed to p_sample (the reference feeds the training rows); data_te: ground-truth CSR;
     mask_his: CSR of interactions to exclude from the ranking.  sparse=True: p_sample receives each batch as a
     data_utils.CsrBatch (never densified where the reverse loop takes sparse rows; densified inside p_sample otherwise).
-    latent=True: p_sample(latent=True) -- the reverse loop in the first hidden layer's space where
-    GaussianDiffusion._latent_reverse_ok holds; composes with sparse=True.  latent="extended" is passed through as it is
-    (the EPSILON target and DNNCat too), also to gdmcf_amd.recommend with recommend=True.
+    latent=True / "extended": passed to p_sample -- the reverse loop in the first hidden layer's space where it can run there
+    (routes: DESIGN 4.9); composes with sparse=True.  "extended" is also passed to gdmcf_amd.recommend with recommend=True.
     recommend=True: each batch's list comes from gdmcf_amd.recommend with mask_his as a DeviceCSR -- uploaded once
     per call, or passed through when it already is one -- so no batch slices a matrix on the host; `sparse` is then ignored and
     of `latent` only the value "extended" matters (recommend picks its own route, `diffusion.last_recommend_route`).
@@ -70,6 +69,7 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
     if ranks and (not recommend or candidates is not None):
         raise ValueError("driver.evaluate: ranks=True needs recommend=True and takes no candidates")
     model.eval()
+    extended = {} if reverse_route.latent_mode(latent) in (None, "base") else dict(latent=latent)  # (recommend's default: True)
     n = mask_his.shape[0]
     predict_items = []
     dcsr = data_csr if isinstance(data_csr, DeviceCSR) else DeviceCSR(data_csr, device)
@@ -81,20 +81,18 @@ def evaluate(diffusion, model, data_csr, data_te, mask_his, topN, sampling_steps
             gt = data_te.tocsr().astype(np.float32, copy=True)  # (the ground truth as computeTopNAccuracy_device reads it)
             gt.eliminate_zeros()
             got = rank_targets(diffusion, model, dcsr, np.arange(n), DeviceCSR(gt, device), mask=mask, sampling_steps=sampling_steps,
-                               sampling_noise=sampling_noise, batch_size=batch_size,
-                               **(dict(latent="extended") if isinstance(latent, str) and latent == "extended" else {}))
+                               sampling_noise=sampling_noise, batch_size=batch_size, **extended)
             return evaluate_utils.rank_metrics_device(got, topN)
         lists = recommend_fn(diffusion, model, dcsr, np.arange(n), topN[-1], mask=mask, sampling_steps=sampling_steps,
                              sampling_noise=sampling_noise, batch_size=batch_size,  # (the same batches, made inside)
-                             **(dict(latent="extended") if isinstance(latent, str) and latent == "extended" else {}),
-                             **(dict(candidates=candidates) if candidates is not None else {}))
+                             **extended, **(dict(candidates=candidates) if candidates is not None else {}))
         return evaluate_utils.computeTopNAccuracy_device(data_te, lists, topN)
     for lo in range(0, n, batch_size):
         rows = np.arange(lo, min(lo + batch_size, n))
         batch = dcsr.batch(torch.from_numpy(rows)) if sparse else dcsr.rows(torch.from_numpy(rows))
         kw = dict(index=torch.from_numpy(rows)) if getattr(diffusion, "indexIn", False) else {}
         if latent:
-            kw["latent"] = "extended" if isinstance(latent, str) and latent == "extended" else True
+            kw["latent"] = latent
         prediction = diffusion.p_sample(model, batch, sampling_steps, sampling_noise, **kw)
         indptr, cols = evaluate_utils.csr_rows_to_device(mask_his, rows, device)
         predict_items.append(masked_topk(prediction, topN[-1], indptr, cols))

@@ -15,8 +15,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, reverse_route
 from .DNN import DNN
+from .data_utils import CsrBatch
 from .engine_core import TrainLoss, prep_input, step_tables
 
 _SCHEDULE_KIND = {"linear": 0, "linear-var": 1, "cosine": 2, "binomial": 3}
@@ -50,7 +51,7 @@ class GaussianDiffusion(nn.Module):
         self.Lt_count = torch.zeros(steps, dtype=torch.int64, device=self.device)
         self.update_history = True  # data-parallel wrappers switch this off and replay the gathered batch
         self.rng = "philox"  # "philox": in-kernel noise/dropout;  "torch": torch.randn / torch.bernoulli
-        self.last_reverse_route = None  # "latent" / "item": the route the last p_sample took (_latent_reverse_ok)
+        self.last_reverse_route = None  # "latent" / "item": the route the last reverse loop took (reverse_route.plan)
         if noise_scale != 0.0:
             if noise_schedule not in _SCHEDULE_KIND:
                 raise NotImplementedError(f"unknown beta schedule: {noise_schedule}!")
@@ -64,11 +65,14 @@ class GaussianDiffusion(nn.Module):
     def calculate_for_diffusion(self):
         """All float64 schedule tables of the reference (:132-159: alphas_cumprod(_prev/_next), their roots and logs,
         posterior variance / clipped log variance / mean coefficients), built by gdmcf_schedule_build."""
-        tabs = _lib.schedule_tables(_SCHEDULE_KIND[self.noise_schedule], self.noise_scale, self.noise_min, self.noise_max,
-                                    self.steps, self.beta_fixed)
-        for name, row in zip(_lib.TABLE_NAMES, tabs):
+        for name, row in zip(_lib.TABLE_NAMES, self._host_tables()):
             setattr(self, name, torch.from_numpy(row.copy()).to(self.device))
         self._derive_tables()
+
+    def _host_tables(self):
+        """The float64 tables on the host, built anew (gdmcf_schedule_build; no device read)."""
+        return _lib.schedule_tables(_SCHEDULE_KIND[self.noise_schedule], self.noise_scale, self.noise_min, self.noise_max,
+                                    self.steps, self.beta_fixed)
 
     def get_betas(self):
         kind = _SCHEDULE_KIND.get(self.noise_schedule)
@@ -209,18 +213,7 @@ class GaussianDiffusion(nn.Module):
     def training_losses(self, model, x_start, reweight=False, index=None, *, ts=None, pt=None, noise=None,
                         drop_mask=None):
         _lib.require_gpu(x_start, "x_start")
-        if not isinstance(model, DNN):
-            raise TypeError("gdmcf_amd.GaussianDiffusion.training_losses needs a gdmcf_amd.DNN denoiser")
-        from .data_utils import CsrBatch
-        csr_batch = None
-        if isinstance(x_start, CsrBatch):
-            # rows left sparse: only what the CSR-fed kernels cover, otherwise densify here
-            sparse_ok = (self.mean_type == ModelMeanType.START_X and not model.norm and x_start.csr.values is None
-                         and self.rng == "philox")
-            if sparse_ok:
-                csr_batch = x_start
-            else:
-                x_start = x_start.dense()
+        x_start, csr_batch = self._train_rows(self._denoiser(model, "training_losses"), x_start, self.rng == "philox")
         batch_size, device = x_start.size(0), x_start.device
         assert x_start.dim() == 2 and x_start.size(1) == model.in_dims[0], "x_start must be [B, n_items]"
         spec = self._train_spec(x_start, reweight, ts, pt, noise, drop_mask)
@@ -229,6 +222,17 @@ class GaussianDiffusion(nn.Module):
         if csr_batch is not None:
             spec.update(x_start=None, csr=csr_batch)
         return self._fused_loss(model, spec, batch_size, device)
+
+    def _train_rows(self, model, x_start, noise_without_rows):
+        """(x_start, csr_batch) of a training step.  A CsrBatch stays sparse (csr_batch) only where the CSR-fed kernels
+        cover the step -- x0 target, no F.normalize, all values 1, a backbone that takes the rows (`csr_rows`: DNNCat only when built
+        with it) -- and the noise is not torch.randn_like of the dense rows (rng == "torch"); otherwise it is densified here."""
+        if not isinstance(x_start, CsrBatch):
+            return x_start, None
+        if (self.mean_type == ModelMeanType.START_X and not model.norm and x_start.csr.values is None and noise_without_rows
+                and getattr(model, "csr_rows", True)):
+            return x_start, x_start
+        return x_start.dense(), None
 
     def _train_spec(self, x_start, reweight, ts, pt, noise, drop_mask):
         """What an engine's train_forward needs of one training step: timesteps (drawn here unless given), schedule
@@ -274,97 +278,47 @@ class GaussianDiffusion(nn.Module):
         return {"loss": loss}
 
     # -- sampling --------------------------------------------------------------------------------
+    # (reverse_route.plan decides the route; the next three are its answers under the names the engines' error messages use)
     def _sparse_reverse_ok(self, model, x_start, steps):
-        """Whether a reverse loop may keep the data_utils.CsrBatch `x_start` sparse: x_T must be x_0 itself (steps == 0), binary
-        (all values 1, no F.normalize) and undropped, so that the first layers' products are sums of weight rows
-        (gdmcf_gather_fwd_f32); float32 products only; the backbones whose engines take the rows (exact types: DNNCat and the
-        GCN backbone densify).  Anything else: p_sample calls x_start.dense() and runs the dense route, to the bit."""
-        from .onehot import DNNOneHot
-        from .onehot_embedding import DNNOneHotEmbedding
-        return (steps == 0 and self.noise_scale != 0.0 and not model.norm and x_start.csr.values is None
-                and getattr(model, "gemm_dtype", "f32") == "f32" and (not model.training or model.drop.p == 0)
-                and type(model) in (DNN, DNNOneHot, DNNOneHotEmbedding))
-
-    @staticmethod
-    def _latent_backbones():
-        """Exact types whose engines carry the reverse loop in the first hidden layer's space (p_sample(latent=True))."""
-        from .onehot import DNNOneHot
-        from .onehot_embedding import DNNOneHotEmbedding
-        from .onehot_gcn import DNNOneHotEmbeddingGCN
-        return (DNN, DNNOneHot, DNNOneHotEmbedding, DNNOneHotEmbeddingGCN)
-
-    def _latent_tables_ok(self):
-        """posterior_mean_coef2[0] == 0 (alphas_cumprod_prev[0] is 1 for every schedule: the last step needs no x_1) and finite
-        posterior_mean_coef1, as float32; read back once per table set."""
-        c1, c2 = self._t32.get("c1"), self._t32.get("c2")
-        if c1 is None or c2 is None:
-            return False
-        rec = getattr(self, "_latent_tabs_rec", None)
-        if rec is None or rec[0] is not c1 or rec[1] is not c2:
-            ok = bool(c2[0].item() == 0.0) and bool(torch.isfinite(c1).all().item())
-            rec = self._latent_tabs_rec = (c1, c2, ok)
-        return rec[2]
-
-    @staticmethod
-    def _latent_backbones_extended():
-        """_latent_backbones plus DNNCat (exact type): what p_sample(latent="extended") carries in the hidden space."""
-        from .cat import DNNCat
-        return GaussianDiffusion._latent_backbones() + (DNNCat,)
-
-    def _eps_tables(self):
-        """engine_core.EpsTables of this schedule (the EPSILON target's latent loop): g_t, d_t, G, D from the host's float64
-        tables (gdmcf_schedule_build; no device read) with the four inputs rounded to float32 first, as the item-space route
-        reads them; once per table set."""
-        c1 = self._t32.get("c1")
-        rec = getattr(self, "_eps_tabs_rec", None)
-        if rec is None or rec[0] is not c1:
-            from .engine_core import EpsTables
-            tabs = _lib.schedule_tables(_SCHEDULE_KIND[self.noise_schedule], self.noise_scale, self.noise_min, self.noise_max,
-                                        self.steps, self.beta_fixed)
-            row = lambda name: tabs[_lib.TABLE_NAMES.index(name)].astype("float32")
-            et = EpsTables(row("posterior_mean_coef1"), row("posterior_mean_coef2"), row("sqrt_recip_alphas_cumprod"),
-                           row("sqrt_recipm1_alphas_cumprod"), self.steps)
-            rec = self._eps_tabs_rec = (c1, et)
-        return rec[1]
+        """Whether an item-space reverse loop keeps the data_utils.CsrBatch `x_start` sparse (reverse_route.plan)."""
+        return reverse_route.plan(self, model, x_start, steps).keep_sparse
 
     def _latent_reverse_ok(self, model, sampling_noise=False, capture=None, extended=False):
-        """Whether p_sample(latent=True) may carry the reverse loop in the first hidden layer's space: between two
-        hidden activations the loop must be linear in x_t -- x0 target, no sampling noise, no F.normalize, no dropout -- nothing may
-        ask for the per-step x_t (capture), the products are float32, the last step needs no x_1 (c2[0] == 0), and the backbone's
-        engine has the loop (exact types).  Anything else takes the item-space route, to the bit.
-        extended (p_sample(latent="extended")): the same predicate with the EPSILON target allowed -- its tables must give finite
-        g, d, G, D and D > 0 (_eps_tables) instead of c2[0] == 0 -- and DNNCat among the backbones."""
-        common = (self.noise_scale != 0.0 and not sampling_noise and capture is None
-                  and not model.norm and (not model.training or model.drop.p == 0)
-                  and getattr(model, "gemm_dtype", "f32") == "f32")
-        if not extended:
-            return (self.mean_type == ModelMeanType.START_X and common and type(model) in self._latent_backbones()
-                    and self._latent_tables_ok())
-        if not (common and type(model) in self._latent_backbones_extended() and "c1" in self._t32):
-            return False
-        if self.mean_type == ModelMeanType.START_X:
-            return self._latent_tables_ok()
-        return self.mean_type == ModelMeanType.EPSILON and self._eps_tables().ok
+        """Whether p_sample(latent=True) -- extended: latent="extended" -- runs the loop in the first hidden layer's space."""
+        return reverse_route.plan(self, model, None, None, sampling_noise, capture, "extended" if extended else "base").route == "latent"
+
+    def _eps_tables(self):
+        """engine_core.EpsTables of this schedule, once per table set (reverse_route.TableSet.eps)."""
+        return reverse_route.TableSet.of(self).eps
+
+    def _denoiser(self, model, caller="p_sample"):
+        if not isinstance(model, DNN):
+            raise TypeError(f"gdmcf_amd.GaussianDiffusion.{caller} needs a gdmcf_amd.DNN denoiser")
+        return model
+
+    def _reverse_plan(self, model, rows, steps, sampling_noise=False, capture=None, latent=False, masks=None):
+        """reverse_route.plan of one call, recorded in `last_reverse_route`."""
+        plan = reverse_route.plan(self, model, rows, steps, sampling_noise, capture, reverse_route.latent_mode(latent), masks)
+        self.last_reverse_route = plan.route
+        return plan
+
+    def _reverse_prologue(self, model, x_start, steps, sampling_noise, capture, latent):
+        """What both p_sample start with: the checks, the plan, the rows as the plan takes them (densified: the dense route's bits)."""
+        assert steps <= self.steps, "Too much steps in inference."
+        _lib.require_gpu(x_start, "x_start")
+        model = self._denoiser(model)
+        plan = self._reverse_plan(model, x_start, steps, sampling_noise, capture, latent)
+        if isinstance(x_start, CsrBatch) and not plan.keep_sparse:
+            x_start = x_start.dense()
+        return model, plan, x_start
 
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,
                  capture=None, latent=False):
-        """x_start: dense [B, n_items] rows, or a data_utils.CsrBatch -- kept sparse where _sparse_reverse_ok holds (the first
-        reverse step's first hidden layer is then a gather of the rows' weight rows), densified here otherwise.
-        latent=True: where _latent_reverse_ok holds, the loop runs in the first hidden layer's space (two item-wide products per
-        call instead of two per step; same [B, n_items] result up to float32 rounding); `last_reverse_route` says which route ran.
-        latent="extended": the same with _latent_reverse_ok(extended=True) -- the EPSILON target too (and, in the discrete class,
-        DNNCat); everything latent=True covers runs exactly as under latent=True."""
-        assert steps <= self.steps, "Too much steps in inference."
-        _lib.require_gpu(x_start, "x_start")
-        if not isinstance(model, DNN):
-            raise TypeError("gdmcf_amd.GaussianDiffusion.p_sample needs a gdmcf_amd.DNN denoiser")
-        from .data_utils import CsrBatch
-        if isinstance(x_start, CsrBatch) and not self._sparse_reverse_ok(model, x_start, steps):
-            x_start = x_start.dense()
-        extended = isinstance(latent, str) and latent == "extended"
-        latent = bool(latent) and self._latent_reverse_ok(model, sampling_noise, capture, extended=extended)
-        self.last_reverse_route = "latent" if latent else "item"
-        eps_mode = self.mean_type == ModelMeanType.EPSILON
+        """x_start: dense [B, n_items] rows, or a data_utils.CsrBatch -- kept sparse where the first reverse step's first hidden
+        layer can be a gather of the rows' weight rows, densified here otherwise.  latent=True / "extended": the loop runs in the
+        first hidden layer's space where it can (two item-wide products per call instead of two per step; same result up to float32
+        rounding); `last_reverse_route` says which ran.  What runs for which backbone, target, mode and rows: DESIGN 4.9, "Routes"."""
+        model, plan, x_start = self._reverse_prologue(model, x_start, steps, sampling_noise, capture, latent)
         if self.noise_scale == 0.0:
             x_t = x_start
             with torch.no_grad():
@@ -372,18 +326,16 @@ class GaussianDiffusion(nn.Module):
                     t = torch.full((x_t.shape[0],), i, dtype=torch.int64, device=x_t.device)
                     x_t = model(x_t, t)
             return x_t
-        if latent:
-            return self._latent_sample(model, x_start, steps, noise0=noise0)
+        if plan.route == "latent":
+            return self._latent_sample(model, x_start, steps, eps=plan.eps, noise0=noise0)
         with torch.no_grad():
-            return model.engine.p_sample_loop(x_start, steps, self.steps, self._t32, eps_mode, bool(sampling_noise),
-                                              noise0=noise0, step_noise=step_noise, capture=capture,
+            return model.engine.p_sample_loop(x_start, steps, self.steps, self._t32, self.mean_type == ModelMeanType.EPSILON,
+                                              bool(sampling_noise), noise0=noise0, step_noise=step_noise, capture=capture,
                                               draw_noise=lambda like: self._draw_noise(like, stream_id=7))
 
-    def _latent_sample(self, model, x, steps, index=None, stop=False, noise0=None, sampled0=None):
-        """The latent route of p_sample on `x` (dense rows, or a CsrBatch the route keeps sparse; the caller has checked
-        _latent_reverse_ok).  stop (gdmcf_amd.recommend): the loop ends before its last product and returns that product's
-        engine_core.LatentProduct.  (index, sampled0: the one-hot variant's.)"""
-        eps = self._eps_tables() if self.mean_type == ModelMeanType.EPSILON else None
+    def _latent_sample(self, model, x, steps, index=None, stop=False, eps=None, noise0=None, sampled0=None):
+        """The latent route on `x` (dense rows, or a CsrBatch the plan keeps sparse); eps: the plan's.  stop (gdmcf_amd.recommend):
+        the loop ends before its last product and returns its engine_core.LatentProduct.  (index, sampled0: the one-hot variant's.)"""
         with torch.no_grad():
             return model.engine.p_sample_loop(x, steps, self.steps, self._t32, eps is not None, False, noise0=noise0, latent=True,
                                               stop=stop, eps=eps)
@@ -456,24 +408,17 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
                             "(DNNOneHotEmbedding with indexIn = True)")
         return model
 
+    def _denoiser(self, model, caller="p_sample"):
+        return self._onehot_model(model) if self.CatOneHot else super()._denoiser(model, caller)
+
     def training_losses(self, model, x_start, reweight=False, index=None, *, ts=None, pt=None, noise=None,
                         drop_mask=None, ts_U=None, sampled=None, drop_mask_U=None):
         if not self.CatOneHot:
             return super().training_losses(model, x_start, reweight, index, ts=ts, pt=pt, noise=noise, drop_mask=drop_mask)
         _lib.require_gpu(x_start, "x_start")
         model = self._onehot_model(model)
-        from .data_utils import CsrBatch
-        csr_batch = None
-        if isinstance(x_start, CsrBatch):
-            # rows left sparse: only what the CSR-fed kernels cover, otherwise densify here.  (rng == "torch"
-            # draws the noise with torch.randn_like of the dense rows, unless the noise is given or there is none.)
-            sparse_ok = (self.mean_type == ModelMeanType.START_X and not model.norm and x_start.csr.values is None
-                         and (self.rng == "philox" or noise is not None or self.noise_scale == 0.0)
-                         and getattr(model, "csr_rows", True))  # (DNNCat: CSR-fed only when built with csr_rows=True)
-            if sparse_ok:
-                csr_batch = x_start
-            else:
-                x_start = x_start.dense()
+        # (torch-drawn noise needs the dense rows unless it is given or there is none)
+        x_start, csr_batch = self._train_rows(model, x_start, self.rng == "philox" or noise is not None or self.noise_scale == 0.0)
         batch_size, device = x_start.size(0), x_start.device
         assert x_start.dim() == 2 and x_start.size(1) == model.in_dims[0], "x_start must be [B, n_items]"
         if sampled is None and ts_U is None:
@@ -487,9 +432,8 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
 
     def p_sample(self, model, x_start, steps, sampling_noise=False, index=None, *, noise0=None, step_noise=None,
                  capture=None, sampled0=None, graph_sampled=None, graph_pick=None, latent=False):
-        """latent: as GaussianDiffusion.p_sample -- where _latent_reverse_ok holds the loop runs in the engine (_latent_sample:
-        OneHotEngine.latent_loop / CatEngine.latent_loop); both routes start from _reverse_inputs, and with `indexIn` the per-step
-        graph update runs exactly as on the item-space route (same draws, same `last_graph`).
+        """x_start, latent: as GaussianDiffusion.p_sample (routes: DESIGN 4.9); the latent loop is the engine's latent_loop.  Both
+        routes start from _reverse_inputs; with `indexIn` the per-step graph update runs on both (same draws, same `last_graph`).
         Reverse loop of the one-hot variant (reference :668-768).  With `indexIn` (the embedding backbones) every reverse
         step also advances the degree-guided graph of :706-729 on the device (gdmcf_graph_guided_step_u8: classes drawn
         from the accumulated graph's transition rows, one bit per user drawn from its relative degree, AND-ed when
@@ -499,21 +443,10 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         if not self.CatOneHot:
             return super().p_sample(model, x_start, steps, sampling_noise, index, noise0=noise0, step_noise=step_noise,
                                     capture=capture, latent=latent)
-        assert steps <= self.steps, "Too much steps in inference."
-        _lib.require_gpu(x_start, "x_start")
-        model = self._onehot_model(model)
-        extended = isinstance(latent, str) and latent == "extended"
-        latent = bool(latent) and self._latent_reverse_ok(model, sampling_noise, capture, extended=extended)
-        self.last_reverse_route = "latent" if latent else "item"
-        from .cat import DNNCat
-        from .data_utils import CsrBatch
-        # (DNNCat keeps CSR rows on the latent route only: its item-space loop takes dense rows)
-        if isinstance(x_start, CsrBatch) and not (self._sparse_reverse_ok(model, x_start, steps) or (
-                latent and type(model) is DNNCat and steps == 0 and x_start.csr.values is None)):
-            x_start = x_start.dense()
-        if latent:
-            return self._latent_sample(model, x_start, steps, index, noise0=noise0, sampled0=sampled0, graph_sampled=graph_sampled,
-                                       graph_pick=graph_pick)
+        model, plan, x_start = self._reverse_prologue(model, x_start, steps, sampling_noise, capture, latent)
+        if plan.route == "latent":
+            return self._latent_sample(model, x_start, steps, index, eps=plan.eps, noise0=noise0, sampled0=sampled0,
+                                       graph_sampled=graph_sampled, graph_pick=graph_pick)
         B, dev = x_start.shape[0], x_start.device
         with torch.no_grad():
             x_t, x_tU, keep, graph, degp, _ = self._reverse_inputs(model, x_start, steps, noise0, sampled0)
@@ -590,13 +523,11 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
         graph, degp (with `indexIn`, else None): the zeroed degree-guided graph and the users' relative degrees (:710-711; a batch
         without any interaction gives nan, as there) -- row lengths on CSR rows, row sums on dense ones, exact in float32 either
         way.  before_step(n, i): the graph update ahead of step n (timestep i) as the latent loop calls it."""
-        from .cat import DNNCat
-        from .data_utils import CsrBatch
         eng = model.engine
         B, dev = x.shape[0], x.device
         if isinstance(x, CsrBatch):
             x0, x_t, keep = None, x, None
-            x_tU = None if type(model) is DNNCat else eng.onehot_rows_sparse(x)
+            x_tU = eng.onehot_rows_sparse(x) if reverse_route.carries(model).second_handle else None
         else:
             x0 = x.float().contiguous()
             if steps == 0:
@@ -623,15 +554,14 @@ class GaussianDiffusionDiscrete(GaussianDiffusion):
 
         return x_t, x_tU, keep, graph, degp, before_step
 
-    def _latent_sample(self, model, x, steps, index=None, stop=False, **draws):
+    def _latent_sample(self, model, x, steps, index=None, stop=False, eps=None, **draws):
         """GaussianDiffusion._latent_sample for the one-hot variant: the engine's latent_loop on _reverse_inputs(**draws: noise0,
         sampled0, graph_sampled, graph_pick), `last_graph` kept."""
         if not self.CatOneHot:
-            return super()._latent_sample(model, x, steps, index, stop, **draws)
+            return super()._latent_sample(model, x, steps, index, stop, eps, **draws)
         model = self._onehot_model(model)
         with torch.no_grad():
             x_t, x_tU, keep, graph, _, before_step = self._reverse_inputs(model, x, steps, **draws)
-            eps = self._eps_tables() if self.mean_type == ModelMeanType.EPSILON else None
             res = model.engine.latent_loop(x_t, x_tU, self.steps, self._t32, index=index if self.indexIn else None,
                                            before_step=before_step, stop=stop, eps=eps)
             del keep

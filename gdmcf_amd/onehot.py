@@ -31,6 +31,7 @@ import torch.nn as nn
 from . import _lib
 from . import engine_core as core
 from .engine_core import EngineBase, _Bufs, _ceil64, with_precision
+from .reverse_route import Carries
 
 
 class SparseXU:
@@ -535,6 +536,7 @@ class OneHotEngine(EngineBase):
 class DNNOneHot(nn.Module):
     """Drop-in for the reference DNNOneHot (models/DNN.py:360-477).  As there, `out_dims[0]` of the CALLER's list grows
     by the width of the second branch (the reference aliases and mutates it, :384-385)."""
+    reverse_carries = Carries("base", True)
 
     def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, gemm_dtype="f32"):
         super().__init__()

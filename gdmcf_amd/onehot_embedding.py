@@ -24,6 +24,7 @@ from . import _lib
 from . import engine_core as core
 from .engine_core import _ceil64, with_precision
 from .onehot import DNNOneHot, OneHotEngine
+from .reverse_route import Carries
 
 
 def nt_xent_loss(z1, z2, temperature=0.1, eps=1e-5):
@@ -279,6 +280,7 @@ class OneHotEmbeddingEngine(OneHotEngine):
 class DNNOneHotEmbedding(DNNOneHot):
     """Drop-in for the reference DNNOneHotEmbedding (models/DNN.py:510-682); main.py:239-242 builds it with
     `item_num=n_item, user_num=n_user` and sets `diffusion.indexIn = True`."""
+    reverse_carries = Carries("base", True)
 
     def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, item_num=2810, user_num=5949,
                  gemm_dtype="f32", ntxent="torch"):

@@ -23,6 +23,7 @@ from . import _lib
 from . import engine_core as core
 from .engine_core import _ceil64
 from .onehot_embedding import DNNOneHotEmbedding, OneHotEmbeddingEngine
+from .reverse_route import Carries
 
 
 class OneHotGCNEngine(OneHotEmbeddingEngine):
@@ -138,6 +139,7 @@ class _LayerGCNParams(nn.Module):
 class DNNOneHotEmbeddingGCN(DNNOneHotEmbedding):
     """Drop-in for the reference DNNOneHotEmbeddingGCN (main.py:243-246), args.noise_type == 0; `args.gcnLayerNum` (0, 1,
     2; parse_args_util.py:24 defaults to 2) may also be given as `gcn_layers=`."""
+    reverse_carries = Carries("base", False)  # (its item-space loop takes dense rows)
 
     def __init__(self, in_dims, out_dims, emb_size, time_type="cat", norm=False, dropout=0.5, item_num=2810, user_num=5949,
                  args=None, gcn_layers=None, gemm_dtype="f32", ntxent="torch"):

@@ -10,54 +10,21 @@ read (gdmcf_cand_scores_f32); otherwise the named scores are picked out of the [
 instead of a list (gdmcf_rank_targets_f32) -- the evaluation side: every metric that is a function of where the held-out items sit."""
 import types
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, reverse_route
 from . import engine_core as core
 from .data_utils import DeviceCSR
 
 
-def _c1_0_positive(diffusion):
-    """posterior_mean_coef1[0] > 0 as float32, from the host's float64 table (gdmcf_schedule_build; no device read); once per
-    table set."""
-    c1 = diffusion._t32.get("c1")
-    rec = getattr(diffusion, "_recommend_c1_rec", None)
-    if rec is None or rec[0] is not c1:
-        from .gaussian_diffusion import _SCHEDULE_KIND
-        tabs = _lib.schedule_tables(_SCHEDULE_KIND[diffusion.noise_schedule], diffusion.noise_scale, diffusion.noise_min,
-                                    diffusion.noise_max, diffusion.steps, diffusion.beta_fixed)
-        c1_0 = np.float32(tabs[_lib.TABLE_NAMES.index("posterior_mean_coef1")][0])
-        rec = diffusion._recommend_c1_rec = (c1, bool(np.isfinite(c1_0) and c1_0 > 0))
-    return rec[1]
-
-
 def route_of(diffusion, model, rows, sampling_steps=0, sampling_noise=False, extended=False, masks=None):
-    """Which route `recommend` takes for this call:
-      "latent-csr"  GaussianDiffusion._latent_reverse_ok holds (x0 target, no sampling noise, no F.normalize, no active dropout,
-                    float32 products, DNN / DNNOneHot / DNNOneHotEmbedding / DNNOneHotEmbeddingGCN), sampling_steps == 0 and every
-                    value of `rows` is 1: gathered first layers, latent steps, one item-wide product, top-k on the raw scores
-      "latent"      _latent_reverse_ok holds but x_T is not the binary rows (sampling_steps > 0, values other than 1): the same,
-                    from dense rows
-      "item"        everything else: p_sample as driver.evaluate calls it, then the top-k.
-    extended (recommend(latent="extended")): _latent_reverse_ok(extended=True) decides, so DNNCat takes the same two routes, and
-    so does the EPSILON target with one more condition on "latent-csr": x_0 = G x_T - D (second Q^ + b_out) is ranked without
-    its first term, which is only right where G x_T touches masked items alone -- `rows` itself must be among `masks` (the
-    tuple of DeviceCSRs the call masks with); otherwise "latent" (dense rows, x_0 from the posterior epilogue)."""
-    if not extended:
-        if not (diffusion._latent_reverse_ok(model, sampling_noise, None) and _c1_0_positive(diffusion)):
-            return "item"
-        return "latent-csr" if (sampling_steps == 0 and rows.values is None) else "latent"
-    if not diffusion._latent_reverse_ok(model, sampling_noise, None, extended=True):
-        return "item"
-    from .gaussian_diffusion import ModelMeanType
-    eps = diffusion.mean_type == ModelMeanType.EPSILON
-    if not eps and not _c1_0_positive(diffusion):
-        return "item"
-    binary = sampling_steps == 0 and rows.values is None
-    if eps:
-        return "latent-csr" if binary and masks is not None and any(m is rows for m in masks) else "latent"
-    return "latent-csr" if binary else "latent"
+    """Which route `recommend` takes for this call (reverse_route.plan decides; DESIGN 4.9, "Routes"; extended: latent="extended"):
+      "latent-csr"  the latent loop from the binary rows themselves: gathered first layers, one item-wide product, raw scores ranked
+      "latent"      the latent loop from dense rows (sampling_steps > 0, values other than 1, or the EPSILON target without `rows`
+                    among `masks`, the tuple of DeviceCSRs the call masks with)
+      "item"        everything else: p_sample as driver.evaluate calls it, then the top-k."""
+    return reverse_route.plan(diffusion, model, rows, sampling_steps, sampling_noise, None, "extended" if extended else "base",
+                              masks or ()).recommend
 
 
 def _as_mask(mask, rows):
@@ -124,18 +91,15 @@ def _setup(diffusion, model, rows, user_ids, mask, sampling_steps, sampling_nois
         if not (0 <= int(lo) and int(hi) < n_ok):
             raise IndexError("recommend: user_ids out of range")
     ids = ids.to(dev).contiguous()
-    if not (latent is True or (isinstance(latent, str) and latent == "extended")):
+    if latent is not True and reverse_route.latent_mode(latent) in (None, "base"):
         raise ValueError('recommend: latent is True or "extended"')
-    route = route_of(diffusion, model, rows, sampling_steps, sampling_noise, extended=latent is not True, masks=masks)
-    diffusion.last_recommend_route = route
-    from .gaussian_diffusion import ModelMeanType
-    # the EPSILON target's x_0 = G x_T + D (second (-Q^) + (-b_out)): where G x_T lies on masked items only ("latent-csr") the bracket
-    # is ranked like the x0 target's last product; on "latent" x_0 itself comes from the posterior epilogue on dense rows
-    stop = route == "latent-csr" or diffusion.mean_type != ModelMeanType.EPSILON
+    # (has_product -- the EPSILON target's "latent" route has none: x_0 itself comes from the posterior epilogue on dense rows)
+    plan = diffusion._reverse_plan(model, rows, sampling_steps, sampling_noise, None, latent, masks)  # (sets last_reverse_route)
+    diffusion.last_recommend_route = plan.recommend
     ip1, ix1 = (masks[0].indptr, masks[0].indices) if masks else (None, None)
     ip2, ix2 = (masks[1].indptr, masks[1].indices) if len(masks) > 1 else (None, None)
-    return types.SimpleNamespace(dev=dev, I=I, ids=ids, n=ids.numel(), batch_size=batch_size, route=route, stop=stop, masks=masks,
-                                 has_product=route != "item" and stop, sampling_steps=sampling_steps,
+    return types.SimpleNamespace(dev=dev, I=I, ids=ids, n=ids.numel(), batch_size=batch_size, route=plan.recommend, plan=plan,
+                                 masks=masks, has_product=plan.ends_at_product, sampling_steps=sampling_steps,
                                  sampling_noise=sampling_noise, mask_ptrs=tuple(_lib.ptr(t) for t in (ip1, ix1, ip2, ix2)))
 
 
@@ -153,9 +117,8 @@ def _reverse_chunks(diffusion, model, rows, c, noise0=None, sampled0=None):
             yield lo, chunk, B, None, core._f32_rows(diffusion.p_sample(model, rows.rows(chunk), c.sampling_steps, c.sampling_noise, **kw))
             continue
         x = rows.batch(chunk) if c.route == "latent-csr" else rows.rows(chunk)
-        res = diffusion._latent_sample(model, x, c.sampling_steps, index, stop=c.stop, **inj)  # (as p_sample(latent=...) runs it)
-        diffusion.last_reverse_route = "latent"
-        yield (lo, chunk, B, res, None) if c.stop else (lo, chunk, B, None, res)
+        res = diffusion._latent_sample(model, x, c.sampling_steps, index, c.has_product, c.plan.eps, **inj)
+        yield (lo, chunk, B, res, None) if c.has_product else (lo, chunk, B, None, res)
 
 
 def _all_scores(eng, B, dev, product, scores):
@@ -232,9 +195,8 @@ def recommend(diffusion, model, rows, user_ids, k, *, mask="rows", sampling_step
     live on the device cost the call's one synchronising copy there.
     noise0 [n, I] / sampled0 [n, I] inject the draws of x_T with sampling_steps > 0, row for row of user_ids, as p_sample's
     keywords of the same names do (parity runs).
-    latent: True -- the routes above; "extended" -- route_of(extended=True): DNNCat on both latent routes, and the EPSILON
-    target: on "latent-csr" (only with `rows` itself among the masks) second (-Q^) + (-b_out) is ranked and the k values scaled by
-    D; on "latent" x_0 comes from the posterior epilogue on dense rows and is ranked as it is.
+    latent: True or "extended" (DNNCat and the EPSILON target on the latent routes too: DESIGN 4.9, "Routes").  With the EPSILON
+    target "latent-csr" ranks second (-Q^) + (-b_out) and scales the k values by D; "latent" ranks the posterior epilogue's x_0.
     candidates (score_candidates' lists, [n, C] or a shared [C]; candidate_route as there): only these items are ranked, 1 <= k
     <= C.  The ids returned are the candidates' item ids; equal scores come back in ascending POSITION in the list (the top-k
     runs over list positions, which one torch.gather translates); return_values returns the scores; masked or out-of-range
