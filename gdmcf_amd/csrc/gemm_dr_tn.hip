@@ -998,3 +998,28 @@ int gd_dr_tn_launch(GdGemm& g, hipStream_t s) {
     if (bias_db) g.out2 = nullptr;  // taken: the caller skips its column-sum pass
     return gd_launch_status("gemm_dr");
 }
+
+// gdmcf_debug_dr_tn_plan (include/gdmcf_hip.h): dr_tn_prepare on a scratch product, nothing launched.  Shapes as the weight-
+// gradient entries name them (batch M, dW[N, K]); the product is built as linear.hip builds it in float32 mode.
+extern "C" int gdmcf_debug_dr_tn_plan(int M, int N, int K, int64_t lddz, int64_t lda, int64_t ldw, int bias_col, int fused,
+                                      int* depth, int* ksp, int* tiles_m, int* tiles_n, int* m_fastest, int* has_bias) {
+    static float db_scratch;  // (never written: only its address travels, as the bias gradient's would)
+    GdGemm g = {};
+    DrArgs d = {};
+    float* bias_db = nullptr;
+    int dep = 0;
+    bool ok = M > 0 && N > 0 && K > 0 && lddz >= N && lda >= K && ldw >= K && (fused ? dr_fused_on() : dr_routes().dw);
+    if (ok) {
+        g.lda = lddz; g.ldb = lda; g.ldc = ldw; g.M = N; g.N = K; g.K = M; g.splits = 1;
+        g.out2 = (bias_col && lda > K) ? &db_scratch : nullptr;  // (linear.hip: bias_col_request)
+        ok = dr_tn_prepare(fused ? GD_EPI_ADAMW : GD_EPI_STORE, g, d, &bias_db, &dep);
+        if (ok && fused) ok = (long)d.tiles_m * d.tiles_n < (1L << DR_VT_SHIFT);
+    }
+    if (depth) *depth = ok ? dep : 0;
+    if (ksp) *ksp = ok ? d.ksp : 0;
+    if (tiles_m) *tiles_m = ok ? d.tiles_m : 0;
+    if (tiles_n) *tiles_n = ok ? d.tiles_n : 0;
+    if (m_fastest) *m_fastest = ok ? d.m_fastest : 0;
+    if (has_bias) *has_bias = ok && bias_db != nullptr;
+    return ok ? 1 : 0;
+}

@@ -57,6 +57,16 @@ int gdmcf_debug_last_gemm(void);
  * 16 k per split *cps, or 0 (all three 0) when the route does not take the shape.  The call itself may still decline: a workspace
  * that is not 16-byte aligned or smaller than gdmcf_linear_ws_bytes.  Tests pick their shapes with it. */
 int gdmcf_debug_fat_slab_plan(int M, int N, int K, int* nb, int* splits, int* cps);
+/* What the register-streaming weight-gradient kernels (families 2 and 3) plan for dW[N, K] = dZ[M, N]^T A[M, K] in float32 mode,
+ * host only, nothing launched.  bias_col != 0: the call asks for db as column K of the product (a_scale_col != 0 with db given; it
+ * needs lda > K); fused != 0: the plan of gdmcf_linear_bwd_weight_adamw_f32, else of gdmcf_linear_bwd_weight_f32.  Returns 1 and the
+ * ring depth *depth (7, 8 or 9), the k-steps of 4 batch rows a tile runs *ksp (a multiple of depth + 1; ksp - ceil(M / 4) of
+ * them are padded steps that read past the operands), the 64 x 64 tiles along N and along K (the bias column counted) *tiles_m and
+ * *tiles_n, the ticket order *m_fastest and whether the product carries the bias column *has_bias -- or 0 (all six 0) when the
+ * kernels do not take the shape or their route is switched off.  A fused product updates W inside the k loop of the next tile when
+ * ksp / (depth + 1) >= 9, else at the end of its own tile. */
+int gdmcf_debug_dr_tn_plan(int M, int N, int K, int64_t lddz, int64_t lda, int64_t ldw, int bias_col, int fused, int* depth,
+                           int* ksp, int* tiles_m, int* tiles_n, int* m_fastest, int* has_bias);
 
 /* Optional in-library timing with HIP events on the launch stream (bench.py's live roofline
  * measurement).  While enabled, every tagged kernel launch is bracketed by two hipEventRecord

@@ -103,6 +103,7 @@ PINS = {
                                       c_int, c_int64, c_float, c_double, P]),
     "gdmcf_adam_hyper_fill": (c_int, [P, c_int, c_float, c_float, c_float, c_float, c_float, c_int64, c_float]),
     "gdmcf_linear_bwd_weight_adamw_multi_f32": (c_int, [P, c_int, P]),
+    "gdmcf_debug_dr_tn_plan": (c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int, P, P, P, P, P, P]),
 }
 
 
