@@ -1,5 +1,5 @@
 """ctypes binding of libgdmcf_hip.so, derived from the C ABI's own text: include/gdmcf_hip.h is parsed once at import, and
-every signature, GdDwAdamw's fields and the GDMCF_* constants follow from it.  A new entry point is declared in the header and
+every signature, the fields of GdDwAdamw and GdKnTail and the GDMCF_* constants follow from it.  A new entry point is declared in the header and
 defined in a .hip file; nothing is restated here.  The header is plain C99 in one style (`<type> <name>` parameters, /* */
 comments), which is all the parser reads.  Type map, for parameters, return types and struct members (`const` is dropped):
     int -> c_int    int64_t -> c_int64    uint64_t -> c_uint64    size_t -> c_size_t    float -> c_float    double -> c_double
@@ -112,6 +112,12 @@ class GdDwAdamw(ctypes.Structure):
     """One entry of gdmcf_linear_bwd_weight_adamw_multi_f32's list (include/gdmcf_hip.h): the arguments of one
     gdmcf_linear_bwd_weight_adamw_f32 call."""
     _fields_ = parse_structs(_HEADER)["GdDwAdamw"]
+
+
+class GdKnTail(ctypes.Structure):
+    """The tail job of gdmcf_linear_bwd_input_tail_f32 (include/gdmcf_hip.h): the arguments of the row-partial reducer, of
+    gdmcf_row_loss_finish_mean_f64 and of gdmcf_rowscale_f32."""
+    _fields_ = parse_structs(_HEADER)["GdKnTail"]
 
 
 _lib = None

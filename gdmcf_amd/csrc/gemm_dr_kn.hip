@@ -1,6 +1,9 @@
 // dr_kn_kernel of gemm_dr.h -- the input gradient and the cached-W^T forward as split-K slabs, both operands straight into
 // registers -- with its split count gd_dr_kn_splits and its entry point gd_dr_kn_launch.
+#include <stdlib.h>
+
 #include "gemm_dr.h"
+#include "tail_job.h"
 
 namespace {
 
@@ -16,24 +19,34 @@ namespace {
 // 5 + 4 NL loads (0.08 other instructions per MFMA; the LDS-tiled kernel that served this product: 0.35 and a barrier per 80,
 // MFMA pipe busy 0.72).  Tasks (split, tile) are dealt statically, the tiles of one split to one XCD (they share its rows of B).
 // The slabs go to the same reducer as before (gd_splitk_reduce: row scale, tanh').  Deterministic: static assignment, fixed k order.
+// The passenger: a launch deals ntasks <= 4 gridDim.x tasks, and a workgroup whose four slots all lie past them exits at
+// once -- its CU stands empty for the whole product.  With a tail job (job.on), the FIRST such workgroup in slot order runs the job
+// (tail_job.h: row-partial reducer, float64 loss tail, row scale -- nothing the product reads) and exits; it hands over to nobody
+// inside the launch, every other workgroup runs what it ran before.  The launch's dynamic LDS is the job's (none without one).
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef GD_KN_EVERY
 #define GD_KN_EVERY 4
 #endif
 template <int NL>
-__global__ __launch_bounds__(256, 1) void dr_kn_kernel(const DrArgs d) {
+__global__ __launch_bounds__(256, 1) void dr_kn_kernel(const DrArgs d, const GdTailJob job) {
     constexpr int TMB = 5;
     const GdGemm& g = d.g;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, q = lane >> 4;
     const int nblk = gridDim.x, per = nblk >> 3;
-    const int wl = ((nblk & 7) == 0 ? ((int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3)) : (int)blockIdx.x) * 4 + wave;
+    const int slot = (nblk & 7) == 0 ? ((int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3)) : (int)blockIdx.x;
+    const int wl = slot * 4 + wave;
     const int n_waves = nblk * 4;
     const int ntiles = d.tiles_m * d.tiles_n;
     const int CPS = d.ksp;                      // chunks of 16 k per split (even)
     const int total_chunks = (g.K + 15) >> 4;
     const int ntasks = ntiles * g.splits;
+    if (job.on && slot == (ntasks + 3) >> 2) {  // the first workgroup without a task: the passenger's
+        extern __shared__ __attribute__((aligned(16))) unsigned char kn_lds[];
+        gd_tail_job_run(job, kn_lds);
+        return;
+    }
     const __amdgpu_buffer_rsrc_t srdA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0, (int)(((int64_t)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
     // (rows k >= K of B lie outside the descriptor and read as 0)
     const __amdgpu_buffer_rsrc_t srdB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0, (int)(((int64_t)(g.K - 1) * g.ldb + g.N) * 4), 0x00020000);
@@ -155,9 +168,17 @@ int gd_dr_kn_splits(int M, int N, int K) {
     return splits;
 }
 
+// Whether a launch of dr_kn_kernel on n_cu workgroups over `ntasks` (split, tile) tasks leaves a workgroup without any: workgroup slot
+// s owns tasks 4 s .. 4 s + 3 of the first round, so the first idle one is slot ceil(ntasks / 4).
+static bool kn_idle_workgroup(int ntasks, int n_cu) { return gd_cdiv(ntasks, 4) < n_cu; }
+
+#ifndef GD_KN_TAIL_DEFAULT
+#define GD_KN_TAIL_DEFAULT 1  // GDMCF_KN_TAIL when the environment does not set it
+#endif
+
 // The input gradient as split-K slabs on dr_kn_kernel (sets g.splits / kchunk / tiles_* for the reducer), or GD_DR_NOT_TAKEN with g
-// as it was.
-int gd_dr_kn_launch(GdGemm& g, hipStream_t s) {
+// as it was.  job (may be NULL): a tail job that must ride the launch -- declined with GD_DR_NOT_TAKEN where it cannot.
+static int kn_launch(GdGemm& g, const GdTailJob* job, hipStream_t s) {
     if (!dr_routes().kn) return GD_DR_NOT_TAKEN;
     const int splits = gd_dr_kn_splits(g.M, g.N, g.K);
     const size_t need = (size_t)splits * g.M * g.ldc * sizeof(float);
@@ -169,18 +190,41 @@ int gd_dr_kn_launch(GdGemm& g, hipStream_t s) {
     const int n_cu = dr_cu_count();
     const int total_chunks = gd_cdiv(g.K, 16);
     const int cps = (gd_cdiv(total_chunks, splits) + 1) & ~1;  // chunks per split, even (the loop runs them in pairs)
+    const int real_splits = gd_cdiv(total_chunks, cps);
     d.tiles_m = gd_cdiv(g.M, 80);
     d.tiles_n = gd_cdiv(g.N, 128);
     d.ksp = cps;
-    g.splits = gd_cdiv(total_chunks, cps);
+    GdTailJob none = {};
+    size_t lds = 0;
+    if (job) {
+        const char* env = getenv("GDMCF_KN_TAIL");  // (read at every call: one process can time and test both)
+        const bool tail_on = env ? atoi(env) != 0 : GD_KN_TAIL_DEFAULT != 0;
+        lds = lt_lds_bytes(job->T, job->H, job->B);
+        if (!tail_on || !job->on || !kn_idle_workgroup(d.tiles_m * d.tiles_n * real_splits, n_cu) || lds > GD_LT_LDS_MAX)
+            return GD_DR_NOT_TAKEN;
+        static bool attr_set = false;
+        if (!gd_allow_big_lds(dr_kn_kernel<2>, lds, &attr_set, "gemm_dr_kn")) return GDMCF_E_HIP;
+    }
+    g.splits = real_splits;
     g.kchunk = cps * 16;
     g.tiles_m = d.tiles_m;
     g.tiles_n = d.tiles_n;
     d.g = g;
     {
         GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
-        hipLaunchKernelGGL((dr_kn_kernel<2>), dim3(n_cu), dim3(256), 0, s, d);
+        hipLaunchKernelGGL((dr_kn_kernel<2>), dim3(n_cu), dim3(256), lds, s, d, job ? *job : none);
     }
     t_gd_last_gemm = 5;
     return gd_launch_status("gemm_dr_kn");
+}
+
+int gd_dr_kn_launch(GdGemm& g, hipStream_t s) { return kn_launch(g, nullptr, s); }
+int gd_dr_kn_launch_tail(GdGemm& g, const GdTailJob& job, hipStream_t s) { return kn_launch(g, &job, s); }
+
+int gdmcf_debug_kn_tail_rides(int M, int N, int K) {
+    const int splits = gd_dr_kn_splits(M, N, K);
+    if (splits <= 0) return 0;
+    const int total_chunks = gd_cdiv(K, 16);
+    const int cps = (gd_cdiv(total_chunks, splits) + 1) & ~1;
+    return kn_idle_workgroup(gd_cdiv(M, 80) * gd_cdiv(N, 128) * gd_cdiv(total_chunks, cps), dr_cu_count()) ? 1 : 0;
 }

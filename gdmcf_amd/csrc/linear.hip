@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "tail_job.h"
 
 int gd_splitk_reduce(const float* slabs, int64_t slab_stride, int splits, int64_t ld_slab, int M, int N, int mode,
                      const float* bias, const float* rowscale, const float* aact, int64_t ldact, int act, float* out,
@@ -18,6 +19,8 @@ static const int TARGET_WGS = getenv("GDMCF_TARGET_WGS") ? atoi(getenv("GDMCF_TA
 
 // input precision of the dense products issued by the calling thread (gdmcf_gemm_precision)
 thread_local int t_gemm_prec = GDMCF_GEMM_F32;
+// partial row sums per row of the calling thread's last fused-loss product (gdmcf_loss_parts_last)
+thread_local int t_loss_parts = 0;
 
 // tile class of an [M,N] output.  bf16 products are bound by L2 reads of the f32 sources, so batch-sized M takes
 // the 208x256 class when that wastes little: <= 10 % row padding and, for products that cannot split K
@@ -256,6 +259,8 @@ int gdmcf_linear_loss_fwd_f32(const float* A, int64_t lda, const float* W, int64
     attach_shadows(g, GD_LAY_KC, GD_LAY_KC);
     int rc = gd_gemm_launch(GD_LAY_KC, GD_LAY_KC, GD_EPI_LOSS, cls, g, s);
     if (rc) return rc;
+    t_loss_parts = g.tiles_n;
+    if (rowsum == nullptr) return GDMCF_OK;  // the caller reduces (gdmcf_linear_bwd_input_tail_f32)
     return gd_rowpart_reduce(rowpart, g.ld_rowpart, M, g.tiles_n, rowsum, s);
 }
 
@@ -279,6 +284,8 @@ int gdmcf_linear_loss_fwd_bits_f32(const float* A, int64_t lda, const float* W, 
     attach_shadows(g, GD_LAY_KC, GD_LAY_KC);
     int rc = gd_gemm_launch(GD_LAY_KC, GD_LAY_KC, GD_EPI_LOSS, cls, g, s);
     if (rc) return rc;
+    t_loss_parts = g.tiles_n;
+    if (rowsum == nullptr) return GDMCF_OK;  // the caller reduces (gdmcf_linear_bwd_input_tail_f32)
     return gd_rowpart_reduce(rowpart, g.ld_rowpart, M, g.tiles_n, rowsum, s);
 }
 
@@ -331,6 +338,65 @@ int gdmcf_linear_bwd_input_f32(const float* dZ, int64_t lddz, const float* W, in
     const int real_splits = gd_cdiv(N, g.kchunk);
     return gd_splitk_reduce((const float*)ws, g.slab_stride, real_splits, lds_, M, K, 1, nullptr, rowscale, Aact,
                             ldact, act, dA, ldda, s);
+}
+
+int gdmcf_loss_parts_last(void) { return t_loss_parts; }
+
+int gdmcf_kn_tail_run(const GdKnTail* tail, int M, void* stream) {
+    GD_CHECK_ARG(tail != nullptr, "kn_tail_run: tail missing");
+    const GdKnTail& t = *tail;
+    GD_CHECK_SHAPE(M > 0 && t.nt > 0 && t.ld_rowpart >= t.nt, "kn_tail_run: bad shape");
+    GD_CHECK_ARG(t.rowpart && t.rowsum, "kn_tail_run: null pointer");
+    int rc = gd_rowpart_reduce(t.rowpart, t.ld_rowpart, M, t.nt, t.rowsum, (hipStream_t)stream);
+    if (rc) return rc;
+    rc = gdmcf_row_loss_finish_mean_f64(t.rowsum, t.rowdiv, t.alpha, t.ts, t.weight_t, t.pt, M, t.T, t.H, t.Lt_history, t.Lt_count,
+                                        t.update_history, t.loss_unscaled, t.loss, t.gradcoef, t.loss_mean, t.rowscale_mean, stream);
+    if (rc) return rc;
+    return gdmcf_rowscale_f32(t.A, t.lda, t.rowscale, M, t.Ka, t.out, t.ldo, stream);
+}
+
+int gdmcf_linear_bwd_input_tail_f32(const float* dZ, int64_t lddz, const float* W, int64_t ldw, const float* rowscale,
+                                    const float* Aact, int64_t ldact, int act, int M, int N, int K, float* dA, int64_t ldda,
+                                    void* ws, size_t ws_bytes, const GdKnTail* tail, void* stream) {
+    GD_CHECK_SHAPE(M > 0 && N > 0 && K > 0 && lddz >= N && ldw >= K && ldda >= K, "linear_bwd_input_tail: bad shape");
+    GD_CHECK_ARG(act == 0 || (act == 1 && Aact && ldact >= K), "linear_bwd_input_tail: activation output missing");
+    GD_CHECK_ARG(tail != nullptr, "linear_bwd_input_tail: tail missing");
+    const GdKnTail& t = *tail;
+    // (the three launches' own checks, ahead of anything launched)
+    GD_CHECK_SHAPE(t.nt > 0 && t.ld_rowpart >= t.nt && t.T > 0 && t.H > 0 && t.Ka > 0 && t.lda >= t.Ka && t.ldo >= t.Ka,
+                   "linear_bwd_input_tail: bad tail shape");
+    GD_CHECK_ARG(t.rowpart && t.rowsum && t.rowdiv && t.ts && t.weight_t && t.pt && t.loss_unscaled && t.loss && t.A && t.rowscale && t.out,
+                 "linear_bwd_input_tail: null pointer");
+    GD_CHECK_ARG(!t.update_history || (t.Lt_history && t.Lt_count), "linear_bwd_input_tail: update_history without the history");
+    GD_CHECK_ARG(!t.rowscale_mean || t.gradcoef, "linear_bwd_input_tail: rowscale_mean needs gradcoef");
+    GD_CHECK_ARG(lt_lds_bytes(t.T, t.H, M) <= GD_LT_LDS_MAX, "linear_bwd_input_tail: T*H and B too large for the LDS-resident FIFO update (150 KiB)");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t lds_ = round4(K);
+    if (t_gemm_prec == GDMCF_GEMM_F32 && ws != nullptr) {  // the product as gdmcf_linear_bwd_input_f32 hands it to dr_kn_kernel
+        GdGemm g = {};
+        g.A = dZ; g.lda = lddz; g.B = W; g.ldb = ldw; g.M = M; g.N = K; g.K = N;
+        g.C = (float*)ws; g.ldc = lds_; g.slab_stride = (int64_t)M * lds_; g.prof_tag = 4;
+        g.ws_cap = ws_bytes;
+        GdShadow sh;
+        const bool has16 = gd_shadow_lookup(t.out, &sh) && sh.rows == M && sh.cols == t.Ka;  // as gdmcf_rowscale_f32
+        GdTailJob j = {};
+        j.on = 1; j.B = M;
+        j.rowpart = t.rowpart; j.ld_rowpart = t.ld_rowpart; j.nt = t.nt; j.rowsum = t.rowsum;
+        j.rowdiv = t.rowdiv; j.alpha = t.alpha; j.gradcoef = t.gradcoef; j.ts = t.ts; j.weight_t = t.weight_t; j.pt = t.pt;
+        j.T = t.T; j.H = t.H; j.update = t.update_history; j.hist = t.Lt_history; j.cnt = t.Lt_count; j.lu = t.loss_unscaled;
+        j.loss = t.loss; j.loss_mean = t.loss_mean; j.rowscale_mean = t.rowscale_mean; j.inv_b = 1.0f / (float)M;
+        j.K = t.Ka; j.A = t.A; j.lda = t.lda; j.rs = t.rowscale; j.out = t.out; j.ldo = t.ldo;
+        j.out16 = has16 ? (unsigned short*)sh.p16 : nullptr; j.ldo16 = has16 ? sh.ld16 : 0; j.bias_col = t.ldo > t.Ka;
+        const int rc = gd_dr_kn_launch_tail(g, j, s);
+        if (rc != GD_DR_NOT_TAKEN) {
+            if (rc) return rc;
+            return gd_splitk_reduce((const float*)ws, g.slab_stride, gd_cdiv(N, g.kchunk), lds_, M, K, 1, nullptr, rowscale, Aact, ldact,
+                                    act, dA, ldda, s);
+        }
+    }
+    const int rc = gdmcf_kn_tail_run(tail, M, stream);
+    if (rc) return rc;
+    return gdmcf_linear_bwd_input_f32(dZ, lddz, W, ldw, rowscale, Aact, ldact, act, M, N, K, dA, ldda, ws, ws_bytes, stream);
 }
 
 int gdmcf_linear_bwd_weight_f32(const float* dZ, int64_t lddz, const float* A, int64_t lda, const float* rowscale,

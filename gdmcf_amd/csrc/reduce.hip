@@ -1,6 +1,6 @@
 // What linear.hip calls around the dense products: the split-K slab reducer, the bias-gradient column sum, the row-partial
 // reducer of the fused loss, the row scale (with its C entry) and the f32 -> bf16 shadow cast.  Fixed orders: deterministic.
-#include "common.h"
+#include "tail_job.h"
 
 namespace {
 
@@ -59,31 +59,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
-// out[m, k] = A[m, k] * rs[m]; four columns per thread (16-byte accesses; rows need only 4-byte alignment on gfx950)
+// out[m, k] = A[m, k] * rs[m]: gd_rowscale_rows (tail_job.h), one workgroup per 1024 columns of a row
 __global__ __launch_bounds__(256) void rowscale_kernel(const float* __restrict__ A, int64_t lda,
                                                        const float* __restrict__ rs, int M, int K,
                                                        float* __restrict__ out, int64_t ldo,
                                                        unsigned short* __restrict__ out16, int64_t ldo16, int bias_col) {
-    const int m = blockIdx.y, k = (blockIdx.x * 256 + threadIdx.x) * 4;
-    // column K of the scaled copy = the row scale itself: as one more column of the weight-gradient product's second operand it
-    // makes the bias gradient sum_m rs[m] dZ[m, n] column K of that product (gdmcf_linear_bwd_weight_f32)
-    if (bias_col && blockIdx.x == 0 && threadIdx.x == 0) out[(int64_t)m * ldo + K] = rs[m];
-    if (k >= K) return;
-    const float r = rs[m];
-    const float* a = A + (int64_t)m * lda + k;
-    float* o = out + (int64_t)m * ldo + k;
-    float v[4];
-    if (k + 3 < K) {
-        const f32x4 t = *reinterpret_cast<const f32x4_u4*>(a);
-        v[0] = t.x * r; v[1] = t.y * r; v[2] = t.z * r; v[3] = t.w * r;
-        *reinterpret_cast<f32x4_u4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
-    } else {
-        for (int j = 0; j < 4; ++j)
-            if (k + j < K) o[j] = v[j] = a[j] * r;
-    }
-    if (out16)
-        for (int j = 0; j < 4; ++j)
-            if (k + j < K) out16[(int64_t)m * ldo16 + k + j] = gd_bf16_bits(v[j]);
+    gd_rowscale_rows<1>(A, lda, rs, M, K, out, ldo, out16, ldo16, bias_col, blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
 }
 
 // db[n] = sum_m rs[m]*dZ[m,n].  One workgroup per 64 columns; wave w sums rows w, w+4, ... (each row read
@@ -110,15 +91,10 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ d
     if (wave == 0 && n < N) db[n] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
 
-// rowsum[m] = sum_j rowpart[m, j]: one wave per row, lane-strided partials + xor tree (fixed order)
+// rowsum[m] = sum_j rowpart[m, j]: gd_rowpart_reduce_rows (tail_job.h), one wave per row
 __global__ __launch_bounds__(256) void rowpart_reduce_kernel(const float* __restrict__ rowpart, int ld, int M, int nt,
                                                              float* __restrict__ rowsum) {
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (m >= M) return;
-    float s = 0.f;
-    for (int j = lane; j < nt; j += 64) s += rowpart[(int64_t)m * ld + j];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) rowsum[m] = s;
+    gd_rowpart_reduce_rows<1>(rowpart, ld, M, nt, rowsum, blockIdx.x, gridDim.x);
 }
 
 typedef __bf16 gd_bf16x2 __attribute__((ext_vector_type(2)));

@@ -48,6 +48,14 @@ class DenoiserEngine(EngineBase):
         self._side2 = None
         self._side2_used = False
         self._wt_on = os.environ.get("GDMCF_FWD_WT", "1") == "1"
+        # Deferred loss tail.  A caller that runs train_backward(1 / B) right behind training_losses
+        # (parallel.DataParallelStep's direct backward, and GraphedTrainStep through it) sets `defer_tail` around that call:
+        # train_forward then launches neither the loss tail nor the last layer's row scale, and the backward's FIRST launch --
+        # gdmcf_linear_bwd_input_tail_f32, the last layer's input gradient -- carries them on a workgroup the product leaves idle.
+        # Until then losses["loss"], last_loss_mean, bufs.rowscale_mean / gradcoef / lu / hs and the Lt history of that step are
+        # UNWRITTEN; anything else that follows a deferred forward runs the tail on its own first (_flush_tail).
+        self.defer_tail = False
+        self._pending_tail = None
 
     def _grad_like(self, p):
         if not self.static_grads:
@@ -67,8 +75,27 @@ class DenoiserEngine(EngineBase):
                 rec[1] = w._version
 
     def flush_weight_waiters(self):
+        self._flush_tail()
         while self.weight_waiters:
             self.weight_waiters.popitem()[1]()
+
+    def _defers_tail(self, spec, layers, B):
+        """Whether this training forward leaves its loss tail to the backward: asked for (defer_tail), the plain DNN engine, float32
+        products, x0 target, no data-parallel gradient sink, and a last layer whose input gradient the register-streaming kernel takes with a
+        workgroup to spare."""
+        if not self.defer_tail or type(self) is not DenoiserEngine or self.gemm_dtype != "f32" or spec["eps_mode"]:
+            return False
+        if (self.grad_sink is not None and not self.input_grad_first) or len(layers) < 2:  # (a data-parallel sink wants dW first)
+            return False
+        n, k = layers[-1][0].shape
+        return bool(self.lib.gdmcf_debug_kn_tail_rides(B, k, n))
+
+    def _flush_tail(self):
+        """Runs the tail of a deferred training forward whose backward has not come, as launches of its own: no tensor of that
+        step stays unwritten."""
+        pend, self._pending_tail = self._pending_tail, None
+        if pend is not None:
+            core.tail_job_run(self.lib, pend[0], pend[1], _lib.stream_ptr())
 
     # ------------------------------------------------------------------------------------------
     # bf16 shadows (gemm_dtype == "bf16"): bf16 copies of every GEMM operand, streamed instead of the f32 tensors.
@@ -194,6 +221,9 @@ class DenoiserEngine(EngineBase):
     # ------------------------------------------------------------------------------------------
     @with_precision
     def train_forward(self, spec):
+        """loss [B] (float64).  With `defer_tail` set and _defers_tail true, the returned tensor and last_loss_mean are written by
+        the FIRST launch of the train_backward(1 / B) that follows (see __init__)."""
+        self._flush_tail()
         x0, ts = spec["x_start"], spec["ts"]
         csr = spec.get("csr")
         B, dev = (csr.shape[0], csr.device) if csr is not None else (x0.shape[0], x0.device)
@@ -225,14 +255,21 @@ class DenoiserEngine(EngineBase):
         w, bias, _ = layers[-1]
         N, K = w.shape
         self._use_weight(w)
+        defer = self._defers_tail(spec, layers, B)
         if csr is not None:  # the target rows are bitmaps written by the CSR-fed input builder
-            core.loss_layer_bits(lib, bufs, A, w, bias, bufs.x0bits, None, B, N, K, st)
+            nt = core.loss_layer_bits(lib, bufs, A, w, bias, bufs.x0bits, None, B, N, K, st, reduce=not defer)
         else:
-            core.loss_layer(lib, bufs, A, w, bias, target, alpha, B, N, K, st)
+            nt = core.loss_layer(lib, bufs, A, w, bias, target, alpha, B, N, K, st, reduce=not defer)
         # the tail also emits mean(loss) and gradcoef/B: the reference's step takes the mean next (main.py:348), and its
         # backward scales every row by 1/B -- two launches less per step (DataParallelStep uses both)
-        loss, self.last_loss_mean = core.loss_tail(lib, bufs, spec, B, rowdiv, alpha, st, mean=True)
-        self._saved = dict(kind="train", B=B, bufs=bufs, layers=layers, keepalive=(keepalive, target, alpha, rowdiv, spec["pt"]))
+        tail = None
+        if defer:  # row-partial reduction, tail and the last layer's row scale: in the backward's first launch
+            loss, self.last_loss_mean, tail = core.loss_tail_job(lib, bufs, spec, B, rowdiv, alpha, nt, A, K)
+            self._pending_tail = (tail, B)
+        else:
+            loss, self.last_loss_mean = core.loss_tail(lib, bufs, spec, B, rowdiv, alpha, st, mean=True)
+        self._saved = dict(kind="train", B=B, bufs=bufs, layers=layers, tail=tail,
+                           keepalive=(keepalive, target, alpha, rowdiv, spec["pt"]))
         return loss
 
     @with_precision
@@ -243,6 +280,14 @@ class DenoiserEngine(EngineBase):
         if sv is None or sv.get("kind") != "train":
             raise RuntimeError("gdmcf_amd: train_backward without a preceding training_losses")
         bufs = sv["bufs"]
+        tail = sv.get("tail")
+        if tail is not None and self._pending_tail is not None and self._pending_tail[0] is tail:
+            if isinstance(gloss, float) and gloss == 1.0 / sv["B"]:
+                # the deferred tail rides the last layer's input gradient, which reads the row scale it writes only behind a
+                # kernel boundary (the split-K reducer)
+                self._pending_tail = None
+                return self._backward(sv, bufs.diff, bufs.rowscale_mean, tail=tail)
+            self._flush_tail()
         if isinstance(gloss, float) and gloss == 1.0 / sv["B"] and getattr(bufs, "rowscale_mean", None) is not None:
             rowscale = bufs.rowscale_mean  # gradcoef * (float)(1/B), written by the loss tail: same bits as the product below
         else:
@@ -280,9 +325,12 @@ class DenoiserEngine(EngineBase):
         return self._backward(sv, g, None)
 
     # ------------------------------------------------------------------------------------------
-    def _backward(self, sv, dz_last, rowscale):
+    def _backward(self, sv, dz_last, rowscale, tail=None):
         """Gradients in model.parameters() order: emb_layer (w, b), in_layers..., out_layers...
         dz_last is d(loss)/d(last layer output) up to the per-row factor `rowscale`.
+        tail: the job of a deferred training forward (engine_core.loss_tail_job).  The last layer's input gradient then comes first
+        and carries it (gdmcf_linear_bwd_input_tail_f32): that launch writes `rowscale` and the row-scaled copy bufs.hs, which
+        the last layer's weight gradient reads without a row-scale launch of its own.
 
         Order inside a layer: data parallel wants the weight gradient first (its all-reduce then overlaps the
         input-gradient GEMM); the fused optimiser needs the input gradient first (it reads W, which the
@@ -307,7 +355,10 @@ class DenoiserEngine(EngineBase):
             N, K = w.shape
             if li > 0:
                 dprev = bufs.dzs[li - 1]
-                self._input_grad(bufs, B, w, N, K, dz, rs, A_prev, layers[li - 1][2], dprev, st)
+                if tail is not None and li == L - 1:
+                    core.linear_bwd_input_tail(lib, bufs, dz, w, rs, A_prev, layers[li - 1][2], B, N, K, dprev, tail, st)
+                else:
+                    self._input_grad(bufs, B, w, N, K, dz, rs, A_prev, layers[li - 1][2], dprev, st)
                 return dprev
             dWe = self._grad_like(m.emb_layer.weight)
             dbe = self._grad_like(m.emb_layer.bias)
@@ -318,7 +369,10 @@ class DenoiserEngine(EngineBase):
             db = self._grad_like(bias)
             # without a row scale, the first layer's input already holds 1 in its first padding column (the input builder's)
             scol = int(rs is None and li == 0 and getattr(bufs, "xin_ones", False) and A_prev.stride(0) > w.shape[1])
-            A_use, scol = self._row_scaled(bufs, B, w.shape[1], A_prev, rs, scol, st)
+            if tail is not None and li == L - 1:  # the tail job wrote bufs.hs, its column K included
+                A_use, scol = bufs.hs, int(bufs.hs.stride(0) > w.shape[1])
+            else:
+                A_use, scol = self._row_scaled(bufs, B, w.shape[1], A_prev, rs, scol, st)
             fs = fused.fused_state(w) if fused is not None else None
             dW = self._grad_like(w) if fs is None else None
             if fs is None and self._gemm_side and self.grad_sink is None and li == L - 1 and L > 1:
@@ -340,7 +394,7 @@ class DenoiserEngine(EngineBase):
         for li in range(L - 1, -1, -1):
             w, bias, _ = layers[li]
             A_prev = bufs.acts[li - 1] if li > 0 else bufs.xin
-            if fused is not None or self.input_grad_first:
+            if fused is not None or self.input_grad_first or (tail is not None and li == L - 1):
                 nxt = input_grad(li, w, A_prev)
                 weight_grad(li, w, bias, A_prev)
             else:

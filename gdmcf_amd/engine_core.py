@@ -10,6 +10,7 @@
 PyTorch is used for device memory and streams only; every arithmetic step is a HIP kernel.
 """
 import collections
+import ctypes
 import functools
 
 import torch
@@ -325,21 +326,24 @@ def emb_bwd(lib, bufs, dz, W, I_cols, E, B, N, dWe, dbe, st):
 # ------------------------------------------------------------------------------------------------------------------
 # output layers
 # ------------------------------------------------------------------------------------------------------------------
-def loss_layer(lib, bufs, A, W, bias, target, alpha, B, N, K, st):
+def loss_layer(lib, bufs, A, W, bias, target, alpha, B, N, K, st, reduce=True):
     """Last product fused with the per-row loss: bufs.diff = alpha * (A @ W^T + bias) - target, its row sums of squares in
-    bufs.rowsum (the output itself is never stored)."""
+    bufs.rowsum (the output itself is never stored).  reduce=False: the sums stay partial in bufs.rowpart (loss_tail_job reduces
+    them); returns how many there are per row."""
     (a, lda), (w, ldw) = _pl(A), _pl(W)
     _lib.check(lib.gdmcf_linear_loss_fwd_f32(a, lda, w, ldw, _lib.ptr(bias), target.data_ptr(), target.stride(0),
                                              _lib.ptr(alpha), B, N, K, None, 0, bufs.diff.data_ptr(), bufs.ldi,
-                                             bufs.rowpart.data_ptr(), bufs.rowsum.data_ptr(), st))
+                                             bufs.rowpart.data_ptr(), bufs.rowsum.data_ptr() if reduce else None, st))
+    return int(lib.gdmcf_loss_parts_last())
 
 
-def loss_layer_bits(lib, bufs, A, W, bias, x0bits, alpha, B, N, K, st):
+def loss_layer_bits(lib, bufs, A, W, bias, x0bits, alpha, B, N, K, st, reduce=True):
     """loss_layer with the {0,1} target rows given as bitmaps (the CSR-fed input builders write them): same arithmetic."""
     (a, lda), (w, ldw) = _pl(A), _pl(W)
     _lib.check(lib.gdmcf_linear_loss_fwd_bits_f32(a, lda, w, ldw, _lib.ptr(bias), x0bits.data_ptr(), x0bits.stride(0),
                                                   _lib.ptr(alpha), B, N, K, None, 0, bufs.diff.data_ptr(), bufs.ldi,
-                                                  bufs.rowpart.data_ptr(), bufs.rowsum.data_ptr(), st))
+                                                  bufs.rowpart.data_ptr(), bufs.rowsum.data_ptr() if reduce else None, st))
+    return int(lib.gdmcf_loss_parts_last())
 
 
 def loss_tail(lib, bufs, spec, B, rowdiv, alpha, st, mean=False):
@@ -359,6 +363,39 @@ def loss_tail(lib, bufs, spec, B, rowdiv, alpha, st, mean=False):
         bufs.rowscale_mean = torch.zeros(B, dtype=torch.float32, device=ts.device)
     _lib.check(lib.gdmcf_row_loss_finish_mean_f64(*args, loss_mean.data_ptr(), bufs.rowscale_mean.data_ptr(), st))
     return loss, loss_mean
+
+
+def loss_tail_job(lib, bufs, spec, B, rowdiv, alpha, nt, A, K):
+    """What loss_layer(reduce=False) leaves to do, as the tail job of gdmcf_linear_bwd_input_tail_f32: the reduction of the `nt`
+    partial sums per row of bufs.rowpart, loss_tail(mean=True), and rowscale(A, bufs.rowscale_mean, B, K, bufs.hs).  Nothing is
+    launched here.  Returns (loss, mean(loss), job): the two tensors loss_tail would return -- UNWRITTEN until the job has run
+    -- and the _lib.GdKnTail, which keeps `refs` (every tensor it points into) alive."""
+    ts = spec["ts"]
+    loss = torch.empty(B, dtype=torch.float64, device=ts.device)
+    loss_mean = torch.empty((), dtype=torch.float64, device=ts.device)
+    if getattr(bufs, "rowscale_mean", None) is None:
+        bufs.rowscale_mean = torch.zeros(B, dtype=torch.float32, device=ts.device)
+    (a, lda) = _pl(A)
+    job = _lib.GdKnTail(bufs.rowpart.data_ptr(), bufs.rowpart.stride(0), nt, bufs.rowsum.data_ptr(), rowdiv.data_ptr(),
+                        _lib.ptr(alpha), ts.data_ptr(), spec["weight_t"].data_ptr(), spec["pt"].data_ptr(), spec["T"], spec["H"],
+                        spec["Lt_history"].data_ptr(), spec["Lt_count"].data_ptr(), int(spec["update_history"]),
+                        bufs.lu.data_ptr(), loss.data_ptr(), bufs.gradcoef.data_ptr(), loss_mean.data_ptr(),
+                        bufs.rowscale_mean.data_ptr(), a, lda, bufs.rowscale_mean.data_ptr(), K, bufs.hs.data_ptr(),
+                        bufs.hs.stride(0))
+    job.refs = (loss, loss_mean, rowdiv, alpha, ts, spec["weight_t"], spec["pt"], spec["Lt_history"], spec["Lt_count"], A)
+    return loss, loss_mean, job
+
+
+def tail_job_run(lib, job, B, st):
+    """The three launches of a loss_tail_job on their own (gdmcf_kn_tail_run)."""
+    _lib.check(lib.gdmcf_kn_tail_run(ctypes.byref(job), B, st))
+
+
+def linear_bwd_input_tail(lib, bufs, dz, W, rs, A_prev, act_prev, B, N, K, d_prev, job, st):
+    """linear_bwd_input with a loss_tail_job in (or in front of) its launch: gdmcf_linear_bwd_input_tail_f32."""
+    (z, ldz), (w, ldw), (a, lda), (d, ldd) = _pl(dz), _pl(W), _pl(A_prev), _pl(d_prev)
+    _lib.check(lib.gdmcf_linear_bwd_input_tail_f32(z, ldz, w, ldw, _lib.ptr(rs), a, lda, act_prev, B, N, K, d, ldd,
+                                                   bufs.ws.data_ptr(), bufs.ws_bytes, ctypes.byref(job), st))
 
 
 def posterior_fwd(lib, A, W, bias, x_t, c1, c2, r1, r2, sigma, z, B, N, K, x_next, pred, st):

@@ -1,7 +1,8 @@
 """The training step as ONE hipGraph (MI355X-native: capture the launch-bound loop instead of tracing it).
 
 `GraphedTrainStep(diffusion, model, optimizer, csr, batch_size)` captures the body of the reference's loop (main.py:345-351:
-zero_grad -> training_losses -> mean -> backward -> AdamW.step; 18 kernel launches at the Yelp shape) once and replays it per
+zero_grad -> training_losses -> mean -> backward -> AdamW.step; 15 kernel launches at the Yelp shape: the loss tail rides the
+input gradient's launch, DenoiserEngine.defer_tail) once and replays it per
 batch: the host then enqueues one graph launch and one 3 KB copy of the batch's row ids per step instead of ~150 Python /
 ctypes calls.  A replay runs the SAME launches with the SAME arguments, so everything that changes from step to step lives
 in device memory:
@@ -173,6 +174,8 @@ class GraphedTrainStep:
         tensors: eager steps, checkpoints and resumes then continue exactly where the graph stopped."""
         if self._state is None:
             return
+        if hasattr(self.eng, "_flush_tail"):
+            self.eng._flush_tail()  # (a deferred loss tail whose backward never came)
         prep, ts, step = self._read_state()
         self.eng.offset = prep
         if self.reweight:  # (the sampler's Philox position only moves when importance sampling draws timesteps)

@@ -314,8 +314,17 @@ class DataParallelStep:
         if self.direct_backward and eng is not None:
             # mean reduction has the constant upstream gradient 1/B: run the backward directly instead of through an
             # autograd graph (same kernels on the same values; saves four tiny elementwise launches per step)
-            with torch.no_grad():
-                losses = self.diffusion.training_losses(self.model, batch, reweight, **rand)
+            # the backward follows at once: the engine may leave the loss tail to its first launch (DenoiserEngine.defer_tail --
+            # losses["loss"] and last_loss_mean are then written there, and read by nobody before)
+            defers = hasattr(eng, "defer_tail")
+            if defers:
+                eng.defer_tail = True
+            try:
+                with torch.no_grad():
+                    losses = self.diffusion.training_losses(self.model, batch, reweight, **rand)
+            finally:
+                if defers:
+                    eng.defer_tail = False
             loss = getattr(eng, "last_loss_mean", None)  # written by the loss tail kernel (fixed-order float64 mean)
             if loss is None:
                 loss = losses["loss"].mean()

@@ -317,7 +317,8 @@ int gdmcf_latent_acc_f32(const float* q_cur, int64_t ldqc, const float* qa, cons
 /* Last layer fused with the per-row diffusion loss (gaussian_diffusion.py:335 mean_flat):
  *   out = A @ W^T + bias ;  diff[m,n] = alpha[m]*out[m,n] - target[m,n]   (alpha NULL -> 1)
  *   rowsum[m] = sum_n diff[m,n]^2  (deterministic two-stage reduction)
- * `out` may be NULL (training never needs it).  rowpart: scratch [M, gdmcf_loss_tiles(N)]. */
+ * `out` may be NULL (training never needs it).  rowpart: scratch [M, gdmcf_loss_tiles(N)].  rowsum NULL: the second stage is
+ * left to the caller (gdmcf_linear_bwd_input_tail_f32). */
 int gdmcf_loss_tiles(int N);
 int gdmcf_linear_loss_fwd_f32(const float* A, int64_t lda, const float* W, int64_t ldw,
                               const float* bias, const float* target, int64_t ldt,
@@ -348,6 +349,55 @@ int gdmcf_linear_bwd_input_f32(const float* dZ, int64_t lddz, const float* W, in
                                const float* rowscale, const float* Aact, int64_t ldact, int act,
                                int M, int N, int K, float* dA, int64_t ldda, void* ws,
                                size_t ws_bytes, void* stream);
+/* The input gradient of the LAST layer of a training step together with the step's three small launches that stand between the
+ * loss product and it -- none of which writes anything the product reads:
+ *   (1) rowsum[m] = sum_j rowpart[m, j], j < nt       what gdmcf_linear_loss_fwd_*_f32 runs behind its product unless its
+ *                                                      rowsum is NULL (then gdmcf_loss_parts_last() is nt)
+ *   (2) gdmcf_row_loss_finish_mean_f64 on that rowsum  (B = M; T, H, the history and every output as there)
+ *   (3) gdmcf_rowscale_f32(A, lda, rowscale, M, Ka, out, ldo)   rowscale is usually (2)'s rowscale_mean
+ * The entry then runs gdmcf_linear_bwd_input_f32 with the arguments in front of `tail`; its `rowscale` may be written by (2).
+ * Where the register-streaming kernel (family 5) takes the product and its task list leaves a workgroup without work, that one
+ * workgroup runs (1)-(3) in this order INSIDE the product's launch, on a compute unit the product does not use; otherwise --
+ * product not taken, GDMCF_DR_KN=0, no idle workgroup, more LDS than (2) may have, GDMCF_KN_TAIL=0 -- (1), (2), (3) are
+ * launched on their own and gdmcf_linear_bwd_input_f32 after them.  Every buffer holds the same bits either way, and
+ * gdmcf_debug_last_gemm reports what the plain entry would.  All pointers of (1)-(3) as their own entries require them. */
+typedef struct GdKnTail {
+    const float* rowpart;
+    int ld_rowpart, nt;
+    float* rowsum;
+    const float* rowdiv;
+    const float* alpha;
+    const int64_t* ts;
+    const double* weight_t;
+    const double* pt;
+    int T, H;
+    double* Lt_history;
+    int64_t* Lt_count;
+    int update_history;
+    double* loss_unscaled;
+    double* loss;
+    float* gradcoef;
+    double* loss_mean;
+    float* rowscale_mean;
+    const float* A;
+    int64_t lda;
+    const float* rowscale;
+    int Ka;
+    float* out;
+    int64_t ldo;
+} GdKnTail;
+int gdmcf_linear_bwd_input_tail_f32(const float* dZ, int64_t lddz, const float* W, int64_t ldw, const float* rowscale,
+                                    const float* Aact, int64_t ldact, int act, int M, int N, int K, float* dA, int64_t ldda,
+                                    void* ws, size_t ws_bytes, const GdKnTail* tail, void* stream);
+/* (1), (2), (3) of a tail job over M rows as three launches of their own: what gdmcf_linear_bwd_input_tail_f32 issues where the
+ * job cannot ride, for a caller whose step does not reach that entry. */
+int gdmcf_kn_tail_run(const GdKnTail* tail, int M, void* stream);
+/* Partial row sums per row (nt above) that the calling thread's last gdmcf_linear_loss_fwd_f32 / _bits_f32 product wrote. */
+int gdmcf_loss_parts_last(void);
+/* 1 when the register-streaming kernel, on the current device, would take the product C[M, N] with reduction length K (the input
+ * gradient dZ[M, K] W[K, N]) AND leave a workgroup without work for a tail job; host only, nothing launched.  The call itself may
+ * still decline (alignment, workspace, the switches). */
+int gdmcf_debug_kn_tail_rides(int M, int N, int K);
 /* dW[N,K] = dZ[M,N]^T @ A[M,K]  (weight grad; accumulate != 0 adds into dW)
  * db[N]   = sum_m rowscale[m]*dZ[m,n]   (db NULL -> skipped).  When rowscale != NULL the
  * caller passes A already multiplied by rowscale (see gdmcf_rowscale_f32).
