@@ -1,7 +1,8 @@
 """GPU (-m gpu): the fused LightGCN BPR step (csrc/bpr.hip, gdmcf_amd.lightgcn.BPRTrainer / bpr_loss_grad) against
 oracle.lightgcn_bpr_step (CPU torch.sparse autograd) and against the autograd route around the same propagation kernels.
 Tolerances are those of test_gpu_parity.py::test_lightgcn_bpr_step_gradients_match_oracle -- the same quantities against the
-same oracle: |mf - ref| < 1e-6, |reg - ref| < 1e-4 ref, relerr(grad) < 1e-5."""
+same oracle: |mf - ref| < 1e-6, |reg - ref| < 1e-4 ref, relerr(grad) < 1e-5.
+The loss and scatter kernels alone, at every lane width, run length and stride: tests/test_gpu_bpr_kernels.py."""
 import functools
 
 import numpy as np

@@ -79,6 +79,28 @@ def test_draws_match_the_host_model_on_an_unaligned_table_view():
     check_exact(d, 3, 5, view, M)
 
 
+@pytest.mark.parametrize("n_negs,pool", [(1, 3), (3, 5), (2, 70)])
+@pytest.mark.parametrize("d", [1, 3, 4, 12, 20, 200, 256, 260, 516])
+def test_draws_match_the_host_model_at_every_lane_width(d, n_negs, pool):
+    """The lane groups the test above leaves out -- d = 1, 3, 4: one lane; 12: four; 20: eight; 200, 256: a whole wave -- and two
+    (260) and three (516) column passes, where the user row's first pass stays in registers and the rest is read again.  A pool
+    of 70 is more than the widest lane group: two chunks of candidates.  |score| <= 4 d = 2064: exact."""
+    M = integer_table(d)
+    check_exact(d, n_negs, pool, cu(M), M)
+
+
+def test_draws_match_the_host_model_on_an_unaligned_table_view_in_two_column_passes():
+    """as the view above at d = 260: element-wise loads in both column passes"""
+    d = 260
+    M = integer_table(d)
+    N = M.shape[0]
+    store = torch.zeros(N * (d + 1) + 1, dtype=torch.float32, device=DEV)
+    view = store[1:].view(N, d + 1)[:, :d]
+    view.copy_(cu(M))
+    assert view.stride() == (d + 1, 1) and view.data_ptr() % 16 == 4
+    check_exact(d, 2, 70, view, M)
+
+
 def test_ties_keep_the_earliest_drawn():
     indptr, indices, U, It, users = R.edge_graph()
     ip, ix, ud = edge_device()
