@@ -13,7 +13,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 SOURCES = ["capi.hip", "dp_exchange.hip", "gemm_f32.hip", "gemm_bf16.hip", "gemm_split.hip", "gemm_small.hip", "gemm_dr.hip", "gemm_dr_tn.hip", "gemm_dr_fat.hip", "gemm_dr_kn.hip", "prep_input.hip", "noise.hip", "loss_tail.hip", "adamw.hip", "rows.hip", "reduce.hip", "linear.hip", "topk.hip", "spmm_csr.hip", "rank_metrics.hip", "spmm_bundle.hip", "score_topk.hip", "score_rank.hip", "bpr.hip", "cat.hip", "gather_fwd.hip", "ntxent.hip", "latent_step.hip", "cand_scores.hip", "rank.hip"]
-HEADERS = ["common.h", "draws.h", "rank_order.h", "score_product.h", "spmm.h", "gemm_dr.h", "gemm_epilogue.h", "tail_job.h", os.path.join("..", "..", "include", "gdmcf_hip.h")]
+HEADERS = ["common.h", "draws.h", "rank_order.h", "score_product.h", "spmm.h", "gemm_dr.h", "gemm_epilogue.h", "gemm_launch.h", "tail_job.h", os.path.join("..", "..", "include", "gdmcf_hip.h")]
 LIB = os.path.join(CSRC, "libgdmcf_hip.so")
 ASM_LINT = ("gemm_dr_tn.hip", "gemm_split.hip")  # disassembled and run through lint_vmcnt + lint_store_data at every build
 STORE_LINT = ("gemm_f32.hip", "gemm_bf16.hip", "gemm_dr_fat.hip", "gemm_dr_kn.hip", "score_topk.hip", "score_rank.hip", "latent_step.hip", "bpr.hip")  # disassembled for lint_store_data only

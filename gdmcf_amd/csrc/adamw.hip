@@ -140,7 +140,7 @@ static int adamw_launch(const int64_t* table, const int64_t* shadow_table, int n
         GdProfScope prof(6, (shadow_table ? 30.0 : 28.0) * ADAM_BLOCK_ELEMS * (double)total_blocks, (hipStream_t)stream);
         // nontemporal accesses for the streamed optimiser state: A/B on one box 0.344 -> 0.318 ms at the Yelp shape,
         // 1.032 -> 0.911 ms at the Amazon-Book shape (GDMCF_ADAMW_NT=0 switches back for comparison runs)
-        static const bool nt = !(getenv("GDMCF_ADAMW_NT") && atoi(getenv("GDMCF_ADAMW_NT")) == 0);
+        static const bool nt = gd_env_int("GDMCF_ADAMW_NT", 1) != 0;
         if (nt)
             hipLaunchKernelGGL(adamw_kernel<true>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, n_tensors, h,
                                shadow_table, t_gd_step_state);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/gdmcf_hip.h"
 
@@ -53,6 +54,13 @@ struct GdProfScope {
         if (on) gd_prof_end(s);
     }
 };
+
+// An integer knob of the environment, dflt when it is not set (DESIGN.md lists them all; a switch is gd_env_int(name, 1) != 0: on
+// unless set to 0).  The only getenv of the library: callers that read a knob once keep the value in a static const of their own.
+static inline int gd_env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
 
 static inline int gd_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool gd_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -24,12 +24,12 @@
 // plain structure (register-staged double buffering, one barrier per k-tile, occupancy to cover latency) and
 // the extra tile class 3 = 208x256 on eight waves for the batch-sized products (M = 400 = 2 x 208 - 16): 55 %
 // fewer L2 bytes per FLOP than 80x128.
-#include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -495,29 +495,7 @@ int launch_one(GdGemm& g, hipStream_t s) {
     constexpr size_t lds = 2 * (size_t)(BM + BN) * 128;
     auto kern = gemm_bf16_kernel<LAYA, LAYB, BM, BN, WM, WN, EPI, S16>;
     static bool attr_set = false;
-    if (!attr_set && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            gdmcf_set_error("hipFuncSetAttribute(LDS=%zu): %s", lds, hipGetErrorString(e));
-            return GDMCF_E_HIP;
-        }
-        attr_set = true;
-    }
-    g.tiles_m = gd_cdiv(g.M, BM);
-    g.tiles_n = gd_cdiv(g.N, BN);
-    if (g.splits < 1) g.splits = 1;
-    if (g.kchunk <= 0) g.kchunk = gd_cdiv(gd_cdiv(g.K, g.splits), BK) * BK;
-    const long grid = (long)g.tiles_m * g.tiles_n * g.splits;
-    if (grid <= 0 || grid > 0x7fffffffL) {
-        gdmcf_set_error("gemm grid out of range: %ld", grid);
-        return GDMCF_E_SHAPE;
-    }
-    {
-        GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * WM * WN), lds, s, g);
-    }
-    return gd_launch_status("gemm_bf16");
+    return gd_tiled_launch(kern, 64 * WM * WN, lds, lds, BM, BN, BK, &attr_set, "gemm_bf16", g, s);
 }
 
 template <int LAYA, int LAYB, int EPI>
@@ -538,29 +516,20 @@ int launch_class(int cls, GdGemm& g, hipStream_t s) {
     return GDMCF_E_ARG;
 }
 
+struct ClassLauncher {
+    template <int LAYA, int LAYB, int EPI>
+    int operator()(int cls, GdGemm& g, hipStream_t s) const { return launch_class<LAYA, LAYB, EPI>(cls, g, s); }
+};
+
 }  // namespace
 
 int gd_gemm_bf16_launch(int layA, int layB, int epi, int cls, GdGemm& g, hipStream_t s) {
     // timing ablations of the weight-gradient products (tools/bf16_fused_sweep.sh): bit 0 skips the k loop, bit 1 the epilogue
-    static const int dbg = getenv("GDMCF_BF16_DBG") ? atoi(getenv("GDMCF_BF16_DBG")) : 0;
+    static const int dbg = gd_env_int("GDMCF_BF16_DBG", 0);
     if (dbg && layA == GD_LAY_MC && layB == GD_LAY_MC) g.dbg = dbg;
     if (g.kchunk > 0 && g.kchunk % BK != 0) {
         gdmcf_set_error("gemm_bf16: kchunk %d is not a multiple of %d", g.kchunk, BK);
         return GDMCF_E_ARG;
     }
-    if (layA == GD_LAY_KC && layB == GD_LAY_KC) {
-        switch (epi) {
-            case GD_EPI_SLAB: return launch_class<GD_LAY_KC, GD_LAY_KC, GD_EPI_SLAB>(cls, g, s);
-            case GD_EPI_BIAS_ACT: return launch_class<GD_LAY_KC, GD_LAY_KC, GD_EPI_BIAS_ACT>(cls, g, s);
-            case GD_EPI_LOSS: return launch_class<GD_LAY_KC, GD_LAY_KC, GD_EPI_LOSS>(cls, g, s);
-            case GD_EPI_POST: return launch_class<GD_LAY_KC, GD_LAY_KC, GD_EPI_POST>(cls, g, s);
-        }
-    } else if (layA == GD_LAY_KC && layB == GD_LAY_MC) {
-        if (epi == GD_EPI_SLAB) return launch_class<GD_LAY_KC, GD_LAY_MC, GD_EPI_SLAB>(cls, g, s);
-    } else if (layA == GD_LAY_MC && layB == GD_LAY_MC) {
-        if (epi == GD_EPI_STORE) return launch_class<GD_LAY_MC, GD_LAY_MC, GD_EPI_STORE>(cls, g, s);
-        if (epi == GD_EPI_ADAMW) return launch_class<GD_LAY_MC, GD_LAY_MC, GD_EPI_ADAMW>(cls, g, s);
-    }
-    gdmcf_set_error("unsupported bf16 gemm variant (layA=%d layB=%d epi=%d)", layA, layB, epi);
-    return GDMCF_E_UNSUPPORTED;
+    return gd_gemm_variant("bf16 ", layA, layB, epi, ClassLauncher{}, cls, g, s);
 }

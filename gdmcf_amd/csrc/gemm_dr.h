@@ -15,6 +15,8 @@
 //                                        [6]  the same loop over a K range per task: the first-layer forward as split-K slabs  GDMCF_DR_FAT_SLAB
 //   gemm_dr_kn.hip   dr_kn_kernel        [5]  the input gradient and the cached-W^T forward as split-K slabs               GDMCF_DR_KN
 //   gemm_dr.hip      the switches, the CU count and gd_gemm_dr_launch: the common refusals and the (layA, layB, epi) dispatch
+// Who calls: gd_gemm_launch (gemm_f32.hip) offers every f32 product to gd_gemm_dr_launch ahead of the LDS-tiled families; linear.hip
+// calls gd_gemm_dr_adamw_multi for its list entry and gd_dr_kn_launch_tail (tail_job.h) for the input gradient that carries a tail job.
 //
 // Each kernel file exports ONE take-or-decline function (below).  It owns everything that belongs to its kernel -- the route
 // switch, the shape / alignment / 32-bit-offset predicates, the GdProfScope, the family code, the launch -- and either launches

@@ -18,10 +18,7 @@ int dr_cu_count() {
 #define GD_FAT_SLAB_DEFAULT 1  // GDMCF_DR_FAT_SLAB when the environment does not set it
 #endif
 
-static bool dr_env_on(const char* name, bool dflt = true) {
-    const char* v = getenv(name);
-    return v == nullptr ? dflt : atoi(v) != 0;
-}
+static bool dr_env_on(const char* name, bool dflt = true) { return gd_env_int(name, dflt) != 0; }
 DrRoutes& dr_routes() {
     static DrRoutes r = {dr_env_on("GDMCF_DR_DW"), dr_env_on("GDMCF_DR_ADAMW"), dr_env_on("GDMCF_DR_KN"), dr_env_on("GDMCF_DR_FAT"),
                          dr_env_on("GDMCF_DR_FAT_SLAB", GD_FAT_SLAB_DEFAULT != 0)};
@@ -29,7 +26,7 @@ DrRoutes& dr_routes() {
 }
 
 int dr_stagger() {
-    static const int stagger = getenv("GDMCF_DR_STAGGER") ? atoi(getenv("GDMCF_DR_STAGGER")) : 3;
+    static const int stagger = gd_env_int("GDMCF_DR_STAGGER", 3);
     return stagger;
 }
 

@@ -452,7 +452,7 @@ int dr_fat_go(const DrArgs& d, int epi, int dma, int n_cu, hipStream_t s) {
 // B's pieces straight into LDS (GDMCF_FAT_DMA=1; 0: through staging registers): 16 bytes per lane from a 16-byte-aligned source,
 // any other weight runs the register-staged loop
 int dr_fat_dma(const GdGemm& g) {
-    static const int dma_env = getenv("GDMCF_FAT_DMA") ? atoi(getenv("GDMCF_FAT_DMA")) : GD_FAT_DMA_DEFAULT;
+    static const int dma_env = gd_env_int("GDMCF_FAT_DMA", GD_FAT_DMA_DEFAULT);
     return (dma_env > 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0 && (g.ldb & 3) == 0) ? 1 : 0;
 }
 
@@ -493,7 +493,7 @@ int gd_dr_fat_launch(int epi, GdGemm& g, hipStream_t s) {
     d.ksp = gd_cdiv(g.K, 16);  // chunks of 16 k
     {
         // x_t prefetch of the reverse step: this many chunks before the end of the k loop (0: off; A/B knob)
-        static const int pf = getenv("GDMCF_FAT_PF") ? atoi(getenv("GDMCF_FAT_PF")) : 10;
+        static const int pf = gd_env_int("GDMCF_FAT_PF", 10);
         d.stagger = pf;  // (DrArgs: the field doubles as this kernel's prefetch distance)
     }
     const int dma = dr_fat_dma(g);

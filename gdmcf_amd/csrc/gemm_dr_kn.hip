@@ -197,8 +197,7 @@ static int kn_launch(GdGemm& g, const GdTailJob* job, hipStream_t s) {
     GdTailJob none = {};
     size_t lds = 0;
     if (job) {
-        const char* env = getenv("GDMCF_KN_TAIL");  // (read at every call: one process can time and test both)
-        const bool tail_on = env ? atoi(env) != 0 : GD_KN_TAIL_DEFAULT != 0;
+        const bool tail_on = gd_env_int("GDMCF_KN_TAIL", GD_KN_TAIL_DEFAULT) != 0;  // (read at every call: one process can time and test both)
         lds = lt_lds_bytes(job->T, job->H, job->B);
         if (!tail_on || !job->on || !kn_idle_workgroup(d.tiles_m * d.tiles_n * real_splits, n_cu) || lds > GD_LT_LDS_MAX)
             return GD_DR_NOT_TAKEN;

@@ -835,7 +835,7 @@ int dr_tn_adamw_go(const DrMultiArgs& d, hipStream_t s) {
         const DrAdamProd& p = d.p[i];
         lines = lines && (p.ldc & 31) == 0 && (((uintptr_t)p.W | (uintptr_t)p.ea | (uintptr_t)p.ea2) & 127) == 0;
     }
-    static const int force = getenv("GDMCF_DR_NT_LOADS") ? atoi(getenv("GDMCF_DR_NT_LOADS")) : -1;  // tuning knob: 0 / 1
+    static const int force = gd_env_int("GDMCF_DR_NT_LOADS", -1);  // tuning knob: 0 / 1
     return (force >= 0 ? force != 0 : lines) ? dr_tn_adamw_go<D, true>(d, s) : dr_tn_adamw_go<D, false>(d, s);
 }
 
@@ -882,7 +882,7 @@ static bool dr_tn_prepare(int epi, GdGemm& g, DrArgs& d, float** bias_db, int* d
     d.tiles_n = gd_cdiv(g.N, 64);
     d.m_fastest = d.tiles_m <= d.tiles_n;  // tiles that share the LARGER operand's panel draw consecutive tickets
     {   // tuning knob: GDMCF_DR_MF=0|1 forces the ticket order of the fused-AdamW product
-        static const int mf = getenv("GDMCF_DR_MF") ? atoi(getenv("GDMCF_DR_MF")) : -1;
+        static const int mf = gd_env_int("GDMCF_DR_MF", -1);
         if (mf >= 0 && epi == GD_EPI_ADAMW) d.m_fastest = mf;
     }
     const int ks = gd_cdiv(g.K, 4);
@@ -893,7 +893,7 @@ static bool dr_tn_prepare(int epi, GdGemm& g, DrArgs& d, float** bias_db, int* d
         if (w < waste) { waste = w; best = dd; }
     }
     {   // tuning knob: GDMCF_DR_D=7|8|9 forces the ring depth
-        static const int forced = getenv("GDMCF_DR_D") ? atoi(getenv("GDMCF_DR_D")) : 0;
+        static const int forced = gd_env_int("GDMCF_DR_D", 0);
         if (forced >= 7 && forced <= 9) { best = forced; waste = gd_cdiv(ks, best + 1) * (best + 1) - ks; }
     }
     d.ksp = ks + waste;

@@ -12,10 +12,16 @@
 // identically for A and B so a b128 read feeds four consecutive MFMAs.
 // The exact f32 MFMA is a k-ordered fmaf chain, so results are deterministic for a given
 // (tile, split) configuration.
-#include <stdlib.h>
-
+//
+// In this file: TileGeom and the staging / fragment helpers; gemm_f32_kernel and the wave-specialised
+// gemm_f32_spec_kernel (MC/MC, 128x128); launch_one (a kernel and its LDS size, then gd_tiled_launch of
+// gemm_launch.h), launch_class (tile class -> tile shape), ClassLauncher (variant -> tile depth); the tile
+// classes (gd_gemm_tile_m / _n, gd_pick_shape_class); gd_gemm_launch: the door of every dense product --
+// the bf16 / f32x3 families, the direct-to-register kernels (gemm_dr.h), gemm_small.hip, else
+// gd_gemm_variant (gemm_launch.h) onto this family.
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_launch.h"
 
 #ifdef GD_PROBE_NO_LDSWRITE
 #define GD_PROBE_LDSWRITE_OFF 1
@@ -650,7 +656,7 @@ int launch_one(GdGemm& g, hipStream_t s) {
     // Row-contiguous x row-contiguous products (the weight gradients) run the wave-specialised kernel: measured
     // +6-7 % at 128x128 tiles on the Yelp shape, no gain or a loss for the K-contiguous products
     // (profiles/r01_spec_ab.txt).  GDMCF_GEMM_SPEC=0 switches it off for A/B runs.
-    static const bool spec_on = !(getenv("GDMCF_GEMM_SPEC") && atoi(getenv("GDMCF_GEMM_SPEC")) == 0);
+    static const bool spec_on = gd_env_int("GDMCF_GEMM_SPEC", 1) != 0;
     constexpr bool SPEC_OK = (LAYA == 1 && LAYB == 1 && BM == 128 && BN == 128);
     const bool spec = SPEC_OK && spec_on;
     if (spec) lds = (size_t)spec_lds_floats<LAYA, LAYB, BM, BN, BK, WM, EPI>() * sizeof(float);
@@ -658,7 +664,7 @@ int launch_one(GdGemm& g, hipStream_t s) {
     if constexpr (SPEC_OK) {
         // register stages of the loader waves: 2 (default) or 4 via GDMCF_SPEC_STAGES; measured 0.260 / 0.262 / 0.257
         // / 0.272 ms for 2 / 3 / 4 / 6 stages on the Yelp dW products -- the kernel is not load-latency bound
-        static const int nstg = getenv("GDMCF_SPEC_STAGES") ? atoi(getenv("GDMCF_SPEC_STAGES")) : 2;
+        static const int nstg = gd_env_int("GDMCF_SPEC_STAGES", 2);
         if (spec) {
             kern = gemm_f32_spec_kernel<LAYA, LAYB, BM, BN, BK, WM, WN, EPI, 2>;
             // (four stages of 32-deep tiles do not fit the loader waves' registers: with asm loads a spilled stage register
@@ -669,29 +675,7 @@ int launch_one(GdGemm& g, hipStream_t s) {
         }
     }
     static bool attr_set = false;
-    if (!attr_set && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            gdmcf_set_error("hipFuncSetAttribute(LDS=%zu): %s", lds, hipGetErrorString(e));
-            return GDMCF_E_HIP;
-        }
-        attr_set = true;
-    }
-    g.tiles_m = gd_cdiv(g.M, BM);
-    g.tiles_n = gd_cdiv(g.N, BN);
-    if (g.splits < 1) g.splits = 1;
-    if (g.kchunk <= 0) g.kchunk = gd_cdiv(gd_cdiv(g.K, g.splits), BK) * BK;
-    const long grid = (long)g.tiles_m * g.tiles_n * g.splits;
-    if (grid <= 0 || grid > 0x7fffffffL) {
-        gdmcf_set_error("gemm grid out of range: %ld", grid);
-        return GDMCF_E_SHAPE;
-    }
-    {
-        GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(spec ? 2 * NTHREADS : NTHREADS), lds, s, g);
-    }
-    return gd_launch_status("gemm_f32");
+    return gd_tiled_launch(kern, spec ? 2 * NTHREADS : NTHREADS, lds, 160 * 1024, BM, BN, BK, &attr_set, "gemm_f32", g, s);
 }
 
 template <int LAYA, int LAYB, int BK, int EPI>
@@ -704,6 +688,21 @@ int launch_class(int cls, GdGemm& g, hipStream_t s) {
     gdmcf_set_error("bad gemm shape class %d", cls);
     return GDMCF_E_ARG;
 }
+
+// a variant's tile depth (gd_gemm_bk; bk32: 32 for MC/MC STORE too), then its tile class
+struct ClassLauncher {
+    template <int LAYA, int LAYB, int EPI>
+    int operator()(bool bk32, int cls, GdGemm& g, hipStream_t s) const {
+        if constexpr (LAYA == GD_LAY_MC && LAYB == GD_LAY_MC) {
+            if constexpr (EPI == GD_EPI_STORE) {
+                if (bk32) return launch_class<LAYA, LAYB, 32, EPI>(cls, g, s);
+            }
+            return launch_class<LAYA, LAYB, 16, EPI>(cls, g, s);
+        } else {
+            return launch_class<LAYA, LAYB, 32, EPI>(cls, g, s);
+        }
+    }
+};
 
 }  // namespace
 
@@ -734,21 +733,6 @@ int gd_gemm_launch(int layA, int layB, int epi, int cls, GdGemm& g, hipStream_t 
     if (((layA == GD_LAY_KC || layB == GD_LAY_KC) && g.K < 4) || (layA == GD_LAY_MC && g.M < 4) ||
         (layB == GD_LAY_MC && g.N < 4))
         { t_gd_last_gemm = 9; return gd_gemm_small_launch(layA, layB, epi, g, s); }
-    if (layA == GD_LAY_KC && layB == GD_LAY_KC) {
-        switch (epi) {
-            case GD_EPI_SLAB: return launch_class<GD_LAY_KC, GD_LAY_KC, 32, GD_EPI_SLAB>(cls, g, s);
-            case GD_EPI_BIAS_ACT: return launch_class<GD_LAY_KC, GD_LAY_KC, 32, GD_EPI_BIAS_ACT>(cls, g, s);
-            case GD_EPI_LOSS: return launch_class<GD_LAY_KC, GD_LAY_KC, 32, GD_EPI_LOSS>(cls, g, s);
-            case GD_EPI_POST: return launch_class<GD_LAY_KC, GD_LAY_KC, 32, GD_EPI_POST>(cls, g, s);
-        }
-    } else if (layA == GD_LAY_KC && layB == GD_LAY_MC) {
-        if (epi == GD_EPI_SLAB) return launch_class<GD_LAY_KC, GD_LAY_MC, 32, GD_EPI_SLAB>(cls, g, s);
-    } else if (layA == GD_LAY_MC && layB == GD_LAY_MC) {
-        static const int tn_bk = getenv("GDMCF_TN_BK") ? atoi(getenv("GDMCF_TN_BK")) : 16;  // tuning knob
-        if (epi == GD_EPI_STORE && tn_bk == 32) return launch_class<GD_LAY_MC, GD_LAY_MC, 32, GD_EPI_STORE>(cls, g, s);
-        if (epi == GD_EPI_STORE) return launch_class<GD_LAY_MC, GD_LAY_MC, 16, GD_EPI_STORE>(cls, g, s);
-        if (epi == GD_EPI_ADAMW) return launch_class<GD_LAY_MC, GD_LAY_MC, 16, GD_EPI_ADAMW>(cls, g, s);
-    }
-    gdmcf_set_error("unsupported gemm variant (layA=%d layB=%d epi=%d)", layA, layB, epi);
-    return GDMCF_E_UNSUPPORTED;
+    static const int tn_bk = gd_env_int("GDMCF_TN_BK", 16);  // tuning knob: the k depth of the plain weight gradient's tiles
+    return gd_gemm_variant("", layA, layB, epi, ClassLauncher{}, tn_bk == 32, cls, g, s);
 }

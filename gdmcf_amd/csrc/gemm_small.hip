@@ -4,6 +4,7 @@
 // semantics as gemm_epilogue.h written per element.  Speed is irrelevant at these sizes; what matters is that every
 // shape the reference accepts produces a result (reference models/DNN.py:79-86 has no size restriction).
 #include "common.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -65,6 +66,16 @@ __global__ __launch_bounds__(256) void gemm_f32_small_kernel(const GdGemm g, int
     }
 }
 
+// (the kernel takes the layouts at run time: one instance per epilogue)
+struct SmallLauncher {
+    template <int LAYA, int LAYB, int EPI>
+    int operator()(const GdGemm& g, hipStream_t s) const {
+        GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
+        hipLaunchKernelGGL(gemm_f32_small_kernel<EPI>, dim3((unsigned)g.M), dim3(256), 0, s, g, LAYA, LAYB);
+        return GDMCF_OK;
+    }
+};
+
 }  // namespace
 
 // g.splits / g.kchunk / g.tiles_* are set so that the callers' reducers (one slab, one row-partial column) still apply
@@ -73,16 +84,6 @@ int gd_gemm_small_launch(int layA, int layB, int epi, GdGemm& g, hipStream_t s) 
     g.kchunk = g.K > 0 ? g.K : 1;
     g.tiles_m = g.M;
     g.tiles_n = 1;
-    const dim3 grid((unsigned)g.M), block(256);
-    GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
-    switch (epi) {
-        case GD_EPI_SLAB: hipLaunchKernelGGL(gemm_f32_small_kernel<GD_EPI_SLAB>, grid, block, 0, s, g, layA, layB); break;
-        case GD_EPI_BIAS_ACT: hipLaunchKernelGGL(gemm_f32_small_kernel<GD_EPI_BIAS_ACT>, grid, block, 0, s, g, layA, layB); break;
-        case GD_EPI_LOSS: hipLaunchKernelGGL(gemm_f32_small_kernel<GD_EPI_LOSS>, grid, block, 0, s, g, layA, layB); break;
-        case GD_EPI_POST: hipLaunchKernelGGL(gemm_f32_small_kernel<GD_EPI_POST>, grid, block, 0, s, g, layA, layB); break;
-        case GD_EPI_STORE: hipLaunchKernelGGL(gemm_f32_small_kernel<GD_EPI_STORE>, grid, block, 0, s, g, layA, layB); break;
-        case GD_EPI_ADAMW: hipLaunchKernelGGL(gemm_f32_small_kernel<GD_EPI_ADAMW>, grid, block, 0, s, g, layA, layB); break;
-        default: gdmcf_set_error("gemm_small: bad epilogue %d", epi); return GDMCF_E_ARG;
-    }
-    return gd_launch_status("gemm_f32_small");
+    const int rc = gd_gemm_variant("small ", layA, layB, epi, SmallLauncher{}, g, s);
+    return rc ? rc : gd_launch_status("gemm_f32_small");
 }

@@ -19,12 +19,12 @@
 // LDS image of a plane: rows of 32 bf16 = 64 bytes, four 16-byte slots, slot s of row r stored at s ^ (((r >> 3) & 1) << 1).
 // ds_read_b128 serves 16-lane groups that hold 8 rows at k-slot q and 8 rows at q+1 (MI355X_MICROARCH.md, LDS): with this
 // swizzle the 16 addresses fall on 16 distinct 16-byte columns of the 256-byte bank row.
-#include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -574,30 +574,9 @@ int launch_spec(GdGemm& g, hipStream_t s) {
     using Slot = RingSlot<LAYA, LAYB, BM, BN, 256>;
     constexpr int NSTG = (Slot::LOADS * 4 * 3 <= 150) ? 3 : 2;
     auto kern = gemm_split_spec_kernel<LAYA, LAYB, BM, BN, WM, WN, EPI, NSTG>;
+    static_assert(lds > 48 * 1024, "the limit is raised for every ring kernel: none fits the default");
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) {
-            gdmcf_set_error("hipFuncSetAttribute(LDS=%zu): %s", lds, hipGetErrorString(e));
-            return GDMCF_E_HIP;
-        }
-        attr_set = true;
-    }
-    g.tiles_m = gd_cdiv(g.M, BM);
-    g.tiles_n = gd_cdiv(g.N, BN);
-    if (g.splits < 1) g.splits = 1;
-    if (g.kchunk <= 0) g.kchunk = gd_cdiv(gd_cdiv(g.K, g.splits), BK) * BK;
-    const long grid = (long)g.tiles_m * g.tiles_n * g.splits;
-    if (grid <= 0 || grid > 0x7fffffffL) {
-        gdmcf_set_error("gemm grid out of range: %ld", grid);
-        return GDMCF_E_SHAPE;
-    }
-    {
-        GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, g);
-    }
-    return gd_launch_status("gemm_split_spec");
+    return gd_tiled_launch(kern, 512, lds, lds, BM, BN, BK, &attr_set, "gemm_split_spec", g, s);
 }
 
 template <int LAYA, int LAYB, int BM, int BN, int WM, int WN, int EPI, int MINWG>
@@ -605,34 +584,12 @@ int launch_one(GdGemm& g, hipStream_t s) {
     constexpr size_t lds = (size_t)PLANES * (BM + BN) * 64;
     auto kern = gemm_split_kernel<LAYA, LAYB, BM, BN, WM, WN, EPI, MINWG>;
     static bool attr_set = false;
-    if (!attr_set && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) {
-            gdmcf_set_error("hipFuncSetAttribute(LDS=%zu): %s", lds, hipGetErrorString(e));
-            return GDMCF_E_HIP;
-        }
-        attr_set = true;
-    }
-    g.tiles_m = gd_cdiv(g.M, BM);
-    g.tiles_n = gd_cdiv(g.N, BN);
-    if (g.splits < 1) g.splits = 1;
-    if (g.kchunk <= 0) g.kchunk = gd_cdiv(gd_cdiv(g.K, g.splits), BK) * BK;
-    const long grid = (long)g.tiles_m * g.tiles_n * g.splits;
-    if (grid <= 0 || grid > 0x7fffffffL) {
-        gdmcf_set_error("gemm grid out of range: %ld", grid);
-        return GDMCF_E_SHAPE;
-    }
-    {
-        GdProfScope prof(g.prof_tag, 2.0 * g.M * g.N * g.K, s);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * WM * WN), lds, s, g);
-    }
-    return gd_launch_status("gemm_split");
+    return gd_tiled_launch(kern, 64 * WM * WN, lds, lds, BM, BN, BK, &attr_set, "gemm_split", g, s);
 }
 
 template <int LAYA, int LAYB, int EPI>
 int launch_class(int cls, GdGemm& g, hipStream_t s) {
-    static const bool spec = !(getenv("GDMCF_SPLIT_SPEC") && atoi(getenv("GDMCF_SPLIT_SPEC")) == 0);  // A/B knob
+    static const bool spec = gd_env_int("GDMCF_SPLIT_SPEC", 1) != 0;  // A/B knob
     switch (cls) {
         case 0: return spec ? launch_spec<LAYA, LAYB, 80, 128, 1, 4, EPI>(g, s) : launch_one<LAYA, LAYB, 80, 128, 1, 4, EPI, 2>(g, s);
         case 1: return spec ? launch_spec<LAYA, LAYB, 128, 128, 2, 2, EPI>(g, s) : launch_one<LAYA, LAYB, 128, 128, 2, 2, EPI, 2>(g, s);
@@ -643,28 +600,19 @@ int launch_class(int cls, GdGemm& g, hipStream_t s) {
     return GDMCF_E_ARG;
 }
 
+struct ClassLauncher {
+    template <int LAYA, int LAYB, int EPI>
+    int operator()(int cls, GdGemm& g, hipStream_t s) const { return launch_class<LAYA, LAYB, EPI>(cls, g, s); }
+};
+
 }  // namespace
 
 int gd_gemm_split_launch(int layA, int layB, int epi, int cls, GdGemm& g, hipStream_t s) {
-    static const int dbg = getenv("GDMCF_SPLIT_DBG") ? atoi(getenv("GDMCF_SPLIT_DBG")) : 0;
+    static const int dbg = gd_env_int("GDMCF_SPLIT_DBG", 0);
     g.dbg = dbg;
     if (g.kchunk > 0 && g.kchunk % BK != 0) {
         gdmcf_set_error("gemm_split: kchunk %d is not a multiple of %d", g.kchunk, BK);
         return GDMCF_E_ARG;
     }
-    if (layA == GD_LAY_KC && layB == GD_LAY_KC) {
-        switch (epi) {
-            case GD_EPI_SLAB: return launch_class<GD_LAY_KC, GD_LAY_KC, GD_EPI_SLAB>(cls, g, s);
-            case GD_EPI_BIAS_ACT: return launch_class<GD_LAY_KC, GD_LAY_KC, GD_EPI_BIAS_ACT>(cls, g, s);
-            case GD_EPI_LOSS: return launch_class<GD_LAY_KC, GD_LAY_KC, GD_EPI_LOSS>(cls, g, s);
-            case GD_EPI_POST: return launch_class<GD_LAY_KC, GD_LAY_KC, GD_EPI_POST>(cls, g, s);
-        }
-    } else if (layA == GD_LAY_KC && layB == GD_LAY_MC) {
-        if (epi == GD_EPI_SLAB) return launch_class<GD_LAY_KC, GD_LAY_MC, GD_EPI_SLAB>(cls, g, s);
-    } else if (layA == GD_LAY_MC && layB == GD_LAY_MC) {
-        if (epi == GD_EPI_STORE) return launch_class<GD_LAY_MC, GD_LAY_MC, GD_EPI_STORE>(cls, g, s);
-        if (epi == GD_EPI_ADAMW) return launch_class<GD_LAY_MC, GD_LAY_MC, GD_EPI_ADAMW>(cls, g, s);
-    }
-    gdmcf_set_error("unsupported split gemm variant (layA=%d layB=%d epi=%d)", layA, layB, epi);
-    return GDMCF_E_UNSUPPORTED;
+    return gd_gemm_variant("split ", layA, layB, epi, ClassLauncher{}, cls, g, s);
 }

@@ -1,7 +1,10 @@
 // C-ABI entry points for the denoiser's dense layers: forward (plain / fused row-loss / fused
-// posterior mean) and backward (input grad, weight grad).  All of them drive gemm_f32.hip.
-#include <stdlib.h>
-
+// posterior mean) and backward (input grad, weight grad).  All of them drive gd_gemm_launch (gemm_f32.hip).
+//   pick_class, pick_class_dw, pick_splits   the tile class and the K splits of a product
+//   Product                                  a product as the kernels take it (GdGemm): the only place that describes one
+//   slab_plan, slab_product                  a product as split-K slabs + reducer; gdmcf_linear_ws_bytes sizes from the same plan
+//   loss_product, dw_product, BiasCol        what the two loss entries / the three weight-gradient entries share
+//   extern "C"                               the entries: argument checks, then the above
 #include "common.h"
 #include "tail_job.h"
 
@@ -15,7 +18,7 @@ namespace {
 
 // workgroups aimed at by the split-K heuristic: 256 CUs x 2 resident, times ~1.5 so the second wave of
 // workgroups evens out the tail (measured sweet spot on the batch-400 products; GDMCF_TARGET_WGS overrides)
-static const int TARGET_WGS = getenv("GDMCF_TARGET_WGS") ? atoi(getenv("GDMCF_TARGET_WGS")) : 760;
+static const int TARGET_WGS = gd_env_int("GDMCF_TARGET_WGS", 760);
 
 // input precision of the dense products issued by the calling thread (gdmcf_gemm_precision)
 thread_local int t_gemm_prec = GDMCF_GEMM_F32;
@@ -46,7 +49,7 @@ int pick_class(int M, int N, bool fused, int prec) {
 // both dimensions are large and the last round of workgroups is mostly full (measured 0.397 -> 0.374 ms on the
 // Amazon-Book shape; the kernel is bound by getting the f32 operands through L1, not by MFMA).
 int pick_class_dw(int M, int N, int prec, bool fused_adamw = false) {
-    static const int forced = getenv("GDMCF_BF16_DW_CLASS") ? atoi(getenv("GDMCF_BF16_DW_CLASS")) : -1;  // tuning knob
+    static const int forced = gd_env_int("GDMCF_BF16_DW_CLASS", -1);  // tuning knob
     if (prec == GDMCF_GEMM_BF16 && forced >= 0) return forced;
     // AdamW in the epilogue: the kernel is its optimiser stream (26 B per parameter) plus a short, latency-bound k loop that
     // nothing overlaps when one 208x256 workgroup owns the CU: three 80x128 workgroups per CU run one's k loop under the
@@ -58,28 +61,6 @@ int pick_class_dw(int M, int N, int prec, bool fused_adamw = false) {
         if (tiles * 100 >= rounds * 256 * 85) return 3;
     }
     return gd_pick_shape_class(M, N);
-}
-
-// bf16 mode: stream the operands from their registered bf16 shadows when both have one of exactly this shape
-// (operand stored [rows][K] for GD_LAY_KC, [K][rows] for GD_LAY_MC)
-// result written by a fused epilogue (BIAS_ACT without split-K, LOSS): keep its bf16 shadow in sync
-void attach_result_shadow(GdGemm& g) {
-    GdShadow c;
-    if (g.bf16 == 1 && gd_shadow_lookup(g.C, &c) && c.rows == g.M && c.cols >= g.N) {  // x_next lands in a wider xin buffer
-        g.C16 = c.p16;
-        g.ldc16 = c.ld16;
-    }
-}
-
-void attach_shadows(GdGemm& g, int layA, int layB) {
-    if (g.bf16 != 1) return;
-    GdShadow a, b;
-    if (!gd_shadow_lookup(g.A, &a) || !gd_shadow_lookup(g.B, &b)) return;
-    const bool okA = layA == GD_LAY_KC ? (a.rows == g.M && a.cols == g.K) : (a.rows == g.K && a.cols == g.M);
-    const bool okB = layB == GD_LAY_KC ? (b.rows == g.N && b.cols == g.K) : (b.rows == g.K && b.cols == g.N);
-    if (!okA || !okB) return;
-    g.A16 = a.p16; g.lda16 = a.ld16;
-    g.B16 = b.p16; g.ldb16 = b.ld16;
 }
 
 // number of K splits for an [M,N,K] product whose output is small (batch x hidden)
@@ -96,41 +77,165 @@ int pick_splits(int M, int N, int K, int cls, int prec) {
 
 inline int64_t round4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 
-// The bias gradient db[n] = sum_m rowscale[m] dZ[m, n] as column K of the weight-gradient product: possible when the caller
-// states (a_scale_col) that column K of the activation operand A holds rowscale[m] -- gdmcf_rowscale_f32 writes it there when its
-// output has room (ldo > K).  Nothing is remembered between calls.  Returns db when the request can be made, else NULL; a
-// launcher that takes the request clears GdGemm::out2.
-float* bias_col_request(int a_scale_col, int64_t lda, const float* rowscale, int K, float* db) {
-    static const int on = getenv("GDMCF_BIAS_COL") ? atoi(getenv("GDMCF_BIAS_COL")) : 1;
-    if (!on || !a_scale_col || db == nullptr || t_gemm_prec != GDMCF_GEMM_F32 || lda <= K) return nullptr;
-    return db;
+// The product C[M, N] = A B over a reduction of K in the calling thread's precision, operand X stored [rows][K] for layX ==
+// GD_LAY_KC and [K][rows] for GD_LAY_MC: the operands, the dimensions, one split, the tile order of class `cls` (the shorter grid
+// axis runs fastest) and the profiler tag, written here and nowhere else.  The entry adds what its epilogue reads to `g`.
+struct Product {
+    GdGemm g = {};
+    int layA, layB, cls;
+
+    Product(int layA_, int layB_, const float* A, int64_t lda, const float* B, int64_t ldb, int M, int N, int K, int cls_, int tag)
+        : layA(layA_), layB(layB_), cls(cls_) {
+        g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
+        g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K; g.splits = 1;
+        g.m_fastest = gd_cdiv(M, gd_gemm_tile_m(cls)) <= gd_cdiv(N, gd_gemm_tile_n(cls));
+        g.prof_tag = tag;
+        // bf16 mode: stream the operands from their registered bf16 shadows when both have one of exactly this shape
+        GdShadow a, b;
+        if (g.bf16 != 1 || !gd_shadow_lookup(A, &a) || !gd_shadow_lookup(B, &b)) return;
+        const bool okA = layA == GD_LAY_KC ? (a.rows == M && a.cols == K) : (a.rows == K && a.cols == M);
+        const bool okB = layB == GD_LAY_KC ? (b.rows == N && b.cols == K) : (b.rows == K && b.cols == N);
+        if (!okA || !okB) return;
+        g.A16 = a.p16; g.lda16 = a.ld16;
+        g.B16 = b.p16; g.ldb16 = b.ld16;
+    }
+
+    // the result as an epilogue writes it in place (not split-K slabs): in bf16 mode the kernel keeps C's bf16 shadow in sync
+    void result(float* C, int64_t ldc) {
+        g.C = C; g.ldc = ldc;
+        GdShadow c;
+        if (g.bf16 == 1 && gd_shadow_lookup(C, &c) && c.rows == g.M && c.cols >= g.N) {  // x_next lands in a wider xin buffer
+            g.C16 = c.p16;
+            g.ldc16 = c.ld16;
+        }
+    }
+
+    int launch(int epi, hipStream_t s) { return gd_gemm_launch(layA, layB, epi, cls, g, s); }
+};
+
+// ---- split-K slabs --------------------------------------------------------------------------------------------------------
+// An [M, N] product whose output is small against its reduction: `splits` partial products over K ranges into slabs
+// [splits][M][ld] of the caller's workspace, summed by gd_splitk_reduce with the layer's bias / activation / row scale.
+struct SlabPlan {
+    int cls, splits;
+    int64_t ld;
+};
+SlabPlan slab_plan(int M, int N, int K, int prec) {
+    const int cls = pick_class(M, N, false, prec);
+    return {cls, pick_splits(M, N, K, cls, prec), round4(N)};
 }
 
-// The product of one fused weight-gradient + AdamW call: dW[N x K_in] = dZ[M x N]^T A[M x K_in] -> gemm (N, K, reduction M),
-// both operands row-contiguous, W / exp_avg / exp_avg_sq updated in its epilogue
-int dw_adamw_setup(const GdDwAdamw& e, GdGemm& g, int& cls) {
+// what gd_splitk_reduce does with the sum (mode 0: bias + activation, the forward; 1: row scale and the activation's derivative)
+struct SlabReduce {
+    int mode;
+    const float* bias;
+    const float* rowscale;
+    const float* aact;
+    int64_t ldact;
+    int act;
+    float* out;
+    int64_t ldo;
+};
+
+// p as slabs in ws, then the reducer.  The kernel that takes the product may split further than the plan when ws_cap allows
+// (gdmcf_linear_ws_bytes sizes for it) and says so in g.kchunk.  job: a tail job that has to ride the launch, which only
+// dr_kn_kernel offers -- GD_DR_NOT_TAKEN and nothing launched where it does not take both.
+int slab_product(Product& p, const SlabPlan& plan, const char* who, void* ws, size_t ws_bytes, const GdTailJob* job,
+                 const SlabReduce& r, hipStream_t s) {
+    GdGemm& g = p.g;
+    const size_t need = (size_t)plan.splits * g.M * plan.ld * sizeof(float);
+    if (job) {
+        if (ws == nullptr) return GD_DR_NOT_TAKEN;  // (the kernel checks ws_cap against its own split count)
+    } else if (ws == nullptr || ws_bytes < need) {
+        gdmcf_set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+        return GDMCF_E_WORKSPACE;
+    }
+    g.splits = plan.splits; g.C = (float*)ws; g.ldc = plan.ld; g.slab_stride = (int64_t)g.M * plan.ld;
+    g.ws_cap = ws_bytes;
+    const int rc = job ? gd_dr_kn_launch_tail(g, *job, s) : p.launch(GD_EPI_SLAB, s);
+    if (rc) return rc;
+    return gd_splitk_reduce((const float*)ws, g.slab_stride, gd_cdiv(g.K, g.kchunk), plan.ld, g.M, g.N, r.mode, r.bias, r.rowscale,
+                            r.aact, r.ldact, r.act, r.out, r.ldo, s);
+}
+
+// floats of slab workspace an [M, N, K] product may use in precision prec: the plan's, or in float32 what the direct-to-register
+// kernel that takes it would split into (dr_kn_kernel: the input gradient and gdmcf_linear_fwd_wt_f32; fat: also the fat-tile slab
+// loop, the forward only)
+size_t slab_floats(int M, int N, int K, int prec, bool fat) {
+    const SlabPlan plan = slab_plan(M, N, K, prec);
+    int splits = plan.splits;
+    if (prec == GDMCF_GEMM_F32) {
+        const int kn = gd_dr_kn_splits(M, N, K), ft = fat ? gd_dr_fat_slab_plan(M, N, K, nullptr, nullptr) : 0;
+        splits = splits > kn ? splits : kn;
+        splits = splits > ft ? splits : ft;
+    }
+    return (size_t)splits * M * plan.ld;
+}
+
+// ---- the fused row loss ---------------------------------------------------------------------------------------------------
+// diff = alpha . (A W^T + bias) - target with its row sums of squares, the target as floats or as a bitmap of {0, 1} rows
+int loss_product(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* target, int64_t ldt,
+                 const uint32_t* target_bits, int64_t ldbits, const float* alpha, int M, int N, int K, float* out, int64_t ldo,
+                 float* diff, int64_t ldd, float* rowpart, float* rowsum, hipStream_t s) {
+    Product p(GD_LAY_KC, GD_LAY_KC, A, lda, W, ldw, M, N, K, pick_class(M, N, true, t_gemm_prec), 2);
+    GdGemm& g = p.g;
+    g.bias = bias; g.aux = target; g.ldaux = ldt; g.aux_bits = target_bits; g.ldbits = ldbits; g.r0 = alpha;
+    g.out2 = out; g.ldout2 = ldo; g.rowpart = rowpart; g.ld_rowpart = gdmcf_loss_tiles(N);
+    p.result(diff, ldd);
+    int rc = p.launch(GD_EPI_LOSS, s);
+    if (rc) return rc;
+    t_loss_parts = g.tiles_n;
+    if (rowsum == nullptr) return GDMCF_OK;  // the caller reduces (gdmcf_linear_bwd_input_tail_f32)
+    return gd_rowpart_reduce(rowpart, g.ld_rowpart, M, g.tiles_n, rowsum, s);
+}
+
+// ---- weight gradients -----------------------------------------------------------------------------------------------------
+// dW[N x K_in] = dZ[M x N]^T A[M x K_in] -> gemm (N, K, reduction M), both operands row-contiguous
+Product dw_product(const float* dZ, int64_t lddz, const float* A, int64_t lda, int M, int N, int K, bool fused_adamw) {
+    return Product(GD_LAY_MC, GD_LAY_MC, dZ, lddz, A, lda, N, K, M, pick_class_dw(N, K, t_gemm_prec, fused_adamw), 5);
+}
+
+// The bias gradient db[n] = sum_m rowscale[m] dZ[m, n] as column K of the weight-gradient product p: possible when the caller
+// states (a_scale_col) that column K of the activation operand A holds rowscale[m] -- gdmcf_rowscale_f32 writes it there when its
+// output has room (ldo > K).  Nothing is remembered between calls.  The request is GdGemm::out2 = db; a launcher that takes it
+// clears the field, and finish() runs the column sum where the product did not deliver.
+struct BiasCol {
+    const float* dZ = nullptr;
+    int64_t lddz = 0;
+    const float* rowscale = nullptr;
+    int M = 0, N = 0;
+    float* db = nullptr;
+    bool asked = false;
+
+    BiasCol() = default;
+    BiasCol(GdGemm& g, int a_scale_col, const float* rowscale_, float* db_)
+        : dZ(g.A), lddz(g.lda), rowscale(rowscale_), M(g.K), N(g.M), db(db_) {
+        static const int on = gd_env_int("GDMCF_BIAS_COL", 1);
+        asked = on && a_scale_col && db != nullptr && t_gemm_prec == GDMCF_GEMM_F32 && g.ldb > g.N;
+        g.out2 = asked ? db : nullptr;
+    }
+    int finish(const GdGemm& g, hipStream_t s) const {
+        if (asked && g.out2 == nullptr) return GDMCF_OK;  // db came out of the product
+        return db ? gd_colsum(dZ, lddz, rowscale, M, N, db, s) : GDMCF_OK;
+    }
+};
+
+int dw_adamw_check(const GdDwAdamw& e) {
     GD_CHECK_SHAPE(e.M > 0 && e.N > 0 && e.K > 0 && e.lddz >= e.N && e.lda >= e.K && e.ldw >= e.K, "linear_bwd_weight_adamw: bad shape");
     GD_CHECK_ARG(e.W && e.exp_avg && e.exp_avg_sq && e.step >= 1, "linear_bwd_weight_adamw: optimizer state missing");
-    const int M = e.M, N = e.N, K = e.K;
-    cls = pick_class_dw(N, K, t_gemm_prec, true);
-    g = GdGemm{};
-    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
-    g.A = e.dZ; g.lda = e.lddz; g.B = e.A; g.ldb = e.lda; g.M = N; g.N = K; g.K = M; g.splits = 1;
-    g.m_fastest = gd_cdiv(N, gd_gemm_tile_m(cls)) <= gd_cdiv(K, gd_gemm_tile_n(cls));
-    g.C = e.W; g.ldc = e.ldw; g.aux = e.exp_avg; g.aux2 = e.exp_avg_sq; g.prof_tag = 5;
-    g.adam = gd_adam_hyper(e.lr, e.beta1, e.beta2, e.eps, e.weight_decay, e.step, e.grad_scale);
-    g.adam_dev = t_gd_step_state ? &t_gd_step_state->hyper : nullptr;  // bound graph step state: the scalars of the step being replayed
-    attach_result_shadow(g);  // the bf16 kernels' row epilogue also refreshes W's bf16 shadow
-    attach_shadows(g, GD_LAY_MC, GD_LAY_MC);
-    g.out2 = bias_col_request(e.a_scale_col, e.lda, e.rowscale, K, e.db);
     return GDMCF_OK;
 }
 
-// after the product: the bias gradient, unless it came out of the product as its extra column
-int dw_adamw_finish(const GdDwAdamw& e, bool asked, const GdGemm& g, hipStream_t s) {
-    if (asked && g.out2 == nullptr) return GDMCF_OK;  // db came out of the product
-    if (e.db) return gd_colsum(e.dZ, e.lddz, e.rowscale, e.M, e.N, e.db, s);
-    return GDMCF_OK;
+// The product of one (checked) fused weight-gradient + AdamW call: W / exp_avg / exp_avg_sq updated in its epilogue, which in
+// the bf16 kernels also refreshes W's bf16 shadow
+Product dw_adamw_product(const GdDwAdamw& e, BiasCol& col) {
+    Product p = dw_product(e.dZ, e.lddz, e.A, e.lda, e.M, e.N, e.K, true);
+    p.result(e.W, e.ldw);
+    p.g.aux = e.exp_avg; p.g.aux2 = e.exp_avg_sq;
+    p.g.adam = gd_adam_hyper(e.lr, e.beta1, e.beta2, e.eps, e.weight_decay, e.step, e.grad_scale);
+    p.g.adam_dev = t_gd_step_state ? &t_gd_step_state->hyper : nullptr;  // bound graph step state: the scalars of the step being replayed
+    col = BiasCol(p.g, e.a_scale_col, e.rowscale, e.db);
+    return p;
 }
 
 }  // namespace
@@ -148,19 +253,7 @@ size_t gdmcf_linear_ws_bytes(int M, int N, int K) {
     // forward: slabs [splits][M][round4(N)];  backward-input: slabs [splits][M][round4(K)]
     size_t need = 0;
     for (int prec = GDMCF_GEMM_F32; prec <= GDMCF_GEMM_F32X3; ++prec) {  // the caller may switch precision later
-        const int cf = pick_class(M, N, false, prec), cb = pick_class(M, K, false, prec);
-        size_t f = (size_t)pick_splits(M, N, K, cf, prec) * M * round4(N);
-        if (prec == GDMCF_GEMM_F32) {  // gdmcf_linear_fwd_wt_f32 on dr_kn_kernel, gdmcf_linear_fwd_f32 on the fat-tile slab loop
-            const size_t fk = (size_t)gd_dr_kn_splits(M, N, K) * M * round4(N);
-            f = f > fk ? f : fk;
-            const size_t ff = (size_t)gd_dr_fat_slab_plan(M, N, K, nullptr, nullptr) * M * round4(N);
-            f = f > ff ? f : ff;
-        }
-        size_t b = (size_t)pick_splits(M, K, N, cb, prec) * M * round4(K);
-        if (prec == GDMCF_GEMM_F32) {  // the input gradient on dr_kn_kernel: one (split, tile) task per wave slot
-            const size_t bk = (size_t)gd_dr_kn_splits(M, K, N) * M * round4(K);
-            b = b > bk ? b : bk;
-        }
+        const size_t f = slab_floats(M, N, K, prec, true), b = slab_floats(M, K, N, prec, false);
         need = need > f ? need : f;
         need = need > b ? need : b;
     }
@@ -183,33 +276,14 @@ int gdmcf_linear_fwd_f32(const float* A, int64_t lda, const float* W, int64_t ld
     GD_CHECK_SHAPE(M > 0 && N > 0 && K > 0 && lda >= K && ldw >= K && ldc >= N, "linear_fwd: bad shape");
     GD_CHECK_ARG(act == 0 || act == 1, "linear_fwd: bad activation");
     hipStream_t s = (hipStream_t)stream;
-    const int cls = pick_class(M, N, false, t_gemm_prec);
-    const int splits = pick_splits(M, N, K, cls, t_gemm_prec);
-    GdGemm g = {};
-    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
-    g.A = A; g.lda = lda; g.B = W; g.ldb = ldw; g.M = M; g.N = N; g.K = K;
-    g.m_fastest = gd_cdiv(M, gd_gemm_tile_m(cls)) <= gd_cdiv(N, gd_gemm_tile_n(cls));
-    g.bias = bias; g.act = act; g.prof_tag = 1;
-    if (splits == 1) {
-        g.splits = 1; g.C = C; g.ldc = ldc;
-        attach_result_shadow(g);
-        attach_shadows(g, GD_LAY_KC, GD_LAY_KC);
-        return gd_gemm_launch(GD_LAY_KC, GD_LAY_KC, GD_EPI_BIAS_ACT, cls, g, s);
+    const SlabPlan plan = slab_plan(M, N, K, t_gemm_prec);
+    Product p(GD_LAY_KC, GD_LAY_KC, A, lda, W, ldw, M, N, K, plan.cls, 1);
+    p.g.bias = bias; p.g.act = act;
+    if (plan.splits == 1) {
+        p.result(C, ldc);
+        return p.launch(GD_EPI_BIAS_ACT, s);
     }
-    const int64_t lds_ = round4(N);
-    const size_t need = (size_t)splits * M * lds_ * sizeof(float);
-    if (ws == nullptr || ws_bytes < need) {
-        gdmcf_set_error("linear_fwd: workspace %zu < %zu bytes", ws_bytes, need);
-        return GDMCF_E_WORKSPACE;
-    }
-    g.splits = splits; g.C = (float*)ws; g.ldc = lds_; g.slab_stride = (int64_t)M * lds_;
-    g.ws_cap = ws_bytes;  // (the fat-tile slab loop splits further when the workspace allows: gdmcf_linear_ws_bytes sizes for it)
-    attach_shadows(g, GD_LAY_KC, GD_LAY_KC);
-    int rc = gd_gemm_launch(GD_LAY_KC, GD_LAY_KC, GD_EPI_SLAB, cls, g, s);
-    if (rc) return rc;
-    const int real_splits = gd_cdiv(K, g.kchunk);
-    return gd_splitk_reduce((const float*)ws, g.slab_stride, real_splits, lds_, M, N, 0, bias, nullptr, nullptr, 0,
-                            act, C, ldc, s);
+    return slab_product(p, plan, "linear_fwd", ws, ws_bytes, nullptr, {0, bias, nullptr, nullptr, 0, act, C, ldc}, s);
 }
 
 int gdmcf_linear_fwd_wt_f32(const float* A, int64_t lda, const float* Wt, int64_t ldwt, const float* bias, int act, int M, int N,
@@ -220,25 +294,10 @@ int gdmcf_linear_fwd_wt_f32(const float* A, int64_t lda, const float* Wt, int64_
         gdmcf_set_error("linear_fwd_wt: float32 GEMM mode only (the bf16 / f32x3 modes keep the weight in its own orientation)");
         return GDMCF_E_UNSUPPORTED;
     }
-    hipStream_t s = (hipStream_t)stream;
     // the product of the input gradient, with a forward reducer: [M x N] = A[M x K] * Wt[K x N], split over K
-    const int cls = pick_class(M, N, false, t_gemm_prec);
-    const int splits = pick_splits(M, N, K, cls, t_gemm_prec);
-    const int64_t lds_ = round4(N);
-    const size_t need = (size_t)splits * M * lds_ * sizeof(float);
-    if (ws == nullptr || ws_bytes < need) {
-        gdmcf_set_error("linear_fwd_wt: workspace %zu < %zu bytes", ws_bytes, need);
-        return GDMCF_E_WORKSPACE;
-    }
-    GdGemm g = {};
-    g.A = A; g.lda = lda; g.B = Wt; g.ldb = ldwt; g.M = M; g.N = N; g.K = K;
-    g.m_fastest = gd_cdiv(M, gd_gemm_tile_m(cls)) <= gd_cdiv(N, gd_gemm_tile_n(cls));
-    g.splits = splits; g.C = (float*)ws; g.ldc = lds_; g.slab_stride = (int64_t)M * lds_; g.prof_tag = 1;
-    g.ws_cap = ws_bytes;
-    int rc = gd_gemm_launch(GD_LAY_KC, GD_LAY_MC, GD_EPI_SLAB, cls, g, s);
-    if (rc) return rc;
-    const int real_splits = gd_cdiv(K, g.kchunk);
-    return gd_splitk_reduce((const float*)ws, g.slab_stride, real_splits, lds_, M, N, 0, bias, nullptr, nullptr, 0, act, C, ldc, s);
+    const SlabPlan plan = slab_plan(M, N, K, t_gemm_prec);
+    Product p(GD_LAY_KC, GD_LAY_MC, A, lda, Wt, ldwt, M, N, K, plan.cls, 1);
+    return slab_product(p, plan, "linear_fwd_wt", ws, ws_bytes, nullptr, {0, bias, nullptr, nullptr, 0, act, C, ldc}, (hipStream_t)stream);
 }
 
 int gdmcf_linear_loss_fwd_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
@@ -246,22 +305,8 @@ int gdmcf_linear_loss_fwd_f32(const float* A, int64_t lda, const float* W, int64
                               int64_t ldo, float* diff, int64_t ldd, float* rowpart, float* rowsum, void* stream) {
     GD_CHECK_SHAPE(M > 0 && N > 0 && K > 0 && lda >= K && ldw >= K && ldt >= N && ldd >= N, "linear_loss_fwd: bad shape");
     GD_CHECK_SHAPE(out == nullptr || ldo >= N, "linear_loss_fwd: ldo < N");
-    hipStream_t s = (hipStream_t)stream;
-    const int cls = pick_class(M, N, true, t_gemm_prec);
-    GdGemm g = {};
-    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
-    g.A = A; g.lda = lda; g.B = W; g.ldb = ldw; g.M = M; g.N = N; g.K = K; g.splits = 1;
-    g.m_fastest = gd_cdiv(M, gd_gemm_tile_m(cls)) <= gd_cdiv(N, gd_gemm_tile_n(cls));
-    g.bias = bias; g.aux = target; g.ldaux = ldt; g.r0 = alpha; g.out2 = out; g.ldout2 = ldo;
-    g.prof_tag = 2;
-    g.C = diff; g.ldc = ldd; g.rowpart = rowpart; g.ld_rowpart = gdmcf_loss_tiles(N);
-    attach_result_shadow(g);
-    attach_shadows(g, GD_LAY_KC, GD_LAY_KC);
-    int rc = gd_gemm_launch(GD_LAY_KC, GD_LAY_KC, GD_EPI_LOSS, cls, g, s);
-    if (rc) return rc;
-    t_loss_parts = g.tiles_n;
-    if (rowsum == nullptr) return GDMCF_OK;  // the caller reduces (gdmcf_linear_bwd_input_tail_f32)
-    return gd_rowpart_reduce(rowpart, g.ld_rowpart, M, g.tiles_n, rowsum, s);
+    return loss_product(A, lda, W, ldw, bias, target, ldt, nullptr, 0, alpha, M, N, K, out, ldo, diff, ldd, rowpart, rowsum,
+                        (hipStream_t)stream);
 }
 
 int gdmcf_linear_loss_fwd_bits_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
@@ -271,22 +316,8 @@ int gdmcf_linear_loss_fwd_bits_f32(const float* A, int64_t lda, const float* W, 
     GD_CHECK_SHAPE(M > 0 && N > 0 && K > 0 && lda >= K && ldw >= K && ldd >= N, "linear_loss_fwd_bits: bad shape");
     GD_CHECK_SHAPE(out == nullptr || ldo >= N, "linear_loss_fwd_bits: ldo < N");
     GD_CHECK_ARG(target_bits && ldbits >= (N + 31) / 32, "linear_loss_fwd_bits: target bitmap missing / ldbits < ceil(N/32)");
-    hipStream_t s = (hipStream_t)stream;
-    const int cls = pick_class(M, N, true, t_gemm_prec);
-    GdGemm g = {};
-    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
-    g.A = A; g.lda = lda; g.B = W; g.ldb = ldw; g.M = M; g.N = N; g.K = K; g.splits = 1;
-    g.m_fastest = gd_cdiv(M, gd_gemm_tile_m(cls)) <= gd_cdiv(N, gd_gemm_tile_n(cls));
-    g.bias = bias; g.aux = nullptr; g.ldaux = 0; g.aux_bits = target_bits; g.ldbits = ldbits; g.r0 = alpha; g.out2 = out;
-    g.ldout2 = ldo; g.prof_tag = 2;
-    g.C = diff; g.ldc = ldd; g.rowpart = rowpart; g.ld_rowpart = gdmcf_loss_tiles(N);
-    attach_result_shadow(g);
-    attach_shadows(g, GD_LAY_KC, GD_LAY_KC);
-    int rc = gd_gemm_launch(GD_LAY_KC, GD_LAY_KC, GD_EPI_LOSS, cls, g, s);
-    if (rc) return rc;
-    t_loss_parts = g.tiles_n;
-    if (rowsum == nullptr) return GDMCF_OK;  // the caller reduces (gdmcf_linear_bwd_input_tail_f32)
-    return gd_rowpart_reduce(rowpart, g.ld_rowpart, M, g.tiles_n, rowsum, s);
+    return loss_product(A, lda, W, ldw, bias, nullptr, 0, target_bits, ldbits, alpha, M, N, K, out, ldo, diff, ldd, rowpart, rowsum,
+                        (hipStream_t)stream);
 }
 
 int gdmcf_linear_posterior_fwd_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
@@ -297,18 +328,22 @@ int gdmcf_linear_posterior_fwd_f32(const float* A, int64_t lda, const float* W, 
     GD_CHECK_ARG(c1 && c2, "linear_posterior_fwd: c1/c2 missing");
     GD_CHECK_ARG((r1 == nullptr) == (r2 == nullptr), "linear_posterior_fwd: r1/r2 must both be set or both NULL");
     GD_CHECK_ARG(z == nullptr || (sigma != nullptr && ldz >= N), "linear_posterior_fwd: sigma missing");
-    hipStream_t s = (hipStream_t)stream;
-    const int cls = pick_class(M, N, true, t_gemm_prec);
-    GdGemm g = {};
-    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
-    g.A = A; g.lda = lda; g.B = W; g.ldb = ldw; g.M = M; g.N = N; g.K = K; g.splits = 1;
-    g.m_fastest = gd_cdiv(M, gd_gemm_tile_m(cls)) <= gd_cdiv(N, gd_gemm_tile_n(cls));
+    Product p(GD_LAY_KC, GD_LAY_KC, A, lda, W, ldw, M, N, K, pick_class(M, N, true, t_gemm_prec), 3);
+    GdGemm& g = p.g;
     g.bias = bias; g.aux = x_t; g.ldaux = ldxt; g.aux2 = z; g.ldaux2 = ldz;
     g.r0 = c1; g.r1 = c2; g.r2 = r1; g.r3 = r2; g.r4 = sigma;
-    g.out2 = pred_out; g.ldout2 = ldp; g.C = x_next; g.ldc = ldxn; g.prof_tag = 3;
-    attach_result_shadow(g);
-    attach_shadows(g, GD_LAY_KC, GD_LAY_KC);
-    return gd_gemm_launch(GD_LAY_KC, GD_LAY_KC, GD_EPI_POST, cls, g, s);
+    g.out2 = pred_out; g.ldout2 = ldp;
+    p.result(x_next, ldxn);
+    return p.launch(GD_EPI_POST, (hipStream_t)stream);
+}
+
+// product dims: [M x K_in] = dZ[M x N] * W[N x K_in]  -> gemm (M, K, reduction N); job: slab_product
+static int bwd_input(const char* who, const float* dZ, int64_t lddz, const float* W, int64_t ldw, const float* rowscale,
+                     const float* Aact, int64_t ldact, int act, int M, int N, int K, float* dA, int64_t ldda, void* ws,
+                     size_t ws_bytes, const GdTailJob* job, hipStream_t s) {
+    const SlabPlan plan = slab_plan(M, K, N, t_gemm_prec);
+    Product p(GD_LAY_KC, GD_LAY_MC, dZ, lddz, W, ldw, M, K, N, plan.cls, 4);
+    return slab_product(p, plan, who, ws, ws_bytes, job, {1, nullptr, rowscale, Aact, ldact, act, dA, ldda}, s);
 }
 
 int gdmcf_linear_bwd_input_f32(const float* dZ, int64_t lddz, const float* W, int64_t ldw, const float* rowscale,
@@ -316,28 +351,8 @@ int gdmcf_linear_bwd_input_f32(const float* dZ, int64_t lddz, const float* W, in
                                int64_t ldda, void* ws, size_t ws_bytes, void* stream) {
     GD_CHECK_SHAPE(M > 0 && N > 0 && K > 0 && lddz >= N && ldw >= K && ldda >= K, "linear_bwd_input: bad shape");
     GD_CHECK_ARG(act == 0 || (act == 1 && Aact && ldact >= K), "linear_bwd_input: activation output missing");
-    hipStream_t s = (hipStream_t)stream;
-    // product dims: [M x K_in] = dZ[M x N] * W[N x K_in]  -> gemm (M, K, reduction N)
-    const int cls = pick_class(M, K, false, t_gemm_prec);
-    const int splits = pick_splits(M, K, N, cls, t_gemm_prec);
-    const int64_t lds_ = round4(K);
-    const size_t need = (size_t)splits * M * lds_ * sizeof(float);
-    if (ws == nullptr || ws_bytes < need) {
-        gdmcf_set_error("linear_bwd_input: workspace %zu < %zu bytes", ws_bytes, need);
-        return GDMCF_E_WORKSPACE;
-    }
-    GdGemm g = {};
-    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
-    g.A = dZ; g.lda = lddz; g.B = W; g.ldb = ldw; g.M = M; g.N = K; g.K = N;
-    g.m_fastest = gd_cdiv(M, gd_gemm_tile_m(cls)) <= gd_cdiv(K, gd_gemm_tile_n(cls));
-    g.splits = splits; g.C = (float*)ws; g.ldc = lds_; g.slab_stride = (int64_t)M * lds_; g.prof_tag = 4;
-    g.ws_cap = ws_bytes;  // (the register-streaming kernel splits further when the workspace allows: gdmcf_linear_ws_bytes sizes for it)
-    attach_shadows(g, GD_LAY_KC, GD_LAY_MC);
-    int rc = gd_gemm_launch(GD_LAY_KC, GD_LAY_MC, GD_EPI_SLAB, cls, g, s);
-    if (rc) return rc;
-    const int real_splits = gd_cdiv(N, g.kchunk);
-    return gd_splitk_reduce((const float*)ws, g.slab_stride, real_splits, lds_, M, K, 1, nullptr, rowscale, Aact,
-                            ldact, act, dA, ldda, s);
+    return bwd_input("linear_bwd_input", dZ, lddz, W, ldw, rowscale, Aact, ldact, act, M, N, K, dA, ldda, ws, ws_bytes, nullptr,
+                     (hipStream_t)stream);
 }
 
 int gdmcf_loss_parts_last(void) { return t_loss_parts; }
@@ -371,12 +386,7 @@ int gdmcf_linear_bwd_input_tail_f32(const float* dZ, int64_t lddz, const float* 
     GD_CHECK_ARG(!t.rowscale_mean || t.gradcoef, "linear_bwd_input_tail: rowscale_mean needs gradcoef");
     GD_CHECK_ARG(lt_lds_bytes(t.T, t.H, M) <= GD_LT_LDS_MAX, "linear_bwd_input_tail: T*H and B too large for the LDS-resident FIFO update (150 KiB)");
     hipStream_t s = (hipStream_t)stream;
-    const int64_t lds_ = round4(K);
-    if (t_gemm_prec == GDMCF_GEMM_F32 && ws != nullptr) {  // the product as gdmcf_linear_bwd_input_f32 hands it to dr_kn_kernel
-        GdGemm g = {};
-        g.A = dZ; g.lda = lddz; g.B = W; g.ldb = ldw; g.M = M; g.N = K; g.K = N;
-        g.C = (float*)ws; g.ldc = lds_; g.slab_stride = (int64_t)M * lds_; g.prof_tag = 4;
-        g.ws_cap = ws_bytes;
+    if (t_gemm_prec == GDMCF_GEMM_F32) {  // the input gradient on dr_kn_kernel with the tail on its idle workgroup
         GdShadow sh;
         const bool has16 = gd_shadow_lookup(t.out, &sh) && sh.rows == M && sh.cols == t.Ka;  // as gdmcf_rowscale_f32
         GdTailJob j = {};
@@ -387,12 +397,8 @@ int gdmcf_linear_bwd_input_tail_f32(const float* dZ, int64_t lddz, const float* 
         j.loss = t.loss; j.loss_mean = t.loss_mean; j.rowscale_mean = t.rowscale_mean; j.inv_b = 1.0f / (float)M;
         j.K = t.Ka; j.A = t.A; j.lda = t.lda; j.rs = t.rowscale; j.out = t.out; j.ldo = t.ldo;
         j.out16 = has16 ? (unsigned short*)sh.p16 : nullptr; j.ldo16 = has16 ? sh.ld16 : 0; j.bias_col = t.ldo > t.Ka;
-        const int rc = gd_dr_kn_launch_tail(g, j, s);
-        if (rc != GD_DR_NOT_TAKEN) {
-            if (rc) return rc;
-            return gd_splitk_reduce((const float*)ws, g.slab_stride, gd_cdiv(N, g.kchunk), lds_, M, K, 1, nullptr, rowscale, Aact, ldact,
-                                    act, dA, ldda, s);
-        }
+        const int rc = bwd_input("linear_bwd_input_tail", dZ, lddz, W, ldw, rowscale, Aact, ldact, act, M, N, K, dA, ldda, ws, ws_bytes, &j, s);
+        if (rc != GD_DR_NOT_TAKEN) return rc;
     }
     const int rc = gdmcf_kn_tail_run(tail, M, stream);
     if (rc) return rc;
@@ -404,21 +410,11 @@ int gdmcf_linear_bwd_weight_f32(const float* dZ, int64_t lddz, const float* A, i
                                 void* stream) {
     GD_CHECK_SHAPE(M > 0 && N > 0 && K > 0 && lddz >= N && lda >= K && lddw >= K, "linear_bwd_weight: bad shape");
     hipStream_t s = (hipStream_t)stream;
-    // dW[N x K_in] = dZ[M x N]^T * A[M x K_in]  -> gemm (N, K, reduction M), both operands row-contiguous
-    const int cls = pick_class_dw(N, K, t_gemm_prec);
-    GdGemm g = {};
-    g.bf16 = t_gemm_prec;  // 0 f32, 1 bf16, 2 three-term split
-    g.A = dZ; g.lda = lddz; g.B = A; g.ldb = lda; g.M = N; g.N = K; g.K = M; g.splits = 1;
-    g.m_fastest = gd_cdiv(N, gd_gemm_tile_m(cls)) <= gd_cdiv(K, gd_gemm_tile_n(cls));
-    g.C = dW; g.ldc = lddw; g.accumulate = accumulate; g.prof_tag = 5;
-    attach_shadows(g, GD_LAY_MC, GD_LAY_MC);
-    g.out2 = bias_col_request(a_scale_col, lda, rowscale, K, db);
-    const bool asked = g.out2 != nullptr;
-    int rc = gd_gemm_launch(GD_LAY_MC, GD_LAY_MC, GD_EPI_STORE, cls, g, s);
-    if (rc) return rc;
-    if (asked && g.out2 == nullptr) return GDMCF_OK;  // db came out of the product
-    if (db) return gd_colsum(dZ, lddz, rowscale, M, N, db, s);
-    return GDMCF_OK;
+    Product p = dw_product(dZ, lddz, A, lda, M, N, K, false);
+    p.g.C = dW; p.g.ldc = lddw; p.g.accumulate = accumulate;  // (not result(): a gradient keeps no bf16 shadow)
+    const BiasCol col(p.g, a_scale_col, rowscale, db);
+    const int rc = p.launch(GD_EPI_STORE, s);
+    return rc ? rc : col.finish(p.g, s);
 }
 
 int gdmcf_linear_bwd_weight_adamw_f32(const float* dZ, int64_t lddz, const float* A, int64_t lda, const float* rowscale,
@@ -427,14 +423,12 @@ int gdmcf_linear_bwd_weight_adamw_f32(const float* dZ, int64_t lddz, const float
                                       int step, float grad_scale, void* stream) {
     const GdDwAdamw e = {dZ, lddz, A, lda, rowscale, a_scale_col, M, N, K, W, ldw, exp_avg, exp_avg_sq, db,
                          lr, beta1, beta2, eps, weight_decay, step, grad_scale};
-    GdGemm g;
-    int cls;
-    int rc = dw_adamw_setup(e, g, cls);
+    int rc = dw_adamw_check(e);
     if (rc) return rc;
-    const bool asked = g.out2 != nullptr;
-    rc = gd_gemm_launch(GD_LAY_MC, GD_LAY_MC, GD_EPI_ADAMW, cls, g, (hipStream_t)stream);
-    if (rc) return rc;
-    return dw_adamw_finish(e, asked, g, (hipStream_t)stream);
+    BiasCol col;
+    Product p = dw_adamw_product(e, col);
+    rc = p.launch(GD_EPI_ADAMW, (hipStream_t)stream);
+    return rc ? rc : col.finish(p.g, (hipStream_t)stream);
 }
 
 int gdmcf_linear_bwd_weight_adamw_multi_f32(const GdDwAdamw* list, int n, void* stream) {
@@ -444,12 +438,11 @@ int gdmcf_linear_bwd_weight_adamw_multi_f32(const GdDwAdamw* list, int n, void* 
     for (int i0 = 0; i0 < n; i0 += MAXN) {
         const int k = n - i0 < MAXN ? n - i0 : MAXN;
         GdGemm g[MAXN];
-        bool asked[MAXN];
-        int cls;
+        BiasCol col[MAXN];
         for (int j = 0; j < k; ++j) {
-            const int rc = dw_adamw_setup(list[i0 + j], g[j], cls);
+            const int rc = dw_adamw_check(list[i0 + j]);
             if (rc) return rc;
-            asked[j] = g[j].out2 != nullptr;
+            g[j] = dw_adamw_product(list[i0 + j], col[j]).g;
         }
         int rc = gd_gemm_dr_adamw_multi(g, k, s);
         if (rc == GD_DR_NOT_TAKEN) {  // one call per product
@@ -464,7 +457,7 @@ int gdmcf_linear_bwd_weight_adamw_multi_f32(const GdDwAdamw* list, int n, void* 
         }
         if (rc) return rc;
         for (int j = 0; j < k; ++j) {
-            rc = dw_adamw_finish(list[i0 + j], asked[j], g[j], s);
+            rc = col[j].finish(g[j], s);
             if (rc) return rc;
         }
     }

@@ -386,7 +386,7 @@ template <int LPR>
 void launch_bundle(int n_blocks, hipStream_t s, const SpmmBundlePlan& pl, const int32_t* col, const float* val, int64_t nnz,
                    const float* X, int64_t ldx, int n_x_rows, float* Y, int64_t ldy, float* partial, int d, const SpmmAdd& add,
                    const int32_t* crow, const int32_t* cptr, int n_cut) {
-    static const int unr = getenv("GDMCF_SPMM_UN") ? atoi(getenv("GDMCF_SPMM_UN")) : 4;  // tuning knob
+    static const int unr = gd_env_int("GDMCF_SPMM_UN", 4);  // tuning knob
     const bool wide = (double)n_x_rows * (double)ldx * 4.0 >= 4294967296.0 || ldx * 4 >= (int64_t)1 << 31;
 #define GD_K(U, W) hipLaunchKernelGGL((spmm_bundle_kernel<LPR, U, W>), dim3(n_blocks), dim3(256), 0, s, pl, col, val, nnz, X, ldx, Y, ldy, partial, d, add)
     if (wide) {
@@ -483,7 +483,7 @@ extern "C" int gdmcf_spmm_stream_f32(const int32_t* wdesc, int n_waves, const in
     hipStream_t s = (hipStream_t)stream;
     const int n_blocks = n_waves / 4;
     const bool wide = (double)n_x_rows * (double)ldx * 4.0 >= 4294967296.0 || ldx * 4 >= (int64_t)1 << 31;
-    static const int dbg = getenv("GDMCF_SPMM_DBG") ? atoi(getenv("GDMCF_SPMM_DBG")) : 0;  // ablation switches (tools/spmm_probe2.py)
+    static const int dbg = gd_env_int("GDMCF_SPMM_DBG", 0);  // ablation switches (tools/spmm_probe2.py)
     {
         GdProfScope prof(8, alg_bytes, s);
 #define GD_GO(L)                                                                                                                        \

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "common.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -201,17 +202,7 @@ __device__ __forceinline__ void gd_tail_job_run(const GdTailJob& j, unsigned cha
 
 // dynamic LDS of the FIFO update (lt_history_parallel): T*H doubles, 2 T ints, B ints
 inline size_t lt_lds_bytes(int T, int H, int B) { return (size_t)T * H * 8 + (size_t)T * 8 + (size_t)B * 4 + 16; }
-constexpr size_t GD_LT_LDS_MAX = 150 * 1024;  // what the loss tail's entries accept
-
-// raises `kernel`'s dynamic-LDS limit when `lds` needs more than the default 48 KiB, once per kernel (*done: the caller's static
-// flag).  T = 1000 diffusion steps x 10 history entries need 88 KB.
-template <class K>
-bool gd_allow_big_lds(K* kernel, size_t lds, bool* done, const char* who) {
-    if (*done || lds <= 48 * 1024) return true;
-    *done = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-    if (!*done) gdmcf_set_error("%s: hipFuncSetAttribute failed", who);
-    return *done;
-}
+constexpr size_t GD_LT_LDS_MAX = 150 * 1024;  // what the loss tail's entries accept (their kernels: gd_allow_big_lds, gemm_launch.h)
 
 }  // namespace
 

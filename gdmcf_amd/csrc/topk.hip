@@ -373,7 +373,7 @@ int topk_launch(const char* what, const float* pred, int64_t ldp, int B, int I, 
     const size_t lds_base = (size_t)KP * 8 + (256 + 24) * 4 + (size_t)((I + 31) / 32) * 4;
     GdProfScope prof(9, 4.0 * B * (double)I, stream);  // (both launches)
     // the fast path (topk_fast_kernel): rows up to 40 960 wide, k <= 256 -- followed by topk_kernel for the rows it marks
-    static const int fast_on = getenv("GDMCF_TOPK_FAST") ? atoi(getenv("GDMCF_TOPK_FAST")) : 1;  // 0: the radix-select kernel only
+    static const int fast_on = gd_env_int("GDMCF_TOPK_FAST", 1);  // 0: the radix-select kernel only
     const bool fast = fast_on && k <= 256 && I <= 1024 * 40 && k <= I;
     if (fast) {
         const size_t lds_f = (size_t)TOPK_FAST_CAP * 8 + (1024 + 4) * 4 + (size_t)((I + 31) / 32) * 4;
