@@ -140,7 +140,8 @@ __global__ __launch_bounds__(256) void prep_rowss_kernel(PrepArgs a, float* __re
         float v[4];
         xt4(a, b, col, ca, cb, v);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ss += v[j] * v[j];
+        for (int j = 0; j < 4; ++j)
+            if (col + j < a.I) ss += v[j] * v[j];  // (in-kernel noise draws all four normals of a ragged group: x_t past I is not 0)
     }
     __shared__ float red[4];
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
@@ -178,7 +179,7 @@ __device__ __forceinline__ void prep_input_body(PrepArgs a, const OneHotSrc o) {
         for (int64_t k = beg + threadIdx.x; k < end; k += 256) {
             const int ci = a.csr_indices[k];
             const int c = ci - first;
-            if (c >= 0 && c < SPAN && (SRC == 0 || ci < o.items)) atomicOr(&s_bm[c >> 5], 1u << (c & 31));
+            if (c >= 0 && c < SPAN && ci < (SRC == 1 ? o.items : a.I)) atomicOr(&s_bm[c >> 5], 1u << (c & 31));
         }
         __syncthreads();
         if (a.bits_out && threadIdx.x < SPAN / 32) {

@@ -135,6 +135,8 @@ int gdmcf_dnn_prep_input_f32(const float* x, int64_t ldx, const int64_t* ts, con
  * 4096 columns of the row in an LDS bitmap and builds x_t = ca*x0 + cb*noise, dropout, the embedding columns from it
  * (same arithmetic and the same Philox streams as the dense entry: identical xin).  bits_out (optional, uint32
  * [B, ldbits], ldbits >= ceil(I/32)) receives the rows as bitmaps -- the target of gdmcf_linear_loss_fwd_bits_f32.
+ * Indices outside [0, I) are ignored, as gdmcf_densify_rows_f32 skips them: they add nothing to xin and set no bit of
+ * bits_out (every bit >= I of a written word is zero); an index stored twice counts once.
  * No F.normalize here (it needs the dense row twice): densify (gdmcf_densify_rows_f32) and use the dense entry.        */
 int gdmcf_dnn_prep_input_csr_f32(const int64_t* indptr, const int32_t* indices, const int64_t* rows, const int64_t* ts,
                                  const float* ca, const float* cb, int noise_mode, const float* noise, int64_t ldn,
